@@ -11,6 +11,10 @@ three buckets in the order the backward pass finishes them, overlapped with it: 
 LJSpeech-shaped batch of 32 utterances per GPU (BASELINE.json configs[1]; weak scaling).  Prints ONE JSON line on rank 0.
 The run FAILS (non-zero exit, no JSON line) if the process group's world size is not N or fewer than N devices are visible:
 `n_gpus` is what the process group says, never the flag.
+
+A plain run does what the headline needs: set-up, warm-up, the timed steps, the JSON line.  --full adds the rest: live HIP-event
+timing of the dominant recurrent kernel and its `roofline`, the latest profiled GEMM roofline table, the free-running decode
+(BASELINE config 5) and the PyTorch-CPU baseline.  --dump-outputs DIR writes what the last timed step computed (see dump_outputs).
 """
 import argparse
 import json
@@ -111,7 +115,7 @@ def _cpu_baseline_worker():
 
 def cpu_baseline(timeout_s=400):
     """The oracle's PyTorch-CPU restatement (kind 'port') timed on this host in a child process with a hard
-    timeout, so the default bench run always finishes within minutes."""
+    timeout, so a --full bench run always finishes within minutes."""
     import subprocess
     try:
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--cpu-baseline-worker"], capture_output=True,
@@ -169,6 +173,59 @@ def decode_bench(eng, steps=200, Ti=100):
             "ms_per_step": ms / steps, "mel_frames_per_sec": steps * r / (ms * 1e-3),
             "realtime_factor": (ms * 1e-3) / (steps * r * 0.0125),
             "launches_per_step": (1.0 / ses.K) if ses.mega is not None else max(x.kernel_launches for x in eng._decode_sessions.values())}
+
+
+DUMP_CAP = 1 << 20            # elements per dumped array (4 MiB): at most 12 arrays reach it, the others are losses
+DUMP_LIMIT = 64 << 20         # bytes of all dumped arrays together
+
+
+def _carried_state(eng):
+    """the device tensors one train step + update hands to the next: parameters, Adam moments, optimiser scratch (without its
+    two sticky skip counters, which the result line reports), the step counter of the rate schedule, the dropout / zoneout
+    seed (the update advances both) and the BatchNorm moving statistics.  The bf16 shadows are derived from the parameters."""
+    return [eng.flat, eng.m, eng.v, eng.opt_state[:-2], eng.step_dev, eng.seed] + [t for pair in eng.bn.values() for t in pair]
+
+
+def snapshot_state(eng):
+    return [t.clone() for t in _carried_state(eng)], eng.global_step
+
+
+def restore_state(eng, snap):
+    """--dump-outputs: put the engine back into the state of `snap` before the last timed step.  The float atomics of the step
+    (split-K GEMMs, column sums) make every step reproducible to rounding only; through Adam and the bf16 weight shadows such
+    differences grow from step to step, so the last of many steps would not start from the same inputs in every run.  From
+    the restored state it does, and two runs (or two builds) with the same arguments compute the same step."""
+    eng._wait_recurrent_shadows()         # the shadow refresh of the last update reads the parameters: let it finish first
+    for t, s in zip(_carried_state(eng), snap[0]):
+        t.copy_(s)
+    eng.global_step = snap[1]
+    eng._refresh_shadows_async()
+
+
+def dump_outputs(eng, ctx, out_dir):
+    """--dump-outputs: what the last timed step computed, as <out_dir>/<name>.npy in float32: the step's results (Engine.outputs:
+    spectrogram, stop logits, alignments, layer outputs, losses), the updated parameters (`params`, the flat fp32 buffer) and the
+    gradient (`grad`).  An array of more than DUMP_CAP elements is written as DUMP_CAP of its elements, flattened, at sorted
+    positions drawn without replacement by numpy's default_rng(0): the same positions in every run of the same configuration."""
+    import numpy as np
+    import torch
+    arrays = {k: v for k, v in eng.outputs(ctx).items() if torch.is_tensor(v)}
+    arrays.update(params=eng.flat, grad=eng.grad)
+    torch.cuda.synchronize()
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() > DUMP_CAP:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_CAP, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        host[name] = t.cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    _log("wrote %d arrays (%.1f MB) to %s" % (len(host), total / 1e6, out_dir))
 
 
 def _free_port():
@@ -229,12 +286,18 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=32, help="utterances per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-decode", action="store_true", help="skip the free-running decode measurement (BASELINE config 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel HIP-event timing and the roofline of the "
+                         "dominant kernel, the GEMM roofline table, the decode measurement and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32); that "
+                         "step starts from the state set-up left, so runs with the same arguments compute the same step")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the PyTorch-CPU baseline")
+    ap.add_argument("--no-decode", action="store_true", help="(--full) skip the free-running decode measurement (BASELINE config 5)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--chunks", type=int, default=None, help="time chunks of the recurrent stream pipeline")
     ap.add_argument("--time-all-kernels", action="store_true",
-                    help="HIP-event brackets around all eight recurrent kernel families instead of the two attention "
+                    help="(--full) HIP-event brackets around all eight recurrent kernel families instead of the two attention "
                          "kernels only (70 instead of 4 events per step: costs ~0.1 ms per step)")
     ap.add_argument("--chunked-attention", action="store_true",
                     help="one attention launch per pipeline chunk instead of one per direction (for counter-"
@@ -251,6 +314,8 @@ def main():
     ap.add_argument("--force-dist", action="store_true", help=argparse.SUPPRESS)     # diagnostics: a one-rank RCCL group at N=1
     ap.add_argument("--dry-run", action="store_true", help=argparse.SUPPRESS)        # test hook: the N-rank plumbing without the engine
     args = ap.parse_args()
+    if args.time_all_kernels and not args.full:
+        ap.error("--time-all-kernels selects the per-kernel timing of --full: give --full as well")
     if args.cpu_baseline_worker:
         return _cpu_baseline_worker()
     if args.gpus < 1:
@@ -308,6 +373,7 @@ def main():
            "vctk": lambda: ModelConfig(num_speakers=152, speaker_offset=225)}[args.model]()
     eng = Engine(cfg, "cuda:%d" % local, param_seed=0, rng_seed=1234)
     dp.bind(eng.grad)
+    snap = snapshot_state(eng) if args.dump_outputs else None     # the state the dumped step starts from (see restore_state)
     if args.chunks:
         eng.pipeline_chunks = args.chunks
     if args.tail:
@@ -329,10 +395,11 @@ def main():
         eng.optimizer_step(grad_scale=1.0 / world)
         return ctx
 
-    # The per-kernel HIP-event timing below keeps ~70 timing events per step alive until the summary; the runtime
+    # The per-kernel HIP-event timing below (--full) keeps ~70 timing events per step alive until the summary; the runtime
     # grows its pool of profiling signals in one ~40 ms host stall when that happens inside the timed steps (measured:
-    # one 23 ms step among 11.6 ms ones).  Grow the pool here, before the warm-up, instead: instrumentation only.
-    pool = [torch.cuda.Event(enable_timing=True) for _ in range(80 * args.steps + 256)]
+    # one 23 ms step among 11.6 ms ones).  Grow the pool here, before the warm-up, instead: instrumentation only.  A plain
+    # run keeps the step marks and, for N > 1, the all-reduce brackets (up to 8 per step) alive.
+    pool = [torch.cuda.Event(enable_timing=True) for _ in range((80 if args.full else 10) * args.steps + 256)]
     for e in pool:
         e.record()
     torch.cuda.synchronize()
@@ -342,18 +409,21 @@ def main():
         step()
         if i == 0:
             torch.cuda.synchronize(); _log("first step done")
-    eng.timing = {}
+    if args.full:
+        eng.timing = {}
+        if not args.time_all_kernels:     # the dominant kernel only (backward attention loop)
+            eng.timing_names = {"attn_rnn_bwd"}       # (every bracket is two marker packets on the launching stream, ~5 us each)
     if dp.active:
         dp.timing = []
-    if not args.time_all_kernels:     # the dominant kernel only (backward attention loop)
-        eng.timing_names = {"attn_rnn_bwd"}       # (every bracket is two marker packets on the launching stream, ~5 us each)
     dp.barrier(); torch.cuda.synchronize()
     skipped0 = [int(float(v)) for v in eng.opt_state[-2:].tolist()]     # sticky device counters: updates skipped / for a non-finite gradient
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     marks[0].record()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step()
+        if snap is not None and i == args.steps - 1:
+            restore_state(eng, snap)       # (one device copy of the ~75 MB state, inside the timed region)
+        ctx = step()
         marks[i + 1].record()
     torch.cuda.synchronize(); dp.barrier()
     dt = time.perf_counter() - t0
@@ -370,6 +440,8 @@ def main():
     # an update the device skipped (a cluster kernel's exchange time-out poisons the step's gradient; a non-finite gradient) would make
     # a timed step cheaper than a real one: counted on the device, reported, and the line says so when it is not zero
     skipped = [int(float(v)) - v0 for v, v0 in zip(eng.opt_state[-2:].tolist(), skipped0)]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(eng, ctx, args.dump_outputs)
 
     if rank == 0:
         ms = 1e3 * dt / args.steps
@@ -429,7 +501,6 @@ def main():
             "step_tflops": step_tflops, "step_frac_of_bf16_peak": step_tflops / (PEAK_BF16_TFLOPS * world),
             "loss": loss,
             "skipped_updates": {"timed_steps": args.steps, "skipped": skipped[0], "non_finite": skipped[1]},
-            "kernel_ms_per_step": {k: round(v, 4) for k, v in sorted(per_step.items())},
             # N > 1: time inside the two gradient-bucket all-reduces (HIP events on their issuing streams; includes waiting for
             # the slowest peer) and the part of it the optimiser's stream actually stalled for (events around its wait)
             "allreduce_ms": (ar_ms / args.steps) if dp.active else None,
@@ -442,16 +513,18 @@ def main():
                                                              ([eng.nparam - eng.enc_end, eng.enc_end - eng.enc_mid, eng.enc_mid]
                                                               if eng.dp_buckets >= 3 else [eng.nparam - eng.enc_end, eng.enc_end])],
                    "wire": "bf16" if dp.bf16_wire else "fp32"} if dp.active else None,
-            "roofline": roof,
         }
-        gfile = _latest_profile("gemm_roofline.txt")
-        if gfile:       # per-shape GEMM roofline table of the latest round (tools/bench_gemm.py on the GPU box)
-            tail = [ln.strip() for ln in open(gfile).read().splitlines() if ln.startswith(("sum:", "roofline fraction"))]
-            line["gemm_roofline"] = {"source": "profiles/" + os.path.basename(gfile), "summary": tail}
-        if world == 1 and not args.no_decode:
-            line["decode"] = decode_bench(eng)
-        if world == 1 and not args.no_cpu_baseline and args.model == "self-attention-tacotron":
-            line["cpu_baseline"] = cpu_baseline()
+        if args.full:
+            line["kernel_ms_per_step"] = {k: round(v, 4) for k, v in sorted(per_step.items())}
+            line["roofline"] = roof
+            gfile = _latest_profile("gemm_roofline.txt")
+            if gfile:       # per-shape GEMM roofline table of the latest round (tools/bench_gemm.py, measured on the GPU)
+                tail = [ln.strip() for ln in open(gfile).read().splitlines() if ln.startswith(("sum:", "roofline fraction"))]
+                line["gemm_roofline"] = {"source": "profiles/" + os.path.basename(gfile), "summary": tail}
+            if world == 1 and not args.no_decode:
+                line["decode"] = decode_bench(eng)
+            if world == 1 and not args.no_cpu_baseline and args.model == "self-attention-tacotron":
+                line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line))
     dp.shutdown()
 

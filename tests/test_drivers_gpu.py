@@ -1,4 +1,4 @@
-"""train.py / predict_mel.py with the reference's command lines on a tiny on-disk corpus (LJSpeech config)."""
+"""train.py / predict_mel.py with the reference's command lines on a tiny on-disk corpus (LJSpeech config); bench.py's plain run."""
 import os
 import subprocess
 import sys
@@ -337,3 +337,36 @@ def test_poison_on_error_makes_the_skip_global():
     assert torch.equal(eng.flat, p1) and torch.equal(eng.m, m1)
     ctx = eng.train_step(b); eng.optimizer_step()                 # and a finite gradient updates again
     assert not torch.equal(eng.flat, p1)
+
+
+def test_bench_plain_run_and_its_dumped_outputs(tmp_path):
+    """a plain `bench.py` run prints the headline line without the figures of --full, and --dump-outputs writes the last timed
+    step's arrays (float32, 64 MB at most; `params` is larger than the cap and is sampled).  The dumped step starts from the
+    state set-up left (bench.py restore_state), so two runs with the same arguments - and a run whose only step is that first
+    one - compute the same step: only reordered float sums may differ (the 1e-4 bar of
+    test_identical_steps_give_identical_gradients, relative to each array's largest element)."""
+    import json
+    runs = []
+    for k, (steps, warmup) in enumerate(((3, 2), (3, 2), (1, 0))):
+        d = tmp_path / ("run%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--batch",
+                            "8", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        line = json.loads(lines[0])
+        assert line["steps"] == steps and line["warmup"] == warmup and line["ms_per_step"] > 0 and line["unit"] == "mel-frames/sec"
+        assert not {"kernel_ms_per_step", "roofline", "gemm_roofline", "decode", "cpu_baseline"} & set(line)
+        arrays = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+        assert {"mel", "stop", "alignment1", "alignment2", "loss", "params", "grad"} <= set(arrays)
+        assert all(a.dtype == np.float32 for a in arrays.values()) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["mel"].shape == (8, 800, 80) and arrays["params"].shape == (1 << 20,)
+        assert float(arrays["loss"]) == line["loss"] and all(np.isfinite(a).all() for a in arrays.values())
+        runs.append(arrays)
+    a = runs[0]
+    for b in runs[1:]:
+        assert a.keys() == b.keys()
+        rel = {k: float(np.abs(a[k] - b[k]).max() / (np.abs(a[k]).max() + 1e-30)) for k in a}
+        print("largest difference / largest element:", max(rel.values()))
+        bad = {k: e for k, e in rel.items() if e > 1e-4}
+        assert not bad, bad

@@ -10,6 +10,7 @@ import re
 import shutil
 import struct
 import subprocess
+import tempfile
 import time
 
 import numpy as np
@@ -32,7 +33,7 @@ def hp(**kw):
     return h
 
 
-def test_library_exports_every_symbol_of_the_header_and_the_struct_layouts_match():
+def test_library_exports_every_symbol_of_the_header_and_the_struct_layouts_match(tmp_path):
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "satt_io.h")).read(), flags=re.S)
     syms = sorted(set(re.findall(r"\b(satt_[a-z0-9_]+)\s*\(", txt)))
     l = _io.lib()
@@ -46,8 +47,7 @@ def test_library_exports_every_symbol_of_the_header_and_the_struct_layouts_match
 #include "satt_io.h"
 int main() { printf("%zu %zu %zu %zu %zu\n", sizeof(satt_example_feature), offsetof(satt_example_feature, first_int),
                     sizeof(satt_utterance), offsetof(satt_utterance, mel_off), offsetof(satt_utterance, prepared_length)); return 0; }'''
-    d = "/tmp/satt_io_struct_test"
-    os.makedirs(d, exist_ok=True)
+    d = str(tmp_path)
     open(os.path.join(d, "t.c"), "w").write(src)
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "t.c"), "-o", os.path.join(d, "t")])
     got = [int(x) for x in subprocess.check_output([os.path.join(d, "t")]).split()]
@@ -353,9 +353,7 @@ def test_pipeline_sustains_the_rate_the_train_step_consumes():
     one: the test measures the pipeline's CPU cost, not this container's disk (whose page cache is reclaimed within seconds).
     Measured here (8 vCPUs): ~4 300 utt/s with one reader thread, 6 000 - 7 000 with 2 - 4 (profiles/r04_input_pipeline.txt)."""
     base = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else "/tmp"
-    d = os.path.join(base, "satt_pipeline_rate_test")
-    shutil.rmtree(d, ignore_errors=True)
-    os.makedirs(d)
+    d = tempfile.mkdtemp(prefix="satt_pipeline_rate_test_", dir=base)
     try:
         src, tgt = _corpus(d, 512, frames=(700, 796), seed=1)
         h = hp(outputs_per_step=2, batch_size=32, max_iters=500, average_mel_level_db=[-40.0] * 80, stddev_mel_level_db=[10.0] * 80)

@@ -38,7 +38,7 @@ def test_build_and_exports():
     assert b"bad argument" in lib.satt_strerror(-1)
 
 
-def test_struct_layouts_match_c():
+def test_struct_layouts_match_c(tmp_path):
     """sizeof / offsetof of the ctypes mirrors == the C structs (compiled with the host compiler)."""
     from satt_amd import _lib
     src = r'''
@@ -56,8 +56,7 @@ int main() {
   printf("%zu %zu %zu %zu %zu\n", sizeof(satt_dec_mega_params), offsetof(satt_dec_mega_params, zc), offsetof(satt_dec_mega_params, Wp0),
          offsetof(satt_dec_mega_params, step), offsetof(satt_dec_mega_params, nsteps));
   return 0; }'''
-    d = "/tmp/satt_struct_test"
-    os.makedirs(d, exist_ok=True)
+    d = str(tmp_path)
     open(os.path.join(d, "t.c"), "w").write(src)
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "t.c"), "-o", os.path.join(d, "t")])
     vals = list(map(int, subprocess.check_output([os.path.join(d, "t")]).split()))

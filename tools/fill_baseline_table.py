@@ -19,7 +19,7 @@ table = '''| config | device | batch | mel-frames/s (padded) | mel-frames/s (val
 | 4. VCTK multi-speaker | 1x MI355X | 32 | %.0f | %.0f | - | config 4's own shape (Ti=80, Tm=500, 152 speakers): %.2f ms/step (`profiles/%s_bench_vctk.json`) |
 | 5. free-running inference | 1x MI355X | 1 | %.0f frames/s, RTF %.4f | - | - | hipGraph of %d launches per decoder step, KV cache: %.1f us per step (`decode` of `profiles/%s_bench.json`) |
 
-(Measured by `python bench.py` / `tools/final_measure.sh` on the %s build; the TF1 reference itself cannot be timed, see section 2.)
+(Measured by `python bench.py --full` / `tools/final_measure.sh` on the %s build; the TF1 reference itself cannot be timed, see section 2.)
 
 ''' % (cores, rows[0]["padded_mel_frames_per_sec"], rows[0]["valid_mel_frames_per_sec"], rows[0]["s_per_step_median"],
        rows[1]["padded_mel_frames_per_sec"], rows[1]["valid_mel_frames_per_sec"], rows[1]["s_per_step_median"],

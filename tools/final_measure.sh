@@ -4,7 +4,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/final; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
 for cnt in FETCH_SIZE WRITE_SIZE; do
-  timeout 300 rocprofv3 --pmc $cnt --kernel-trace -d $O/pmc_$cnt -- python $R/bench.py --steps 2 --warmup 1 --chunks 1 --no-cpu-baseline --no-decode --time-all-kernels > $O/pmc_$cnt.log 2>&1 < /dev/null
+  timeout 300 rocprofv3 --pmc $cnt --kernel-trace -d $O/pmc_$cnt -- python $R/bench.py --full --steps 2 --warmup 1 --chunks 1 --no-cpu-baseline --no-decode --time-all-kernels > $O/pmc_$cnt.log 2>&1 < /dev/null
 done
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-decode > $O/trace.log 2>&1 < /dev/null
 cd $R
@@ -19,10 +19,10 @@ SATT_DECODE_MEGA=0 timeout 200 rocprofv3 --kernel-trace --output-format csv -d $
 timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/megatrace -- python $R/tools/bench_infer.py --steps 192 > $O/megatrace.log 2>&1 < /dev/null
 cd $R
 (echo "# rocprofv3 --kernel-trace of SATT_DECODE_MEGA=0 tools/bench_infer.py --steps 64 (B=1, Ti=100, bf16: the LAUNCH-PER-LAYER path, hipGraph of 8 steps per replay), tools/decode_timeline.py:"; echo "# two consecutive decoder steps; every launch starts when its predecessor ends (gap 0): the step is a chain of dependent"; echo "# launches, each >= 4.7 us start to start however little it does (round 2 start: 11 launches, 75 us)."; timeout 60 python tools/decode_timeline.py $O/dectrace < /dev/null) > $O/decode_timeline.txt 2>&1
-timeout 300 python bench.py --model tacotron --no-decode > $O/bench_tacotron.json 2> $O/bench_tacotron.err < /dev/null
-timeout 300 python bench.py --model vctk --no-decode --no-cpu-baseline > $O/bench_vctk.json 2> $O/bench_vctk.err < /dev/null
+timeout 300 python bench.py --full --model tacotron --no-decode > $O/bench_tacotron.json 2> $O/bench_tacotron.err < /dev/null
+timeout 300 python bench.py --full --model vctk --no-decode --no-cpu-baseline > $O/bench_vctk.json 2> $O/bench_vctk.err < /dev/null
 timeout 200 python tools/phase_marks.py --dist 2>&1 < /dev/null | grep " ms$\|deferred" > $O/phase_marks_rccl.txt
-timeout 200 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-decode --force-dist 2>/dev/null < /dev/null | grep "^{" > $O/bench_rccl_one_rank.json
+timeout 200 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-decode --force-dist 2>/dev/null < /dev/null | grep "^{" > $O/bench_rccl_one_rank.json
 timeout 100 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 < /dev/null
 timeout 900 python -m pytest tests -m gpu -q 2>&1 < /dev/null | tail -4 > $O/gpu_tests.log
 # round 3: dynamic instruction counts (issue-floor table), per-phase anatomy of the attention loops (profile / trace builds made
@@ -52,7 +52,7 @@ timeout 600 python -m pytest tests/test_pinned_gpu.py -m gpu -q -s -k "sized_fro
 timeout 300 python -m pytest tests/test_pinned_gpu.py -m gpu -q -s -k frozen_float64 2>&1 < /dev/null | grep -v amdgpu.ids | cut -c1-400 > $O/parity_frozen_oracle.log
 timeout 300 python -m pytest tests/test_decode_golden_gpu.py -m gpu -q -s 2>&1 < /dev/null | grep "decode b\|stop rule\|mel abs\|passed\|failed" | cut -c1-330 > $O/decode_golden.log
 (for i in 1 2 3; do timeout 100 python tools/host_enqueue_time.py 2>/dev/null | tail -1; done; SATT_BTT=32,80,500 timeout 100 python tools/host_enqueue_time.py 2>/dev/null | tail -1 | sed 's/^/VCTK shape (B=32, Ti=80, Tm=500): /') > $O/host_enqueue.txt < /dev/null
-timeout 600 python bench.py > $O/bench.json 2> $O/bench.err < /dev/null
+timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err < /dev/null
 ls -la $O
 # r6: the LDS-poison sweep (every kernel launch preceded by a launch that leaves the pattern in every LDS word of every CU) over the
 # parity tests, NaN against 1.0; the cold-start trials of the persistent decode kernel are part of the GPU suite (tests/test_decode_cold_gpu.py)
