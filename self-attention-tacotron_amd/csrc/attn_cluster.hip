@@ -40,13 +40,8 @@ namespace {
 // (write-through) stores, and every wave waits for its own stores before the chunk is counted.  The alternative - plain
 // stores + __threadfence() at the chunk boundary - writes back the whole L2 of the XCD for each of the 128 workgroups:
 // measured 0.32 ms per step for the 16 boundaries of the two launches.
-#ifdef SATT_CHUNK_FENCE     // A/B switch: the fenced form
-__device__ __forceinline__ void gst(float* p, float v) { *p = v; }
-__device__ __forceinline__ void chunk_release() { __threadfence(); }
-#else
 __device__ __forceinline__ void gst(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void chunk_release() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }   // own stores have reached memory
-#endif
 
 // register-resident forward slice: a wave owns MNTW tiles of 16 gate columns (NL <= 16 * MNTW * AW) and all K tiles
 // (32 rows each) of them; MNTW * MKT * 4 accumulation registers per lane hold it.
@@ -629,9 +624,6 @@ __global__ __launch_bounds__(ANT) void attn_cluster_fwd_k(const satt_attn_cluste
           ar[0] = hi; ar[F] = lo; ar[2 * F] = hi;
         }
       };
-#ifdef SATT_EXP_NOCONV      // (timing experiment only: is the convolution beside the cell on the chain?  tools/build_variant.sh)
-      if (ct >= 0) return;
-#endif
       if constexpr (FOLD) {
         // (Ti <= 32 FKT = 160: one element per thread at most, the padding rows in two.  As LOOPS these stores made the wait-count
         // pass flush the vector-memory counter at the loop header - an s_waitcnt vmcnt(0) on the next step's x-gate loads and on
@@ -694,9 +686,7 @@ __global__ __launch_bounds__(ANT) void attn_cluster_fwd_k(const satt_attn_cluste
       //  convolution waves, not the cell, are what the barrier below waits for: one element per thread is already their floor)
       conv_phase(tid - AU);
       // LAZY: the previous step's rows on the waves neither the cell nor the convolution uses (Ti <= 160 <= ANT - AU - 256)
-#ifndef SATT_EXP_NOROWSOUT
       if (rows_pending && tid - AU >= 256) rows_out(tid - AU - 256, bt - 1);
-#endif
     }
     lds_barrier();
     // (3) partial processed query of the own units: h'_own x Wq[own rows, :]  -> published per column
@@ -1611,13 +1601,8 @@ __global__ __launch_bounds__(ANT) void attn_cluster_bwd_k(const satt_attn_cluste
     }
     // ONE wave invalidates (the vector L1 belongs to the CU, the L2 to the XCD: eight invalidates per workgroup bought nothing
     // and cost 0.04 ms per step), in front of the barrier that releases the others
-#ifdef SATT_ACQ_ALL
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#else
     if (threadIdx.x < 64) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     __syncthreads();
-#endif
   };
   // NLOC rows of step tn for the own rows of M tile mt (one wave): see the comment at `ub`
   // Three waves (5..7: no share in the d ctx sums of (a) nor in the value-row MFMAs of (b)) take one M tile each at the TOP of the
@@ -1772,25 +1757,12 @@ __global__ __launch_bounds__(ANT) void attn_cluster_bwd_k(const satt_attn_cluste
       r4[1] = dcs * av;
       r4[2] = (tid >= V1 ? dcx : 0.f) + e2 * a2v;
       r4[3] = wv * av;
-#ifdef SATT_EXP_SUMS_TRANSPOSE
-      const float tot = wave_sum_transpose<4>(r4);                // lane l: total of slot l & 3
-      if (lane < 4) scal[wave * 4 + lane] = tot;
-#else
       // r4: DPP butterflies + lane reads (wave_sum_multi) instead of the transposing reduction: that one needs four dependent trips
       // through the LDS pipe (three swizzles + a bpermute, ~100 cycles each) - fewer instructions, but this phase is one short
       // dependent chain between two barriers, not an issue-bound loop
       wave_sum_multi<4>(r4);
       if (lane == 0) *reinterpret_cast<float4*>(scal + wave * 4) = make_float4(r4[0], r4[1], r4[2], r4[3]);
-#endif
     }
-#ifdef SATT_PF_TOP
-#ifndef SATT_EXP_NOPF_ROWS      // (timing experiments only: tools/build_variant.sh)
-    prefetch_rows(p, max(t - 1, cb.t0), tid);
-#endif
-#ifndef SATT_EXP_NOPF_CELL
-    prefetch_cell(p, max(t - 1, cb.t0), tid);
-#endif
-#endif
     lds_barrier();
     PROF(1); BTRACE(cb.t1 - 1 - t, 0);
     // (b) raw d alpha / d a2 of the own rows through the contexts: d ctx . value row -> LDS.  NO exchange follows (r3): the
@@ -1890,10 +1862,8 @@ __global__ __launch_bounds__(ANT) void attn_cluster_bwd_k(const satt_attn_cluste
       }
     };
     if constexpr (SAF) load_saf(wave, sq, sq2, RBB);
-#ifndef SATT_SR_LATE
     uint2 sr[RBB]; uint32_t sr2[RBB];
     if constexpr (SAF) load_saf(wave + RBB * AW, sr, sr2, RBB - 1);
-#endif
     PROF(10);
     PROF(11);
     BTRACE(cb.t1 - 1 - t, 1);
@@ -2008,14 +1978,6 @@ __global__ __launch_bounds__(ANT) void attn_cluster_bwd_k(const satt_attn_cluste
           }
           // (r4: the d location-feature values of these rows were published by phase (c) from the NLOC rows)
         };
-#ifdef SATT_SR_LATE
-        uint2 sr[RBB]; uint32_t sr2[RBB];
-        load_saf(wave + RBB * AW, sr, sr2, RBB - 1);           // second pass: own rows wave + AW * (RBB + u), u < RBB - 1
-#endif
-#ifdef SATT_PF_IN_D      // (experiment: the next step's prefetch behind the last loads this step consumes from registers)
-        prefetch_rows(p, max(t - 1, cb.t0), tid);
-        prefetch_cell(p, max(t - 1, cb.t0), tid);
-#endif
         if (wave + (RBB - 1) * AW < nown) pass(std::true_type{}, wave, sq, sq2, RBB); else pass(std::false_type{}, wave, sq, sq2, RBB);
         if (wave + (2 * RBB - 2) * AW < nown) pass(std::true_type{}, wave + RBB * AW, sr, sr2, RBB - 1);
         else if (wave + RBB * AW < nown) pass(std::false_type{}, wave + RBB * AW, sr, sr2, RBB - 1);
@@ -2211,13 +2173,11 @@ __global__ __launch_bounds__(ANT) void attn_cluster_bwd_k(const satt_attn_cluste
       xs_put(dzs, DZS, tid, dzi); xs_put(dzs, DZS, AU + tid, dzj);
       xs_put(dzs, DZS, 2 * AU + tid, dzf); xs_put(dzs, DZS, 3 * AU + tid, dzo);
     }
-#if !defined(SATT_PF_TOP) && !defined(SATT_PF_IN_D)
     // (r5, tried and NOT kept: the cell waves issuing these in FRONT of the cell arithmetic, inside its block, so that the address
     //  arithmetic fills the cell's LDS / transcendental latencies: launch 2.86 -> 3.21 ms - the cell's result stores then wait behind
     //  the loads, and the exchange Xh behind both)
     prefetch_rows(p, max(t - 1, cb.t0), tid);
     prefetch_cell(p, max(t - 1, cb.t0), tid);
-#endif
     lds_barrier();
     PROF(7); BTRACE(cb.t1 - 1 - t, 8);
     // (h) partial d[ctx|h] = dz_own x Wrec[:, own]^T: K tile = wave, every N tile; reduce over waves, publish, gather
@@ -2267,12 +2227,7 @@ __global__ __launch_bounds__(ANT) void attn_cluster_bwd_k(const satt_attn_cluste
           phys[q] = km * KR + (r < CT ? r : r + c * AU);
           g[q] = (const gu64*)(wp + WL.xh + phys[q]); x[q] = 0;
         }
-#ifdef SATT_EXP_XH_ONE_POLL      // (timing experiment, WRONG results: one polling load per lane instead of three - the upper bound of what wider
-        //                              granules could buy this exchange)
-        { const gu64* g1[1] = {g[0]}; u64 x1[1] = {0}; poll_or_die<1>(g1, tag, x1, lane, err_word, dead); x[0] = x[1] = x[2] = x1[0]; }
-#else
         poll_or_die<3>(g, tag, x, lane, err_word, dead);
-#endif
 #pragma unroll
         for (int q = 0; q < 3; ++q) if (lane + 64 * q < cnt) cgx[phys[q]] = __uint_as_float((uint32_t)x[q]);
       } else

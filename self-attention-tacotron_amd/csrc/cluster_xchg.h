@@ -30,11 +30,7 @@ __device__ __forceinline__ void gput_s(u64* base, unsigned idx, uint32_t tag, fl
 }
 // agent-scope (write-through) float store, (uniform base, 32-bit element index)
 __device__ __forceinline__ void gst_s(float* base, unsigned idx, float v) {
-#ifdef SATT_CHUNK_FENCE      // (A/B switch of attn_cluster.hip: plain stores + a fence at the chunk boundary)
-  asm volatile("global_store_dword %0, %1, %2" ::"v"(idx * 4u), "v"(v), "s"(base));
-#else
   asm volatile("global_store_dword %0, %1, %2 sc1" ::"v"(idx * 4u), "v"(v), "s"(base));
-#endif
 }
 // plain float store, (uniform base, 32-bit element index)
 __device__ __forceinline__ void pst_s(float* base, unsigned idx, float v) {
@@ -47,17 +43,12 @@ constexpr uint32_t XCC_TAG = 0xFFFFFFFFu;
 // inspected (branch-free, so the compiler keeps all N in flight: a poll costs ONE L2 round trip; with a branch per granule it
 // serialises them).
 // Returns false on the bounded-spin timeout (the caller raises the error word).
-// r5, tried and NOT kept (-DSATT_POLL_PIPELINED): TWO polls in flight - poll B issued before poll A's results are inspected (the
-// vector-memory counter is in-order: the wait for A leaves B's N loads outstanding), so that a fresh poll reaches L2 every half
-// round trip instead of one per round trip + sleep.  The ISA is as intended (no copies, vmcnt(N) waits), and the step got SLOWER:
-// 7.48 -> 7.63 ms, attention backward launch 3.04 -> 3.15 ms (same box, tools/ab_bench.sh).  More polls in flight is not what
-// the exchanges lack: the polling waves share the CU's vector-memory path with the waves that still have to publish.
-#ifndef SATT_POLL_SLEEP
-#define SATT_POLL_SLEEP 1      // s_sleep argument between two polls (units of 64 clocks)
-#endif
+// r5, tried and NOT kept: TWO polls in flight (poll B issued before poll A's results are inspected), so that a fresh poll reaches
+// L2 every half round trip: the step got SLOWER, 7.48 -> 7.63 ms.  The polling waves share the CU's vector-memory
+// path with the waves that still have to publish.
+constexpr int POLL_SLEEP = 1;      // s_sleep argument between two polls (units of 64 clocks)
 template <int N>
 __device__ __forceinline__ bool poll_until(const gu64* const (&g)[N], uint32_t tag, u64 (&x)[N]) {
-#ifndef SATT_POLL_PIPELINED
   for (unsigned spins = 0;; ++spins) {
 #pragma unroll
     for (int q = 0; q < N; ++q) x[q] = __hip_atomic_load(g[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -66,34 +57,8 @@ __device__ __forceinline__ bool poll_until(const gu64* const (&g)[N], uint32_t t
     for (int q = 0; q < N; ++q) all_ok &= (uint32_t)(x[q] >> 32) == tag;
     if (__all(all_ok)) return true;
     if (spins > (1u << 21)) return false;
-    __builtin_amdgcn_s_sleep(SATT_POLL_SLEEP);
+    __builtin_amdgcn_s_sleep(POLL_SLEEP);
   }
-#else
-  // (no copy between the two register sets inside the loop - a copy of an in-flight poll costs s_waitcnt vmcnt(0) per
-  //  iteration, the drained-ring pattern of DESIGN.md 3.4 -: which set holds the result is a flag, selected behind the loop)
-  u64 y[N];
-  bool from_y = false, done = true;
-#pragma unroll
-  for (int q = 0; q < N; ++q) x[q] = __hip_atomic_load(g[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  for (unsigned spins = 0;; ++spins) {
-#pragma unroll
-    for (int q = 0; q < N; ++q) y[q] = __hip_atomic_load(g[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    bool ok = true;
-#pragma unroll
-    for (int q = 0; q < N; ++q) ok &= (uint32_t)(x[q] >> 32) == tag;
-    if (__all(ok)) break;
-#pragma unroll
-    for (int q = 0; q < N; ++q) x[q] = __hip_atomic_load(g[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    ok = true;
-#pragma unroll
-    for (int q = 0; q < N; ++q) ok &= (uint32_t)(y[q] >> 32) == tag;
-    if (__all(ok)) { from_y = true; break; }
-    if (spins > (1u << 20)) { done = false; break; }
-  }
-#pragma unroll
-  for (int q = 0; q < N; ++q) x[q] = from_y ? y[q] : x[q];
-  return done;
-#endif
 }
 
 // poll_until with the kernels' time-out protocol: raises the error word and marks the workgroup dead (later gathers return at once)

@@ -11,12 +11,10 @@ namespace {
 template <int PREC> struct Cfg;
 template <> struct Cfg<SATT_PREC_BF16> { typedef uint16_t LT; static constexpr int BK = 32, STRIDE = 40; };
 // DEEP: a launch that puts about one workgroup on a CU has nothing to hide the global-load round trip of a K tile
-// behind (the next tile is requested one iteration ahead): stage SATT_GEMM_DEEP_BK elements per iteration instead.
-#ifndef SATT_GEMM_DEEP_BK
-#define SATT_GEMM_DEEP_BK 64
-#endif
+// behind (the next tile is requested one iteration ahead): stage DEEP_BK elements per iteration instead.
+constexpr int DEEP_BK = 64;
 constexpr int PREC_BF16_DEEP = 2;
-template <> struct Cfg<PREC_BF16_DEEP> { typedef uint16_t LT; static constexpr int BK = SATT_GEMM_DEEP_BK, STRIDE = SATT_GEMM_DEEP_BK + 8; };
+template <> struct Cfg<PREC_BF16_DEEP> { typedef uint16_t LT; static constexpr int BK = DEEP_BK, STRIDE = DEEP_BK + 8; };
 template <> struct Cfg<SATT_PREC_F32> { typedef float LT; static constexpr int BK = 16, STRIDE = 17; };
 
 template <int PREC> __device__ __forceinline__ typename Cfg<PREC>::LT cvt(float v);
@@ -456,7 +454,7 @@ void launch2(const satt_gemm_params& p, dim3 grid, hipStream_t s) {
       if constexpr (PREC == SATT_PREC_BF16) {
         static const int deep_max = [] { const char* e = getenv("SATT_GEMM_DEEP_MAX"); return e ? atoi(e) : 384; }();
         const int kper = (p.K + p.splitk - 1) / p.splitk;
-        if ((int64_t)grid.x * grid.y * grid.z <= deep_max && kper >= 2 * SATT_GEMM_DEEP_BK) {
+        if ((int64_t)grid.x * grid.y * grid.z <= deep_max && kper >= 2 * DEEP_BK) {
           if (p.sb_n == 1) hipLaunchKernelGGL((gemm_kernel<PREC_BF16_DEEP, A_MODE, true, true, true>), grid, dim3(NT), 0, s, p);
           else hipLaunchKernelGGL((gemm_kernel<PREC_BF16_DEEP, A_MODE, false, true, true>), grid, dim3(NT), 0, s, p);
           return;

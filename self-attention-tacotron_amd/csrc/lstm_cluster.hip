@@ -60,9 +60,8 @@ __device__ __forceinline__ bool cluster_same_xcd(u64* xi, int C, int c, unsigned
 }
 
 // forward: wave w owns the local gate columns [32w, 32w+32) (2 N tiles) x LKT K tiles = 16 B operands
-#ifdef SATT_LSTM_FWD_PIN      // (r6 experiment, tools/build_variant.sh pin lstm_cluster.hip -DSATT_LSTM_FWD_PIN: 128 registers - two workgroups per
-__attribute__((amdgpu_waves_per_eu(4, 4)))      // CU as the backward kernel, 20 spilled registers, +3.6 % per step - what SATT_LSTM_CU_CHARGE=packed needs;
-#endif                                          // not the default: DESIGN.md 1, "Residency")
+// (r6, tried and NOT kept: pinned to 128 registers - two workgroups per CU as the backward kernel - it spills 20 registers,
+//  +3.6 % on the kernel; DESIGN.md 1, "Residency")
 __global__ __launch_bounds__(CNT) void lstm_cluster_fwd_k(const CArgs a) {
   __shared__ __attribute__((aligned(16))) uint16_t hs[4 * (LKT * 32 + APAD)];   // bf16 [4][HS]: split h_state, row 3 = 0
   __shared__ float z[256];
@@ -240,9 +239,6 @@ __global__ __launch_bounds__(CNT) void lstm_cluster_fwd_k(const CArgs a) {
 #endif
 }
 
-#ifndef SATT_LSTMC_ZAHEAD
-#define SATT_LSTMC_ZAHEAD 8      // all LKT tiles: still 128 registers, no spills (tools/kernel_regs.py)
-#endif
 // backward: wave w owns the output units [32w, 32w+32) (2 N tiles) x ALL K tiles of the own gate columns (NL <= 256) = 16 B
 // operands and accumulates over K inside the MFMA accumulators: the partial d h_prev of a unit leaves the registers of lanes
 // 0..15 straight into the exchange (or the own-unit buffer).  Until r4 the waves owned one K tile each and the eight per-tile
@@ -346,7 +342,7 @@ __global__ __launch_bounds__(CNT) void lstm_cluster_bwd_k(const CArgs a) {
       const uint16_t* zrow = dzs + min(lane & 15, 3) * DZS + (lane >> 4) * 8;
       // r5: the A operands run ZAHEAD tiles ahead of the chain (an LDS read cannot move across an asm block: next to their block,
       // every pair of K tiles waited for its own LDS round trip); no deeper: the kernel must stay within 128 registers
-      constexpr int ZAHEAD = SATT_LSTMC_ZAHEAD;
+      constexpr int ZAHEAD = 8;      // all LKT tiles: still 128 registers, no spills (tools/kernel_regs.py)
       bf16x8_t za[LKT];
 #pragma unroll
       for (int kt = 0; kt < ZAHEAD; ++kt) za[kt] = *reinterpret_cast<const bf16x8_t*>(zrow + kt * 32);

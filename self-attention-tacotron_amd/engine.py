@@ -204,17 +204,12 @@ class Engine:
         hipOccupancyMaxActiveBlocksPerMultiprocessor for the kernel and LDS size of the launch, CU count of this device):
           * attention (forward and backward kernel, the larger): ceil(workgroups / workgroups per CU) CUs of its own - it takes the
             whole register file of a CU, nothing shares a CU with it;
-          * each LSTM cluster launch that can be in flight at the same time (one with lstm_one_stream, else two): the dispatcher
-            SPREADS workgroups over the CUs, so every workgroup is charged a CU of its own even where two would fit.
-            r6 tried the calculator's two per CU (`lstm_cu_charge = "packed"`, forward kernel pinned to 128 registers): the B = 33
-            cliff goes (B = 33 / 36 / 40 at Tm = 400: 6.03 / 5.66 / 5.40 -> 4.69 / 4.51 / 4.55 ms per step) and the FORWARD pipeline
-            never failed up to B = 42 (zero CUs to spare), but the BACKWARD pipeline times out intermittently - always at B = 42,
-            1 in ~3 runs at B = 40, 1 in 12 at B = 38, once at B = 36 - also with the LSTM stream held back until every attention
-            workgroup is resident (`attention_first`).  There the LSTM launches share their CUs with the deferred attention
-            gradients and the weight-gradient GEMMs; which of them keeps a packed LSTM launch from becoming resident as a whole
-            is not located (profiles/r06_residency_packed.txt).  An intermittent time-out is a skipped update: not shipped.
-        Side by side only if the sum stays within the device.  Without a device to ask (CPU import): the r4 rule."""
-        key = (B, ap.Ti, Ca, Cn, D, vw1 is not None, bool(ap.saf), self.lstm_one_stream, self.lstm_cu_charge)
+          * the one LSTM cluster launch in flight at a time: the dispatcher SPREADS workgroups over the CUs, so every workgroup is
+            charged a CU of its own even where two would fit.
+        Side by side only if the sum stays within the device.  Without a device to ask (CPU import): the r4 rule.  Charging the
+        calculator's two LSTM workgroups per CU was measured in r6 and rejected: the backward pipeline then times out
+        intermittently ("Residency")."""
+        key = (B, ap.Ti, Ca, Cn, D, vw1 is not None, bool(ap.saf))
         cache = self.__dict__.setdefault("_fit_cache", {})
         if key not in cache:
             rf = ops.attn_cluster_residency(ap, Ca, False, vw1=vw1)
@@ -222,17 +217,13 @@ class Engine:
             lf = ops.lstm_cluster_residency(B, Td, D, Cn, False)
             lb = ops.lstm_cluster_residency(B, Td, D, Cn, True)
             if None in (rf, rb, lf, lb):
-                cache[key] = dict(fits=B * (Ca + Cn) <= self._cu_count(), attention_first=False)
+                cache[key] = dict(fits=B * (Ca + Cn) <= self._cu_count())
             else:
                 cus = rf[2]
                 attn = max(-(-r[0] // max(r[1], 1)) for r in (rf, rb))
-                spread = (1 if self.lstm_one_stream else 2) * min(max(lf[0], lb[0]), cus)
-                lstm = max(-(-r[0] // max(r[1], 1)) for r in (lf, lb)) if (self.lstm_one_stream and self.lstm_cu_charge == "packed") else spread
+                lstm = min(max(lf[0], lb[0]), cus)
                 fits = all(r[0] <= r[1] * r[2] for r in (rf, rb, lf, lb)) and attn + lstm <= cus
-                # beyond the r5 rule (one CU per LSTM workgroup) the launch ORDER matters: the attention kernel must be resident as
-                # a whole before an LSTM launch spreads over the CUs it needs (backward(): the LSTM stream waits for it)
-                cache[key] = dict(attention=(rf, rb), lstm=(lf, lb), attention_cus=attn, lstm_cus=lstm, cus=cus, fits=fits,
-                                  attention_first=bool(fits and attn + spread > cus))
+                cache[key] = dict(attention=(rf, rb), lstm=(lf, lb), attention_cus=attn, lstm_cus=lstm, cus=cus, fits=fits)
         self.residency = cache[key]
         return cache[key]["fits"]
 
@@ -274,11 +265,11 @@ class Engine:
     #                         kernel has produced the next, smaller chunk or the drain behind the loop grows)
     pipeline_tail = (6, 3)  # (number of geometrically shrinking tail chunks, smallest = Td / (this * chunks))
     # the forward pipeline's own tail (None: the same): the two directions chunk the steps independently
-    pipeline_tail_fwd = tuple(int(v) for v in os.environ["SATT_TAIL_FWD"].split(",")) if os.environ.get("SATT_TAIL_FWD") else None
+    pipeline_tail_fwd = None
     pipeline_kvq = True              # decoder self-attention K|V|Q projection chunk by chunk on the LSTM2 stream
     # forward chunks of at most this many steps form their LSTM input projections inside the LSTM cluster launch (bf16 mode;
     # csrc/lstm_cluster.hip, fused input projection): the chain behind the attention kernel's last steps loses two GEMM launches
-    fuse_xg_steps = int(os.environ.get("SATT_FUSE_XG_STEPS", "32"))
+    fuse_xg_steps = 32
     single_launch_attention = True   # attention kernels span all pipeline chunks and signal chunk ends (see forward())
     save_attention_factors = True    # (with fold_context) energy-derivative factors saved by the forward kernel for the backward one
     fold_context = True              # first-source context folded into the recurrent product where the kernel offers it
@@ -506,6 +497,12 @@ class Engine:
             cls._shared_streams[key] = tuple(chosen)
         return cls._shared_streams[key]
 
+    head_split = True       # decoder self-attention backward as suffix + prefix launches (backward(): the pipeline starts behind the suffix)
+    # (a third launch for the low tiles of the split head, on the weight-gradient stream beside the loop or inside the LSTM stream:
+    #  MEASURED AND NOT KEPT, 8.34 -> 8.43 ms per step: the fused backward's workgroups only find CUs in the gaps between two LSTM
+    #  cluster launches, and the chunk that needs their rows then waits ~300 us; docs/DESIGN_HISTORY.md 9.5)
+    head_split_chunks = 1   # pipeline chunks (from the end) that lie inside the suffix
+
     # Both decoder LSTM layers share ONE stream: next to the attention kernel (one workgroup per CU on half of the chip) there is
     # room for the workgroups of ONE LSTM cluster kernel whatever else is in flight, but two LSTM launches that start dispatching
     # at the same moment (LSTM1 of chunk k, LSTM2 of chunk k+1 - they are released by the same event) could each end up
@@ -514,26 +511,11 @@ class Engine:
     # the two layers that this gives up is bought back by tail chunks that grow by 1.4x instead of 2x (pipeline_growth).
     # (r4: the LSTM cluster kernels now fit two workgroups per CU, i.e. both layers' launches fit the free half of the chip - re-measured
     #  with two streams: within noise of one stream at the default chunking, and with 8-step tail chunks the hand-off time-outs are
-    #  back (profiles/r04_chunk_sweep_b.txt).  SATT_LSTM_STREAMS=2 keeps the switch for experiments.)
-    lstm_one_stream = os.environ.get("SATT_LSTM_STREAMS", "1") != "2"
-    # "spread" (default): one CU per LSTM workgroup; "packed" (r6 experiment, needs the -DSATT_LSTM_FWD_PIN build): the occupancy
-    # calculator's two per CU - removes the B = 33 cliff but time-outs intermittently in the backward pipeline (_layers_fit_side_by_side)
-    lstm_cu_charge = os.environ.get("SATT_LSTM_CU_CHARGE", "spread")
-    flash_bf16 = os.environ.get("SATT_FLASH_BF16", "1") != "0"     # bf16 copies of K | V | Q and d o for the fused attention backward
-    head_split = True       # decoder self-attention backward as suffix + prefix launches (backward(): the pipeline starts behind the suffix)
-    # low tiles of the split head on the weight-gradient stream beside the loop: MEASURED AND NOT KEPT (8.34 -> 8.43 ms per step, VCTK
-    # 5.35 -> 5.44): the head leaves the main stream 90 us earlier, but the fused backward's workgroups (64 KB of LDS, a whole CU's
-    # registers) only find CUs in the gaps between two LSTM cluster launches - three gaps of ~25 us every ~240 us - and the chunk
-    # that needs their rows then waits ~300 us (attention launch 3.69 -> 3.85 ms).  The switch stays for re-measuring.
-    head_split_low = int(os.environ.get("SATT_HEAD_SPLIT_LOW", "0"))       # 0: off, 1: weight-gradient stream, 2: inside the LSTM stream
-    head_split_release = int(os.environ.get("SATT_HEAD_SPLIT_RELEASE", "2"))  # chunks before the first one that needs the low rows
-    head_split_chunks = int(os.environ.get("SATT_HEAD_SPLIT_CHUNKS", "1"))   # pipeline chunks (from the end) that lie inside the suffix
-
+    #  back (profiles/r04_chunk_sweep_b.txt).)
     def _streams(self):
+        """the one stream of the LSTM layers in the layer pipeline"""
         if self._side is None:
-            self._side = self._device_streams(self.dev)[:2]
-        if self.lstm_one_stream:
-            return (self._side[0], self._side[0])
+            self._side = self._device_streams(self.dev)[0]
         return self._side
 
     def _t(self, name):
@@ -580,7 +562,7 @@ class Engine:
             # fused QK^T -> causal softmax -> dropout -> PV (csrc/flash.hip): no [B*H, T, T] tensor; backward recomputes P
             lse = self._e(nbh, T)
             # bf16 copies of K | V | Q for the backward kernels, written by the forward kernel as it stages the rows (no launch)
-            kvq_b = self._e(M, 3 * D, dtype=torch.bfloat16) if (self.flash_bf16 and ctx.get("training")) else None
+            kvq_b = self._e(M, 3 * D, dtype=torch.bfloat16) if ctx.get("training") else None
             ops.flash_attn_fwd(kvq, D, o, lse, B, T, heads, 1.0 / math.sqrt(hd), causal, drop, kvq_b=kvq_b)
         else:
             s = self._e(nbh, T, T)
@@ -629,28 +611,20 @@ class Engine:
         if c["lse"] is not None and suffix_from and causal:
             # causal: key tile j takes query tiles >= j, query tile i key tiles <= i - ANY tile range leaves its own rows final
             # (include/satt_hip.h satt_flash_attn_bwd_tiles).  Two ranges: the suffix (the pipeline's first chunk waits for it) and
-            # the rest (on this stream, in front of the attention kernel).  With head_split_low (OFF: measured slower, see the
-            # class attribute) the low half of the rest becomes a third range handed to the caller as a closure, to run beside or
-            # inside the loop - its rows are reached more than a millisecond later.
+            # the rest (on this stream, in front of the attention kernel).  (A third range - the low half of the rest run beside or
+            # inside the loop - was measured slower: see head_split.)
             ts, nt, delta, cur = suffix_from // ops.FLASH_TILE, (T + ops.FLASH_TILE - 1) // ops.FLASH_TILE, self._e(nbh, T), ops.current_stream()
-            tm = ts // 2 if (self.head_split_low and self.overlap_wgrad) else 0
             sc, Wk = 1.0 / math.sqrt(hd), self.W(prefix + ".kvq.W")
             ops.flash_attn_bwd(kvq, D, o, do, c["lse"], delta, dkvq, B, T, heads, sc, causal, drop, tiles=(ts, nt), **fb)
             ops.linear_dx_rows(dkvq, Wk, dy, B, T, suffix_from, T, accumulate=True)    # dy = the residual path
             ev_a = torch.cuda.Event(); ev_a.record(cur)
             self._side_mark("head: suffix rows done (main stream)")
-            ops.flash_attn_bwd(kvq, D, o, do, c["lse"], delta, dkvq, B, T, heads, sc, causal, drop, tiles=(tm, ts), **fb)
-            ops.linear_dx_rows(dkvq, Wk, dy, B, T, tm * ops.FLASH_TILE, suffix_from, accumulate=True)
+            ops.flash_attn_bwd(kvq, D, o, do, c["lse"], delta, dkvq, B, T, heads, sc, causal, drop, tiles=(0, ts), **fb)
+            ops.linear_dx_rows(dkvq, Wk, dy, B, T, 0, suffix_from, accumulate=True)
             ev_b = torch.cuda.Event(); ev_b.record(cur)
             self._side_mark("head: prefix rows done (main stream)")
-            kvq_dw = lambda: (ops.linear_dw(x, dkvq, G[prefix + ".kvq.W"], db=G[prefix + ".kvq.b"]))
-
-            def low():          # on the stream the caller chooses, ordered behind ev_b; the caller hands kvq_dw to _wgrad afterwards
-                ops.flash_attn_bwd(kvq, D, o, do, c["lse"], delta, dkvq, B, T, heads, sc, causal, drop, tiles=(0, tm), **fb)
-                ops.linear_dx_rows(dkvq, Wk, dy, B, T, 0, tm * ops.FLASH_TILE, accumulate=True)
-            if tm == 0:
-                self._wgrad(kvq_dw, defer=defer)
-            self._head_split = (suffix_from, ev_a, ev_b, tm * ops.FLASH_TILE, (low, kvq_dw) if tm else None)
+            self._wgrad(lambda: (ops.linear_dw(x, dkvq, G[prefix + ".kvq.W"], db=G[prefix + ".kvq.b"])), defer=defer)
+            self._head_split = (suffix_from, ev_a, ev_b)
             return dy
         if c["lse"] is not None:          # fused attention: dK | dV | dQ from Q, K, V, o, d o and the saved log-sum-exp
             ops.flash_attn_bwd(kvq, D, o, do, c["lse"], self._e(nbh, T), dkvq, B, T, heads, 1.0 / math.sqrt(hd), causal, drop, **fb)
@@ -863,7 +837,7 @@ class Engine:
             ops.linear(dpre[-1], self.W("dec.att_lstm.W").rows(0, pn), P["dec.att_lstm.b"], xg_att)
 
         main0 = ops.current_stream()
-        side = self._streams()[0] if self.overlap_wgrad else main0
+        side = self._streams() if self.overlap_wgrad else main0
         if side is not main0:
             ev_in = torch.cuda.Event(); ev_in.record(main0)
             side.wait_event(ev_in)
@@ -1018,14 +992,13 @@ class Engine:
             # The three recurrent layers form a producer/consumer chain and each cluster kernel occupies only
             # B*C CUs: run them as a software pipeline over time chunks on three HIP streams.
             main = ops.current_stream()
-            s1, s2 = self._streams()
+            ls = self._streams()
             bounds = self._chunk_bounds(Td, NC, self.pipeline_tail_fwd)
-            ev1 = None
             # ONE attention launch over all steps (one prologue instead of one per chunk): the kernel counts its finished
             # chunks in `prog` and the LSTM1 stream waits on the counter (hipStreamWaitValue32) instead of on kernel ends
             # (not when kernels of different streams cannot overlap - counter-collecting profilers serialise them, and a
             # serialised wait would sit in front of the kernel it waits for)
-            single = self.single_launch_attention and len(bounds) <= 16 and ops.streams_run_concurrently(main, s1)
+            single = self.single_launch_attention and len(bounds) <= 16 and ops.streams_run_concurrently(main, ls)
             if single:
                 prog = self._ctr[self._ctr_par][0:16]
                 self._keep_fwd = prog
@@ -1038,13 +1011,13 @@ class Engine:
                     with self._t("attn_rnn_fwd"):
                         ops.attn_cluster_fwd(ap, Ca, fold_pack if vw1 is not None else self._pack_cache[Ca][0], aws, t0, t1, vw1=vw1)
                     eva = torch.cuda.Event(); eva.record(main)
-                with ops.on_stream(s1):
+                with ops.on_stream(ls):
                     if single:
                         if k == 0:
-                            s1.wait_event(evz)
-                        ops.stream_wait_value(prog[k:k + 1], B * Ca, s1)       # every workgroup has finished chunk k
+                            ls.wait_event(evz)
+                        ops.stream_wait_value(prog[k:k + 1], B * Ca, ls)       # every workgroup has finished chunk k
                     else:
-                        s1.wait_event(eva)
+                        ls.wait_event(eva)
                     if ctx1_rows is not None:
                         ctx1_rows(t0, t1)
                     fuse = lin is not None and t1 - t0 <= self.fuse_xg_steps
@@ -1057,11 +1030,7 @@ class Engine:
                         with self._t("lstm1_fwd"):
                             ops.lstm_cluster_fwd(xg1, lp1[0], B, Td, D, Cn, training, c.zc, c.zh, seed,
                                                  S_L1_C, S_L1_H, h1, l1[0], l1[1], l1[2], l1[3], cws1, t0, t1)
-                    if s2 is not s1:       # (one LSTM stream: program order; an event pair is two marker packets in the chain)
-                        ev1 = torch.cuda.Event(); ev1.record(s1)
-                with ops.on_stream(s2):
-                    if s2 is not s1:
-                        s2.wait_event(ev1)
+                    # (LSTM2 of the chunk behind LSTM1 in program order: one stream, no event pair)
                     if fuse and lin[1] is not None:
                         with self._t("lstm2_fwd"):
                             ops.lstm_cluster_fwd_x(h1, D, lin[1], P["dec.lstm2.b"], xg2, lp2[0], B, Td, D, Cn, training, c.zc, c.zh,
@@ -1074,7 +1043,7 @@ class Engine:
                     if kvq_dec is not None and self.pipeline_kvq:
                         ops.linear_rows(dec_out, self.W("dec.sa.kvq.W"), P["dec.sa.kvq.b"], kvq_dec, B, Td, t0, t1)
             kvq_done = kvq_dec is not None and self.pipeline_kvq
-            ev2 = torch.cuda.Event(); ev2.record(s2)
+            ev2 = torch.cuda.Event(); ev2.record(ls)
             main.wait_event(ev2)
         else:
             with self._t("attn_rnn_fwd"):
@@ -1389,7 +1358,7 @@ class Engine:
 
         if NC > 1:
             main = ops.current_stream()
-            s1, s2 = self._streams()
+            ls = self._streams()
             bounds = self._chunk_bounds(Td, NC)
             bst1, bst2 = self._e(B, 2, D), self._e(B, 2, D)
             ast = ops.attn_cluster_state(ctx["att_params"], Ca, self.dev)
@@ -1397,7 +1366,7 @@ class Engine:
             # word `ready` that the LSTM1 stream bumps after each chunk's incoming gradients exist, and counts its finished
             # chunks in `done`, on which the deferred parameter gradients wait
             single = self.single_launch_attention and len(bounds) <= 16 and self.overlap_wgrad and \
-                ops.streams_run_concurrently(main, s1) and ops.streams_run_concurrently(main, s2)
+                ops.streams_run_concurrently(main, ls)
             if single:
                 cnt = self._ctr[self._ctr_par][16:48]
                 ready, done = cnt[0:1], cnt[16:32]
@@ -1414,11 +1383,6 @@ class Engine:
             if not hs:
                 ev0.record(main)
             ev_low = hs[2] if hs else None
-            # the low tiles of the split head (rows < low_rows): released onto the weight-gradient stream two chunks before the
-            # pipeline reaches them - by then the LSTM stream is a few hundred microseconds ahead of the attention kernel
-            low_rows, low_fn, ev_low2 = (hs[3], hs[4], None) if hs else (0, None, None)
-            order = list(reversed(bounds))
-            k_rel = max(0, next(i for i, (b0, _) in enumerate(order) if b0 < low_rows) - max(1, self.head_split_release)) if low_fn else -1
             if single:
                 self._side_mark("attention backward launch: main stream reaches it")
                 with self._t("attn_rnn_bwd"):
@@ -1428,41 +1392,28 @@ class Engine:
             pg_done = False
             pg_chunks = []
             for k, (t0, t1) in enumerate(reversed(bounds)):
-                with ops.on_stream(s2):
+                with ops.on_stream(ls):
                     if first:
-                        s2.wait_event(ev0)
-                        if single and self.residency and self.residency.get("attention_first"):
-                            # (r6) the attention kernel is resident as a whole before the first LSTM launch may spread over the CUs
-                            # it needs: csrc/attn_cluster.hip counts its resident workgroups in the word behind `ready`
-                            ops.stream_wait_value(cnt[1:2], B * Ca, s2)
+                        ls.wait_event(ev0)
                         self._side_mark("LSTM 2 backward, first chunk: released (its stream)")
                     if ev_low is not None and t0 < hs[0]:
-                        s2.wait_event(ev_low); ev_low = None
-                    if ev_low2 is not None and t0 < low_rows:
-                        s2.wait_event(ev_low2); ev_low2 = None
+                        ls.wait_event(ev_low); ev_low = None
                     with self._t("lstm2_bwd"):
                         ops.lstm_cluster_bwd(ddec, lp2[1], B, Td, D, Cn, training, c.zc, c.zh, seed,
                                              S_L2_C, S_L2_H, g2, cn2, cs2, dxg, cws2, t0, t1, bst2)
                     ops.linear_dx_rows(dxg[0], self.W("dec.lstm2.W").rows(0, D), dh1, B, Td, t0, t1)
                     if first:
                         self._side_mark("LSTM 2 backward, first chunk: done")
-                    if s1 is not s2:
-                        e2 = torch.cuda.Event(); e2.record(s2)
-                with ops.on_stream(s1):
-                    if first and s1 is not s2:
-                        s1.wait_event(ev0)
-                    if s1 is not s2:
-                        s1.wait_event(e2)
                     with self._t("lstm1_bwd"):
                         ops.lstm_cluster_bwd(dh1, lp1[1], B, Td, D, Cn, training, c.zc, c.zh, seed,
                                              S_L1_C, S_L1_H, g1, cn1, cs1, dxg1, cws1, t0, t1, bst1)
                     ops.linear_dx_rows(dxg1[0], self.W("dec.lstm1.W").rows(0, A + CT), datt, B, Td, t0, t1)
                     if single:
-                        ops.stream_write_value(ready, pieces_upto[k], s1)     # chunk k of d att_out exists
+                        ops.stream_write_value(ready, pieces_upto[k], ls)     # chunk k of d att_out exists
                         if first:
                             self._side_mark("LSTM 1 backward, first chunk: done (the attention kernel's first `ready`)")
                     else:
-                        e1 = torch.cuda.Event(); e1.record(s1)
+                        e1 = torch.cuda.Event(); e1.record(ls)
                 if not single:
                     main.wait_event(e1)
                     with self._t("attn_rnn_bwd"):
@@ -1470,48 +1421,24 @@ class Engine:
                     if self.overlap_wgrad:
                         evc = torch.cuda.Event(); evc.record(main)
                         pg_chunks.append((t0, t1, evc))
-                if k == k_rel:
-                    if self.head_split_low == 2:        # IN the LSTM stream, between two chunks (no other cluster launch of that stream is
-                        with ops.on_stream(s1):         # resident then: the fused backward gets the half of the chip the LSTM layers use)
-                            s1.wait_event(hs[2])
-                            low_fn[0]()
-                            if s2 is not s1:
-                                ev_low2 = torch.cuda.Event(); ev_low2.record(s1)
-                            self._wgrad(low_fn[1])
-                    else:                               # on the weight-gradient stream, beside the loop
-                        if self._wg_stream is None:
-                            self._wg_stream = self._device_streams(self.dev)[2]
-                        wg = self._wg_stream
-                        er = torch.cuda.Event(); er.record(s1)
-                        wg.wait_event(er); wg.wait_event(hs[2])
-                        with ops.on_stream(wg):
-                            low_fn[0](); low_fn[1]()
-                            ev_low2 = torch.cuda.Event(); ev_low2.record(wg)
-                        if self._wg_used is None:
-                            self._wg_used = []
-                        if wg not in self._wg_used:
-                            self._wg_used.append(wg)
                 first = False
             if single:
                 pg_chunks = [(p0, p1, r) for r, (p0, p1) in enumerate(pieces)]
-                with ops.on_stream(s1):
-                    e1 = torch.cuda.Event(); e1.record(s1)
             # The deferred (non-recurrent) attention gradients run chunk by chunk as the attention backward completes
-            # them, on the WEIGHT-GRADIENT stream: it is idle for most of the loop, whereas the LSTM2 stream is busy
+            # them, on the WEIGHT-GRADIENT stream: it is idle for most of the loop, whereas the LSTM stream is busy
             # with its chunks for the first 2 ms and then cannot catch up before the loop ends (3.1 ms of work).  The
-            # weight gradients of the two LSTMs take the LSTM streams instead, which idle once their chains are done
+            # weight gradients of the two LSTMs take the LSTM stream instead, which idles once its chain is done
             # (ROCm multiplexes streams onto 4 hardware queues: a fifth stream would serialise with one of these).
             # The LDS pad keeps the workgroups on CUs the recurrent kernels do not occupy.
-            pgs = s2
+            pgs = ls
             if self.overlap_wgrad:
                 if self._wg_stream is None:
                     self._wg_stream = self._device_streams(self.dev)[2]
                 pgs = self._wg_stream
-            with ops.on_stream(s2):
-                lstm2_dw(direct=pgs is not s2)
-                e2 = torch.cuda.Event(); e2.record(s2)
+            with ops.on_stream(ls):
+                lstm2_dw(direct=pgs is not ls)
             with ops.on_stream(pgs):
-                if pgs is not s2:
+                if pgs is not ls:
                     pgs.wait_event(ev0)
                 # the small chunks at the start of the backward loop are merged into one launch: a 16-step launch of
                 # this kernel costs 17 us per step, a 100-step launch 6 us (fixed per-workgroup set-up), and the stream
@@ -1544,13 +1471,14 @@ class Engine:
                         self._wg_used = []
                     if pgs not in self._wg_used:
                         self._wg_used.append(pgs)
-            with ops.on_stream(s1):
-                lstm1_dw(direct=pgs is not s2)
-                e1 = torch.cuda.Event(); e1.record(s1)
+            with ops.on_stream(ls):
+                lstm1_dw(direct=pgs is not ls)
+                e1 = torch.cuda.Event(); e1.record(ls)
             self._pg_ev = evp if pg_done else None   # waited for right before the first use of d keys
-            self._join = (e1, e2)
+            self._join = (e1,)
             if self.overlap_wgrad and self._wg_stream is not None:
-                self._wg_rr = [self._wg_stream, s1, s2]     # the pipeline streams are idle from here on
+                # the pipeline stream is idle from here on: it takes two of every three weight-gradient launches
+                self._wg_rr = [self._wg_stream, ls, ls]
         else:
             with self._t("lstm2_bwd"):
                 if Cn:
@@ -1606,7 +1534,7 @@ class Engine:
             ops.seq_mask(dv1, slen, dlstm_out, B, Ti, V1)
         src1_done = None
         if c.dual and self.overlap_wgrad and self._wg_rr is not None and len(self._wg_rr) > 1:
-            side = self._wg_rr[-1]       # the second pipeline stream: its last work is the deferred attention gradients
+            side = self._wg_rr[-1]       # the LSTM pipeline stream
             ev = torch.cuda.Event(); ev.record(ops.current_stream())
             side.wait_event(ev)
             with ops.on_stream(side):

@@ -148,7 +148,7 @@ def test_layer_pipeline_schedule(Td, NC, tail, growth):
 
 
 def test_chunk_bounds_honour_an_explicit_tail():
-    """the `tail` argument (pipeline_tail_fwd / SATT_TAIL_FWD) used to be shadowed by a local list and ignored"""
+    """the `tail` argument (pipeline_tail_fwd) used to be shadowed by a local list and ignored"""
     from satt_amd.engine import Engine
 
     class E:
