@@ -429,11 +429,14 @@ typedef struct {
    * u = sigmoid([ctx1_t | processed query 1_t] . agentW + agentb[0]) instead of the constant 0.5 (u of step 0 = 0.5);
    * agentW [V1+U1], agentb [1]; ustate [B,Td] receives the u USED at step t (entries t >= 1; saved for backward). */
   const float* agentW; const float* agentb; float* ustate;
-  /* saf (optional, cluster kernels, benchmark precision): fp16 [B,Td,Ti,U1+U2], s = r - 1/2 of the energy nonlinearity
-   * (r = 1 / (1 + 2^(c x)): tanh x = -2 s, 1 - tanh^2 = 4 (1/4 - s^2)), written by the folded forward kernel for the rows below
-   * the source length.  A backward launch and satt_attn_param_grads* that find it non-NULL read it instead of recomputing
-   * keys + query + location term -> exp2 -> rcp per (step, row, unit) - the largest phase of the backward step.  fp16 rounding
-   * (absolute 2.4e-4 on 1/4 - s^2) is the only difference; exact-fp32 mode leaves it NULL. */
+  /* saf (optional, cluster kernels, benchmark precision): fp16 [B,Td,Ti,U1+U2], one word q per (step, row, unit) for the energy
+   * nonlinearity (r = 1 / (1 + 2^(c x)), tanh x = 1 - 2 r): q = +m where r <= 1/2, -m otherwise, m = min(r, 1 - r) (source 1
+   * rounded toward zero, source 2 to nearest), so r (1 - r) = m (1 - m), 1 - tanh^2 = 4 m (1 - m), tanh = sign(q) (1 - 2 m).  Written by the folded forward kernel
+   * for the rows below the source length.  A backward launch and satt_attn_param_grads* that find it non-NULL read it instead of
+   * recomputing keys + query + location term -> exp2 -> rcp per (step, row, unit) - the largest phase of the backward step.  fp16
+   * rounding of m is the only difference: RELATIVE 2^-10 on the derivative factors in every regime, saturated tanh included
+   * (2^-11 absolute on tanh; below m ~ 6e-5 fp16 subnormals round m to 6e-8 absolute).  Exact-fp32 mode leaves it NULL.  Encode
+   * and decode: csrc/attn_common.h (saf_encode, saf_factor, saf_tanh). */
   void* saf;
 } satt_attn_rnn_params;
 int satt_attn_rnn_fwd(const satt_attn_rnn_params* p, void* stream);

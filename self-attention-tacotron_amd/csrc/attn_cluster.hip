@@ -818,27 +818,29 @@ __global__ __launch_bounds__(ANT) void attn_cluster_fwd_k(const satt_attn_cluste
                 x01 = f2 * Us01[k] + x01; x23 = f2 * Us23[k] + x23;
               }
             }
-            const v2f e01 = (v2f){exp2f_(x01.x), exp2f_(x01.y)} + one2, e23 = (v2f){exp2f_(x23.x), exp2f_(x23.y)} + one2;
+            const v2f p01 = (v2f){exp2f_(x01.x), exp2f_(x01.y)}, p23 = (v2f){exp2f_(x23.x), exp2f_(x23.y)};
+            const v2f e01 = p01 + one2, e23 = p23 + one2;
             const v2f r01 = (v2f){__builtin_amdgcn_rcpf(e01.x), __builtin_amdgcn_rcpf(e01.y)};
             const v2f r23 = (v2f){__builtin_amdgcn_rcpf(e23.x), __builtin_amdgcn_rcpf(e23.y)};
             const v2f a2 = vp01 * r01 + vp23 * r23;
             acc = a2.x + a2.y;
-            const float r2 = __builtin_amdgcn_rcpf(1.f + exp2f_(TS * k2 + pq2));
+            const float p2 = exp2f_(TS * k2 + pq2);
+            const float r2 = __builtin_amdgcn_rcpf(1.f + p2);
             acc2 = lane < U2 ? v2p * r2 : 0.f;
-            if (FOLD && (FULLW || saf)) {     // s = r - 1/2 of this row for the backward pass (satt_attn_rnn_params.saf; tanh = -2 s,
-              //                      r (1 - r) = 1/4 - s^2: both consumers get what they need).  Stored right here: holding the
-              //                      values until after the exchange X2, or until the next step's recurrent product, measured
-              //                      slower (2.66 ms per launch against 2.62; without the stores 2.57, without any of it 2.46)
-              const v2f half2 = (v2f){0.5f, 0.5f};
-              const v2f q01 = r01 - half2, q23 = r23 - half2;
+            if (FOLD && (FULLW || saf)) {     // the saved factor words of this row for the backward pass (satt_attn_rnn_params.saf,
+              //                      attn_common.h saf_encode: from e = 2^(c x) and r; source 1 rounded toward zero; both consumers get what
+              //                      they need).  Stored right here: holding the values until after the exchange X2, or until the
+              //                      next step's recurrent product, measured slower (2.66 ms per launch against 2.62; without the
+              //                      stores 2.57, without any of it 2.46)
               typedef __attribute__((ext_vector_type(2))) __fp16 h2;
               union { h2 h[2]; uint2 u; } pk;
-              pk.h[0] = __builtin_amdgcn_cvt_pkrtz(q01.x, q01.y); pk.h[1] = __builtin_amdgcn_cvt_pkrtz(q23.x, q23.y);
+              pk.h[0] = __builtin_amdgcn_cvt_pkrtz(saf_encode(p01.x, r01.x), saf_encode(p01.y, r01.y));
+              pk.h[1] = __builtin_amdgcn_cvt_pkrtz(saf_encode(p23.x, r23.x), saf_encode(p23.y, r23.y));
               // (row pointers from ONE 64-bit base per step: own rows are C * AW * UQ halfs apart)
               // (r5: scalar row base + 32-bit lane offset, written as the instruction: the compiler forms a 64-bit vector address
               //  per store - three VALU instructions each in the phase that is issue bound; byte offsets 2 d0 / 2 (U1 + lane))
               uint16_t* row = saf_rows + (size_t)(u + (i0 - wave) / AW) * (size_t)(C * AW * UQ);
-              const __fp16 h2v = (__fp16)(r2 - 0.5f);
+              const __fp16 h2v = (__fp16)saf_encode(p2, r2);
               if (d0 < U1) asm volatile("global_store_dwordx2 %0, %1, %2" :: "v"(2 * d0), "v"(pk.u), "s"(row) : "memory");
               if (lane < U2) asm volatile("global_store_short %0, %1, %2" :: "v"(2 * (U1 + lane)), "v"(h2v), "s"(row) : "memory");
             }
@@ -1291,7 +1293,7 @@ __global__ __launch_bounds__(ANT) void attn_cluster_bwd_k(const satt_attn_cluste
   // NLOC (r4): d fl[t', k] = sum_u g[t', u] U[k, u] with g = d e[t'] (4 v[u]) f[t', u] factorises as d e[t'] * N[t', k], and
   // N[t', k] = sum_u f[t', u] (4 v[u] U[k, u]) depends on the FORWARD pass only.  The rows N of the step processed next are formed
   // one step ahead, off the dependency chain (three otherwise idle waves during the single-wave cell phase): 16x16x32 fp16 MFMAs
-  // with A = f = 1/4 - s^2 straight from the saved fp16 rows (loaded in operand layout, 4 packed FMAs per tile) and B = the
+  // with A = f = m (1 - m) straight from the saved fp16 rows (loaded in operand layout, 4 packed FMAs per tile) and B = the
   // constant 4 v U split into fp16 hi + lo columns (resident in LDS).  The energy-backward rows (d) lose their five filter dot
   // products and both 16-value transposing wave reductions; phase (c) multiplies d e into the N row and publishes.
   typedef _Float16 h8_t __attribute__((ext_vector_type(8)));
@@ -1626,11 +1628,10 @@ __global__ __launch_bounds__(ANT) void attn_cluster_bwd_k(const satt_attn_cluste
     if constexpr (VMF) {
       typedef float f4_t __attribute__((ext_vector_type(4)));
       const h8_t* ubk = ub + lane;
-      const h8_t quarter = {0.25f16, 0.25f16, 0.25f16, 0.25f16, 0.25f16, 0.25f16, 0.25f16, 0.25f16};
       f4_t acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int q = 0; q < KT1; ++q) {
-        const h8_t f = quarter - nsv[q] * nsv[q];                   // r (1 - r) from the saved s = r - 1/2
+        const h8_t f = saf_factor_h(nsv[q]);                        // r (1 - r) from the saved words (attn_common.h)
         acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(f, ubk[q * 64], acc, 0, 0, 0);
       }
       float* dst = nl + (mt * 16 + (lane >> 4) * 4) * 16 + (lane & 15);                     // D[m = 4 (l >> 4) + r][n = l & 15]
@@ -1956,7 +1957,7 @@ __global__ __launch_bounds__(ANT) void attn_cluster_bwd_k(const satt_attn_cluste
         }
       };
       if constexpr (SAF) {
-        // rows from the saved s = r - 1/2: g = d e * (4 v) * (1/4 - s^2), no keys, no location term, no exp2 / rcp
+        // rows from the saved factor words: g = d e * (4 v) * r (1 - r), no keys, no location term, no exp2 / rcp
         typedef __attribute__((ext_vector_type(2))) __fp16 h2;
         auto pass = [&](auto full_tag, int i0, const uint2 (&q)[RBB], const uint32_t (&q2)[RBB], int n) {
           constexpr bool FULLW = decltype(full_tag)::value;      // every row of the pass exists: no per-row test (see the forward kernel)
@@ -1967,13 +1968,11 @@ __global__ __launch_bounds__(ANT) void attn_cluster_bwd_k(const satt_attn_cluste
               const float de = de1[tt], dq2 = da2[tt];
               union { uint32_t w; h2 h; } c0, c1, c2;
               c0.w = q[u].x; c1.w = q[u].y; c2.w = q2[u];
-              const v2f s01 = (v2f){(float)c0.h.x, (float)c0.h.y}, s23 = (v2f){(float)c1.h.x, (float)c1.h.y};
-              const v2f quarter2 = (v2f){0.25f, 0.25f};
-              const v2f f01 = quarter2 - s01 * s01, f23 = quarter2 - s23 * s23;     // r (1 - r) from s = r - 1/2
+              const v2f f01 = (v2f){saf_factor((float)c0.h.x), saf_factor((float)c0.h.y)};
+              const v2f f23 = (v2f){saf_factor((float)c1.h.x), saf_factor((float)c1.h.y)};
               const v2f de2v = (v2f){de, de};
               dpq01 += (de2v * vq01) * f01; dpq23 += (de2v * vq23) * f23;           // lanes beyond U1: vq = 0
-              const float s2 = (float)c2.h.x;
-              dpq2a += dq2 * v2q * (0.25f - s2 * s2);                            // lanes beyond U2: v2q = 0
+              dpq2a += dq2 * v2q * saf_factor((float)c2.h.x);                    // lanes beyond U2: v2q = 0
             }
           }
           // (r4: the d location-feature values of these rows were published by phase (c) from the NLOC rows)

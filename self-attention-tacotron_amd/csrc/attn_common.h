@@ -96,6 +96,20 @@ __device__ __forceinline__ float load_key1u(const float* __restrict__ kglob, con
   return kglob[(size_t)tt * U + dc];
 }
 
+// Saved factors of the energy nonlinearity (satt_attn_rnn_params.saf): ONE fp16 word per (step, memory row, unit), written by the
+// folded forward kernel, read by the backward kernel and the deferred parameter gradients - every use of the format is here.
+// With e = 2^(c x) and r = 1 / (1 + e) (tanh x = 1 - 2 r) the word is q = +m where r <= 1/2, -m otherwise, m = min(r, 1 - r),
+// in fp16 (source 1 rounded toward zero by the packed conversion of the forward store, source 2 to nearest): m keeps fp16 RELATIVE precision where tanh saturates (1 - r = e r: no cancellation), so
+//   r (1 - r) = m (1 - m)  and  tanh = sign(q) (1 - 2 m)
+// come out to a few fp16 ulps of relative error in every regime, and tanh to 2^-11 absolute.  (The format before stored s = r - 1/2
+// and rebuilt r (1 - r) = 1/4 - s^2: the fp16 spacing 2^-12 below 1/2 left every saturated unit a factor of >= 2.4e-4 - O(1)
+// relative error where the true value is 1e-6.)
+__device__ __forceinline__ float saf_encode(float e, float r) { return e >= 1.f ? r : -(e * r); }     // (e = inf: r = 0)
+__device__ __forceinline__ float saf_factor(float q) { const float m = fabsf(q); return m - m * m; }  // r (1 - r)
+__device__ __forceinline__ float saf_tanh(float q) { return __builtin_copysignf(1.f - 2.f * fabsf(q), q); }
+template <typename H>      // the factors of a vector of words in fp16 arithmetic (an MFMA operand): one fma each, m - m m
+__device__ __forceinline__ H saf_factor_h(H q) { const H m = __builtin_elementwise_abs(q); return m - m * m; }
+
 // Single-source form (U2 == 0 and V2 == 0: the baseline Tacotron decoder, reference modules/module.py:530-623): the
 // second mechanism degenerates to zero energies, uniform alignments and an empty context.  Its pointers may be NULL;
 // the kernels' clamped (always issued) loads are pointed at the first source, where they read finite values that

@@ -673,7 +673,7 @@ __global__ void attn_param_grads_k(const satt_attn_rnn_params p, const float* __
   }
 }
 
-// The same sums from the SAVED s = r - 1/2 of the forward pass (satt_attn_rnn_params.saf; tanh = -2 s): no keys, no processed query,
+// The same sums from the SAVED factor words of the forward pass (satt_attn_rnn_params.saf, attn_common.h): no keys, no processed query,
 // no score argument, no exp / rcp.  A WAVE owns one (sample, memory row) item at a time and lane l the units 4l .. 4l+3: the factors
 // of a step are one 8-byte load per thread (the rows of a workgroup's eight waves are 4 KB contiguous per step), d e and the
 // location features of the row are wave-uniform.  The grid is FIXED (pgs_nwg workgroups, ~2 items per wave at the benchmark
@@ -737,9 +737,9 @@ __global__ __launch_bounds__(64 * PGS_WAVES) void attn_param_grads_saf_k(const s
           float g[4];
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            const float th = -2.f * (float)s4[i][j];
-            g[j] = de * v[j] * (1.f - th * th);
-            dk[j] += g[j]; dv[j] += de * th; db[j] += g[j];
+            const float q = (float)s4[i][j];
+            g[j] = de * v[j] * (4.f * saf_factor(q));            // 1 - tanh^2 = 4 r (1 - r)
+            dk[j] += g[j]; dv[j] += de * saf_tanh(q); db[j] += g[j];
           }
           // d U: explicit two-wide products against a SPLAT of the feature.  (The scalar form compiled to v_pk_fma_f32 with an op_sel
           // broadcast of one half of a register pair; with that code the sums of 16 elements - filter 1, even units 192..222 - came

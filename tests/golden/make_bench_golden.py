@@ -16,6 +16,9 @@ The full tensors are too large to commit (gradient: 25 MB, alignments: 8 MB), so
 The reference (TF1 + tacotron2@6af04c7) cannot run here and holds no vectors: this pins the build's own
 restatement - "parity unpinned" with respect to TF stays true.  CPU only, ~15 min and ~25 GB for the LJSpeech case:
     python tests/golden/make_bench_golden.py [ljspeech] [vctk] [ljspeech_sharp_lo] [ljspeech_sharp_hi]
+The converged-regime fixtures also carry their bf16 floor (`floor`: the same oracle with bf16-rounded weight matrices, measured by
+`frozen_distances`; ~30 s of CPU per fixture with 4-6 threads), added to an existing fixture without touching its other keys by
+    python tests/golden/make_bench_golden.py --floor [ljspeech_sharp_lo] [ljspeech_sharp_hi]
 """
 import os
 import sys
@@ -53,6 +56,9 @@ CASES = {
                  batch=dict(B=32, Ti=80, Tm=500, seed=4321, min_source_length=30, min_target_steps=90, num_speakers=152,
                             speaker_offset=225)),
 }
+
+
+FLOOR_CASES = ("ljspeech_sharp_lo", "ljspeech_sharp_hi")     # fixtures that also carry the bf16-weight floor (`floor`)
 
 
 def sample_rows(B, Td, seed):
@@ -94,6 +100,96 @@ def sharpen_params(P, keep=0, sv=1.0, sq=1.0, sk=1.0):
     P["dec.att.Wq"] = (np.asarray(P["dec.att.Wq"], dtype=np.float64) * sq).astype(np.float32)
     P["dec.att1.Wm"] = (np.asarray(P["dec.att1.Wm"], dtype=np.float64) * sk).astype(np.float32)
     return P
+
+
+def frozen_distances(r, z, batch):
+    """Distances of one run from the frozen fixture z - the ONE definition that tests/test_pinned_gpu.py (the engine's run) and
+    `floor` below (the float64 oracle with bf16-rounded weight matrices) both use.  r: loss, mel_loss, mel [B,T,nm], al1 / al2
+    [B,Td,Ti], stop, dec_out [B,Td,.], lstm_out / sa_out [B,Ti,.], G {name: gradient}.  Returns (got: {metric: value},
+    tensor: per-tensor relative distances aligned with z["grad_names"] (NaN where the fixture's gradient is zero),
+    extra: row distances, largest path offset, |g| / |g_ref|)."""
+    from common import count_sketch
+    B, Td = batch["done"].shape
+    got = {}
+    got["mel_loss"] = abs(float(r["mel_loss"]) - float(z["mel_loss"]))
+    got["loss"] = abs(float(r["loss"]) - float(z["loss"]))
+    w = batch["spec_loss_mask"].astype(np.float64)
+    per = (np.abs(np.asarray(r["mel"], dtype=np.float64) - batch["mel"]).mean(-1) * w).sum(-1) / np.maximum(w.sum(-1), 1.0)
+    got["per_sample"] = float(np.abs(per - z["per_sample_mel_l1"]).max())
+    sb, st = z["rows_b"], z["rows_t"]
+    got["al1"] = float(np.abs(r["al1"][sb, st] - z["align1_rows"]).max())
+    got["al2"] = float(np.abs(r["al2"][sb, st] - z["align2_rows"]).max())
+    # argmax paths: compared where the run's maximum is not a near-tie (two memory rows within 2 % of each other flip freely)
+    p1 = r["al1"].argmax(-1)
+    top2 = np.sort(r["al1"], -1)[..., -2:]
+    clear = top2[..., 1] > 1.02 * top2[..., 0]
+    got["path"] = float((p1[clear] == z["path1"][clear]).mean())
+    off = int(np.abs(p1.astype(np.int64) - z["path1"]).max())
+    rel = lambda a, b: float(np.abs(np.asarray(a, np.float64) - b).max() / (np.abs(b).max() + 1e-12))
+    rows = dict(mel=rel(np.asarray(r["mel"]).reshape(B, Td, -1)[sb, st], z["mel_rows"]),
+                stop=rel(np.asarray(r["stop"]).reshape(B, Td)[sb, st], z["stop_rows"]),
+                dec_out=rel(np.asarray(r["dec_out"])[sb, st], z["dec_out_rows"]),
+                lstm_out=rel(np.asarray(r["lstm_out"])[z["enc_b"], z["enc_t"]], z["lstm_out_rows"]),
+                sa_out=rel(np.asarray(r["sa_out"])[z["enc_b"], z["enc_t"]], z["sa_out_rows"]))
+    got["rows"] = max(rows.values())
+    names = [str(n) for n in z["grad_names"]]
+    G = {k: np.asarray(r["G"][k], dtype=np.float64) for k in names}
+    flat = np.concatenate([G[k].ravel() for k in names])
+    ref_sk = z["grad_sketch_all"]
+    got["grad"] = float(np.linalg.norm(count_sketch(flat, int(z["meta.sketch_g"]), 0) - ref_sk) / np.linalg.norm(ref_sk))
+    gn = float(np.linalg.norm(flat) / float(z["grad_norm_all"]))
+    tensor = np.full(len(names), np.nan)
+    for i, k in enumerate(names):
+        nrm = float(z["grad_norms"][i])
+        if nrm == 0.0:
+            continue
+        if ("grad_full." + k) in z.files:
+            tensor[i] = np.linalg.norm(G[k] - z["grad_full." + k]) / nrm
+        else:
+            tensor[i] = np.linalg.norm(count_sketch(G[k], int(z["meta.sketch_t"]), i + 1) - z["grad_sketch." + k]) / nrm
+    # the worst tensor among those with gradient signal (>= 1e-6 of the total norm: nothing to be relative to below)
+    live = np.asarray(z["grad_norms"], dtype=np.float64) >= 1e-6 * float(z["grad_norm_all"])
+    got["tensor"] = float(np.nanmax(np.where(live, tensor, np.nan)))
+    return got, tensor, dict(rows=rows, off=off, gn=gn)
+
+
+def bf16_weights(P):
+    """every weight matrix (ndim >= 2) rounded to bf16, the rest as it is - the rule of make_decode_golden.py"""
+    return {k: (torch.as_tensor(np.asarray(v, dtype=np.float32)).to(torch.bfloat16).to(torch.float32).numpy()
+                if np.asarray(v).ndim >= 2 else v) for k, v in P.items()}
+
+
+def floor(name):
+    """The bf16 floor of a fixture: the SAME float64 oracle with every weight matrix rounded to bf16, measured against the fixture by
+    `frozen_distances`.  Adds floor.<metric> scalars and floor.tensor (aligned with grad_names) to bench_<name>.npz and leaves
+    every other key as it is."""
+    import satt_amd  # noqa: F401
+    from satt_amd.params import ModelConfig, init_params
+    from common import oracle_run
+    path = os.path.join(HERE, "bench_%s.npz" % name)
+    z = np.load(path)
+    keep = {k: z[k] for k in z.files if not k.startswith("floor.")}
+    case = CASES[name]
+    P = init_params(ModelConfig(**case["cfg"]), PARAM_SEED)
+    if "sharpen" in case:
+        P = sharpen_params(P, **case["sharpen"])
+    batch = make_batch(case["batch"])
+    assert int(z["meta.batch_crc"]) == crc_of(batch) and int(z["meta.param_crc"]) == crc_of(P)
+    t0 = time.time()
+    out, col, g = oracle_run(case["cfg"], bf16_weights(P), batch, True, seed=RNG_SEED)
+    print("%s: bf16-weight oracle forward + backward %.0f s" % (name, time.time() - t0), flush=True)
+    r = dict(loss=out["loss"].detach(), mel_loss=out["mel_loss"].detach(), mel=out["mel"].detach().numpy(),
+             al1=out["alignment1"].detach().numpy(), al2=out["alignment2"].detach().numpy(), stop=out["stop"].detach().numpy(),
+             dec_out=col["dec_out"].detach().numpy(), lstm_out=out["lstm_out"].detach().numpy(), sa_out=out["sa_out"].detach().numpy(),
+             G=g)
+    got, tensor, extra = frozen_distances(r, z, batch)
+    names = [str(n) for n in z["grad_names"]]
+    print("%s floor: " % name + " ".join("%s=%.3e" % kv for kv in got.items()) + " | rows %s" % extra["rows"], flush=True)
+    print("%s floor, largest tensors: " % name + " ".join("%s=%.3e" % (names[i], tensor[i]) for i in np.argsort(-np.nan_to_num(tensor))[:8]))
+    keep.update({"floor." + k: np.float64(v) for k, v in got.items() if k != "tensor"})     # (the worst tensor: max of floor.tensor)
+    keep["floor.tensor"] = tensor
+    np.savez_compressed(path, **keep)
+    print("%s: wrote %s (%.0f KB)" % (name, path, os.path.getsize(path) / 1024), flush=True)
 
 
 def build(name):
@@ -154,5 +250,12 @@ def build(name):
 
 if __name__ == "__main__":
     torch.set_num_threads(int(os.environ.get("SATT_ORACLE_THREADS", "6")))
-    for n in (sys.argv[1:] or list(CASES)):
-        build(n)
+    args = sys.argv[1:]
+    if args[:1] == ["--floor"]:          # the bf16 floor of existing fixtures (default: the converged-regime ones)
+        for n in (args[1:] or FLOOR_CASES):
+            floor(n)
+    else:
+        for n in (args or list(CASES)):
+            build(n)
+            if n in FLOOR_CASES:
+                floor(n)

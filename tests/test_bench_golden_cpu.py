@@ -82,3 +82,18 @@ def test_count_sketch_measures_relative_distance():
         est = np.linalg.norm(count_sketch(a, 4096, 0) - count_sketch(b, 4096, 0)) / np.linalg.norm(count_sketch(a, 4096, 0))
         assert abs(est / true - 1.0) < 0.1, (eps, true, est)
     assert not np.allclose(count_sketch(a, 1024, 3), count_sketch(a, 1024, 4))       # the salt selects the projection
+
+
+def test_converged_fixtures_carry_their_bf16_floor():
+    """make_bench_golden.py `floor`: the bf16-weight oracle's distances from each converged-regime fixture - one finite positive scalar
+    per metric and one per parameter tensor (floor.tensor, aligned with grad_names) - that tests/test_pinned_gpu.py anchors its bf16 bars to"""
+    from golden.make_bench_golden import FLOOR_CASES
+    for name in FLOOR_CASES:
+        z = np.load(os.path.join(GOLD, "bench_%s.npz" % name))
+        for k in ("mel_loss", "loss", "per_sample", "al1", "al2", "path", "rows", "grad"):
+            v = z["floor." + k]
+            assert v.shape == () and np.isfinite(v) and v > 0, (name, k, v)
+        t = z["floor.tensor"]
+        assert t.shape == z["grad_names"].shape and t.dtype == np.float64, (name, t.shape)
+        live = z["grad_norms"] >= 1e-6 * float(z["grad_norm_all"])
+        assert np.isfinite(t[live]).all() and (t[live] > 0).all(), name

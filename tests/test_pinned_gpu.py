@@ -157,6 +157,32 @@ FROZEN_BARS_SHARP = {
 # 7.5e-3 / 6.4e-2, 9.6e-3 / 6.2e-2, 7.5e-2 (dec.att1.bF) / 0.95 (dec.att1.U: the location term's gradient at sum|v| = 443).  The mel-L1 loss -
 # BASELINE's bar, 1e-3 - stays at the diffuse regime's 1e-6 .. 8e-6 in both forms of the forward variable's softmax.
 
+# bf16 bars of the converged-regime fixtures anchored to their floor (tests/golden/make_bench_golden.py `floor`: the same float64 oracle
+# with every weight matrix rounded to bf16, measured by the same `frozen_distances`): each bar = min(3 x floor, the bar above), relative
+# bars below 0.5; per tensor 3 x that tensor's own floor.  The two losses keep BASELINE's bars: a single signed scalar whose bf16-weight
+# difference cancels by chance (sharp_lo floor 2.8e-7) anchors nothing.
+FLOOR_ANCHORED = ("per_sample", "al1", "al2", "rows", "grad")
+REL_CAP = 0.49
+# OPEN: tensors whose bf16 distance exceeds 3 x their floor on this fixture - not explained by the saved attention factors (the same
+# 1.079 with the backward kernel recomputing them); bars ~1.5x the measured distance instead of 3.0 until it is found
+OPEN_TENSORS = {("ljspeech_sharp_hi", "bf16"): {"dec.att1.U": 1.6, "dec.att1.F": 1.1}}
+
+
+def anchored_bars(name, prec, z):
+    """(metric bars, per-tensor bars aligned with z["grad_names"]) of a converged-regime fixture"""
+    bars = dict(FROZEN_BARS_SHARP[name][prec])
+    names = [str(n) for n in z["grad_names"]]
+    tbar = np.full(len(names), bars["tensor"])
+    if prec == "bf16":
+        for k in FLOOR_ANCHORED:
+            bars[k] = min(bars[k], 3.0 * float(z["floor." + k]), REL_CAP)
+        fl = np.asarray(z["floor.tensor"], dtype=np.float64)
+        tbar = np.where(np.isfinite(fl), np.minimum(tbar, 3.0 * fl), tbar)
+        tbar = np.minimum(tbar, REL_CAP)
+        for k, b in OPEN_TENSORS.get((name, prec), {}).items():
+            tbar[names.index(k)] = min(b, bars["tensor"])
+    return bars, tbar
+
 
 @pytest.mark.parametrize("prec", ["f32", "bf16"])
 @pytest.mark.parametrize("name", ["ljspeech", "vctk", "ljspeech_sharp_lo", "ljspeech_sharp_hi"])
@@ -167,8 +193,7 @@ def test_bench_workload_vs_frozen_float64_oracle(name, prec):
     mel-L1, both alignments (argmax paths + sampled rows), sampled output rows, and the gradient through count sketches
     (flat + per tensor; small tensors in full).  Until r4 these two workloads were only judged by the engine's own f32 mode."""
     from test_model_gpu import assert_same_xcd_fast_path
-    from common import count_sketch
-    from golden.make_bench_golden import CASES, make_batch, sample_rows, sharpen_params
+    from golden.make_bench_golden import CASES, frozen_distances, make_batch, sample_rows, sharpen_params
     from satt_amd.params import ModelConfig, init_params
     z = np.load(os.path.join(GOLD, "bench_%s.npz" % name))
     case = CASES[name]
@@ -185,50 +210,25 @@ def test_bench_workload_vs_frozen_float64_oracle(name, prec):
     eng.last_ctx = ctx
     assert_same_xcd_fast_path(eng, B)
     _invariants(r, batch)
-    bars = FROZEN_BARS_SHARP[name][prec] if name in FROZEN_BARS_SHARP else FROZEN_BARS[prec]
-    got = {}
-    got["mel_loss"] = abs(r["mel_loss"] - float(z["mel_loss"]))
-    got["loss"] = abs(r["loss"] - float(z["loss"]))
-    w = batch["spec_loss_mask"].astype(np.float64)
-    per = (np.abs(r["mel"].astype(np.float64) - batch["mel"]).mean(-1) * w).sum(-1) / np.maximum(w.sum(-1), 1.0)
-    got["per_sample"] = float(np.abs(per - z["per_sample_mel_l1"]).max())
-    sb, st = z["rows_b"], z["rows_t"]
     sb2, st2 = sample_rows(B, Td, 99)
-    assert np.array_equal(sb, sb2) and np.array_equal(st, st2)
-    got["al1"] = float(np.abs(r["al1"][sb, st] - z["align1_rows"]).max())
-    got["al2"] = float(np.abs(r["al2"][sb, st] - z["align2_rows"]).max())
-    # argmax paths: compared where the oracle's maximum is not a near-tie (two memory rows within 2 % of each other flip freely)
-    p1 = r["al1"].argmax(-1)
-    top2 = np.sort(r["al1"], -1)[..., -2:]
-    clear = top2[..., 1] > 1.02 * top2[..., 0]
-    got["path"] = float((p1[clear] == z["path1"][clear]).mean())
-    off = np.abs(p1.astype(np.int64) - z["path1"]).max()
-    rel = lambda a, b: float(np.abs(np.asarray(a, np.float64) - b).max() / (np.abs(b).max() + 1e-12))
-    rows = dict(mel=rel(r["mel"].reshape(B, Td, -1)[sb, st], z["mel_rows"]), stop=rel(r["stop"].reshape(B, Td)[sb, st], z["stop_rows"]),
-                dec_out=rel(r["dec_out"][sb, st], z["dec_out_rows"]), lstm_out=rel(r["lstm_out"][z["enc_b"], z["enc_t"]], z["lstm_out_rows"]),
-                sa_out=rel(r["sa_out"][z["enc_b"], z["enc_t"]], z["sa_out_rows"]))
-    got["rows"] = max(rows.values())
+    assert np.array_equal(z["rows_b"], sb2) and np.array_equal(z["rows_t"], st2)
+    got, tensor, extra = frozen_distances(r, z, batch)
     names = [str(n) for n in z["grad_names"]]
-    flat = np.concatenate([r["G"][k].ravel() for k in names])
-    ref_sk = z["grad_sketch_all"]
-    got["grad"] = float(np.linalg.norm(count_sketch(flat, int(z["meta.sketch_g"]), 0) - ref_sk) / np.linalg.norm(ref_sk))
-    gn = float(np.linalg.norm(flat) / float(z["grad_norm_all"]))
-    worst, wname = 0.0, None
-    for i, k in enumerate(names):
-        nrm = float(z["grad_norms"][i])
-        if nrm < 1e-6 * float(z["grad_norm_all"]):
-            continue                                  # (a tensor without gradient signal: nothing to be relative to)
-        if ("grad_full." + k) in z.files:
-            d = float(np.linalg.norm(r["G"][k] - z["grad_full." + k]) / nrm)
-        else:
-            d = float(np.linalg.norm(count_sketch(r["G"][k], int(z["meta.sketch_t"]), i + 1) - z["grad_sketch." + k]) / nrm)
-        if d > worst:
-            worst, wname = d, k
-    got["tensor"] = worst
+    live = np.asarray(z["grad_norms"], dtype=np.float64) >= 1e-6 * float(z["grad_norm_all"])
+    if name in FROZEN_BARS_SHARP:
+        bars, tbar = anchored_bars(name, prec, z)
+    else:
+        bars, tbar = FROZEN_BARS[prec], np.full(len(names), FROZEN_BARS[prec]["tensor"])
+    fl = z["floor.tensor"] if "floor.tensor" in z.files else np.full(len(names), np.nan)
+    order = np.argsort(-np.nan_to_num(np.where(live, tensor, 0.0)))
+    print("[frozen oracle] %s %s per tensor (distance / bf16-weight floor / bar), largest 12: " % (name, prec) +
+          " ".join("%s=%.3e/%.3e/%.2f" % (names[i], tensor[i], fl[i], tbar[i]) for i in order[:12]))
     print("[frozen oracle] %s %s: " % (name, prec) + " ".join("%s=%.3e" % kv for kv in got.items()) +
-          " | rows %s | max path offset %d | |g|/|g_ref|=%.5f | worst tensor %s" % ({k: "%.2e" % v for k, v in rows.items()}, off, gn, wname))
-    bad = {k: v for k, v in got.items() if (v < bars[k] if k == "path" else not v < bars[k])}
+          " | rows %s | max path offset %d | |g|/|g_ref|=%.5f" % ({k: "%.2e" % v for k, v in extra["rows"].items()}, extra["off"], extra["gn"]))
+    bad = {k: v for k, v in got.items() if k != "tensor" and (v < bars[k] if k == "path" else not v < bars[k])}
+    bad.update({names[i]: (float(tensor[i]), float(tbar[i])) for i in np.nonzero(live)[0] if not tensor[i] < tbar[i]})
     assert not bad, (bad, bars)
+    gn = extra["gn"]
     assert abs(gn - 1.0) < (2e-3 if prec == "f32" else 2e-2), gn
 
 
