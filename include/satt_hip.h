@@ -123,6 +123,28 @@ int satt_embedding_bwd(const int64_t* ids, const float* dout, float* dtable, int
 int satt_embedding_bwd_rows(const int64_t* ids, const float* dout, float* dtable, int n, int dim, int offset, int nrows,
                             void* stream);
 
+/* Accent-type branch of SelfAttentionCBHGEncoderWithAccentType (modules/module.py:444-527) in one launch each way:
+ *   e = table[ids[i] - offset, :dim]  (ntypes rows; ids outside the table are clamped - memory safety only, the input pipeline
+ *   rejects or remaps them);  y = PreNet stack (Dense W0 [dim,n0] + b0, ReLU, dropout; then W1 [n0,n1] + b1 likewise when
+ *   nlayers == 2; W1 = b1 = NULL, n1 ignored when nlayers == 1);  out[i*ldo + c] = y[i, c]  - `out` normally points at column Wp of
+ *   the [rows, Wp + Wa] pre-net buffer whose first Wp columns the phoneme pre-net GEMM writes (ldo = Wp + Wa: no concatenation copy).
+ * Dropout: keep(seed, stream0 / stream1, i*n + c) with n the layer's OWN width (the mask of a [B, Ti, n] tensor), drop_thresh 0 = off.
+ * fp32 throughout, all weights in LDS.  Cap: nlayers 1 or 2, dim / n0 / n1 <= 64 and an LDS footprint <= 64 KB (backward:
+ * + 64-row tiles + ntypes*dim accumulator); beyond it SATT_E_UNSUPPORTED and nothing is launched (compose the branch from
+ * satt_embedding_fwd + satt_gemm).
+ * Backward: dout = gradient of `out` (same column view, stride ldd).  Recomputes the activations from the ids, then
+ * dW0, db0, dW1, db1 += (block-reduced, one float atomic per element and workgroup) and dtable[ids - offset] += (summed per
+ * workgroup in LDS first: many tokens share few accent ids). */
+int satt_accent_prenet_fwd(const int64_t* ids, const float* table, int ntypes, int offset, int dim, int nlayers,
+                           const float* W0, const float* b0, int n0, const float* W1, const float* b1, int n1,
+                           float* out, int64_t ldo, int rows, uint32_t drop_thresh, float drop_scale, uint32_t stream0,
+                           uint32_t stream1, const uint32_t* seed, void* stream);
+int satt_accent_prenet_bwd(const int64_t* ids, const float* table, int ntypes, int offset, int dim, int nlayers,
+                           const float* W0, const float* b0, int n0, const float* W1, const float* b1, int n1,
+                           const float* dout, int64_t ldd, int rows, uint32_t drop_thresh, float drop_scale,
+                           uint32_t stream0, uint32_t stream1, const uint32_t* seed, float* dtable, float* dW0, float* db0,
+                           float* dW1, float* db1, void* stream);
+
 /* dx = dy * act'(y) (* scale where y != 0 for dropout-after-relu); y is the POST-activation(-dropout) output */
 int satt_act_bwd(const float* dy, int64_t lddy, const float* y, int64_t ldy, float* dx, int64_t lddx,
                  int rows, int cols, int act, float scale, void* stream);

@@ -26,6 +26,7 @@ extern "C" {
 #define SATT_IO_E_TOO_MANY (-5)
 #define SATT_IO_E_MALFORMED (-6)
 #define SATT_IO_E_BADARG (-7)
+#define SATT_IO_E_ACCENT (-9)      /* the source record's accent_type feature does not hold source_length int64 values */
 #define SATT_IO_E_IO (-8)          /* a file could not be opened or read: satt_io_last_errno() holds the errno (per thread) */
 
 int satt_io_version(void);
@@ -81,6 +82,10 @@ typedef struct {
   int64_t source_off, source_count;       /* int64 values of the `source` bytes field */
   int64_t target_id, target_length, mel_width, mel_off, mel_count;   /* mel_count floats at mel_off */
   int64_t prepared_length;                /* satt_prepared_length(target_length, r) */
+  /* optional `accent_type` bytes feature of the source record (this project's record contract): raw little-endian
+   * int64, exactly source_length entries.  accent_count = -1 when the record has no such feature; a feature of any other
+   * length is SATT_IO_E_ACCENT.  Range checks against the model's table are the batch assembler's (they need hparams). */
+  int64_t accent_off, accent_count;
 } satt_utterance;
 /* Returns 0, or SATT_IO_E_* (framing / checksum / protobuf damage; SATT_IO_E_IO: a file cannot be opened or read; SATT_IO_E_BADARG: a required
  * field is missing or mel_count != target_length * mel_width).  SATT_IO_E_TOO_MANY: the arena is too small - out->src_bytes

@@ -65,7 +65,7 @@ def main(argv=None):
             # batch size 1, targets merged into the source side (reference predict_mel.py:46-50)
             return dataset_factory(src, tgt, hparams).prepare_and_zip().group_by_batch(batch_size=1) \
                 .merge_target_to_source()
-        from satt_amd.datasets.ljspeech import decode_source_record
+        from satt_amd.datasets.ljspeech import decode_source_record, resolve_accent_types
 
         def gen():
             for f in src:
@@ -74,6 +74,10 @@ def main(argv=None):
                          id=np.array([s.id], np.int64), key=[s.key], text=[s.text])
                 if s.speaker_id >= 0:
                     b["speaker_id"] = np.array([s.speaker_id], np.int64)
+                if hparams.use_accent_type:       # same unknown-id mapping and missing-field error as the batched reader
+                    acc = np.full((1, len(s.source)), hparams.accent_type_offset, np.int64)
+                    acc[0, :s.source_length] = resolve_accent_types(s, hparams)
+                    b["accent_type"] = acc
                 yield b
         return gen()
 
@@ -92,7 +96,7 @@ def main(argv=None):
             tf_ = os.path.join(a.target_data_root, "%s.%s" % (key, hparams.target_file_extension))
             if os.path.exists(tf_):
                 gt = decode_target_record(next(tfrecord.read_records(tf_)))["mel"]
-        tfrecord.write_prediction_result(p["id"], key, aligns, mel, gt, p["text"] or "", p["source"], None,
+        tfrecord.write_prediction_result(p["id"], key, aligns, mel, gt, p["text"] or "", p["source"], p.get("accent_type"),
                                          os.path.join(a.output_dir, "%s.tfrecord" % key))
         print("%s: %d frames" % (key, mel.shape[0]))
 

@@ -13,6 +13,7 @@ c_i64, c_u32, c_sz, _P = ctypes.c_int64, ctypes.c_uint32, ctypes.c_size_t, ctype
 
 ERRORS = {-1: "truncated record header", -2: "corrupt length field", -3: "truncated record", -4: "corrupt record payload",
           -5: "too many entries for the caller's table", -6: "malformed protobuf message", -7: "bad argument",
+          -9: "the accent_type feature does not hold source_length int64 values",
           -8: "file cannot be opened or read"}
 
 
@@ -26,7 +27,8 @@ class Utterance(ctypes.Structure):
     """satt_utterance (include/satt_io.h)"""
     _fields_ = [(n, c_i64) for n in ("src_bytes", "tgt_bytes", "src_records", "tgt_records", "id", "source_length", "speaker_id",
                                      "age", "gender", "key_off", "key_len", "text_off", "text_len", "source_off", "source_count",
-                                     "target_id", "target_length", "mel_width", "mel_off", "mel_count", "prepared_length")]
+                                     "target_id", "target_length", "mel_width", "mel_off", "mel_count", "prepared_length", "accent_off",
+                                     "accent_count")]
 
 
 _SIGS = {

@@ -141,6 +141,9 @@ SIGNATURES = {
     "satt_embedding_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "satt_embedding_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "satt_embedding_bwd_rows": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "satt_accent_prenet_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, c_i64, _I, c_u32, _F, c_u32, c_u32, _P, _P]),
+    "satt_accent_prenet_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, c_i64, _I, c_u32, _F, c_u32, c_u32, _P,
+                                    _P, _P, _P, _P, _P, _P]),
     "satt_act_bwd": (_I, [_P, c_i64, _P, c_i64, _P, c_i64, _I, _I, _I, _F, _P]),
     "satt_act_bwd_res": (_I, [_P, c_i64, _P, c_i64, _P, c_i64, _P, c_i64, _I, _I, _I, _F, _P]),
     "satt_bn_ws_floats": (c_i64, [_I, _I]),

@@ -18,6 +18,11 @@ __device__ __forceinline__ bool satt_keep(uint32_t seed, uint32_t stream, uint32
   return satt_hash(seed, stream, idx) >= thresh;
 }
 
+// dropout streams of the accent pre-net layers (csrc/accent_prenet.hip; engine.py S_ACCENT_PRENET0 / 1 pass them in, the tests'
+// float64 reference draws its masks on the same numbers).  The other sites' ids are listed in engine.py == oracle/rng.py.
+constexpr uint32_t SATT_STREAM_ACCENT_PRENET0 = 40u;
+constexpr uint32_t SATT_STREAM_ACCENT_PRENET1 = 41u;
+
 // two fp32 -> packed bf16 pair (lo = a, hi = b) with the gfx950 conversion instruction v_cvt_pk_bf16_f32
 // (round-to-nearest-even: bitwise equal to f2bf for finite values)
 __device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {

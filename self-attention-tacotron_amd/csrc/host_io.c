@@ -357,6 +357,12 @@ int64_t satt_utterance_load(const char* source_path, const char* target_path, in
   out->source_off = offs[0] + f->val_off; out->source_count = f->val_len / 8;
   /* a length beyond the ids the record holds would reach the device kernels as an out-of-range sequence length */
   if (out->source_length < 0 || out->source_length > out->source_count) return SATT_IO_E_BADARG;
+  out->accent_off = 0; out->accent_count = -1;
+  f = find(ps, fs, n, "accent_type");
+  if (f && f->count >= 1) {        /* one accentual-type id per symbol: exactly source_length int64 values */
+    if (f->kind != 1 || f->val_len % 8 || f->val_len / 8 != out->source_length) return SATT_IO_E_ACCENT;
+    out->accent_off = offs[0] + f->val_off; out->accent_count = f->val_len / 8;
+  }
   /* ---- target record */
   const uint8_t* pt = arena + offs[1];
   n = satt_example_index(pt, (size_t)lens[1], fs, MAXF);

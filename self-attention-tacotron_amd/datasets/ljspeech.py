@@ -25,7 +25,10 @@ import numpy as np
 from .. import _io
 from ..utils import tfrecord
 
-SourceData = namedtuple("SourceData", ["id", "key", "source", "source_length", "text", "speaker_id", "age", "gender"])
+# accent_type: the accentual-type label of every symbol (int64 [source_length], raw ids) or None when the record has no such
+# field - THIS PROJECT'S record contract (the reference ships no accent corpus)
+SourceData = namedtuple("SourceData", ["id", "key", "source", "source_length", "text", "speaker_id", "age", "gender", "accent_type"],
+                        defaults=(None,))
 MelData = namedtuple("MelData", ["id", "key", "mel", "mel_width", "target_length", "done", "spec_loss_mask",
                                  "binary_loss_mask"])
 
@@ -34,11 +37,23 @@ def _scalar(v, default=0):
     return int(v[0]) if len(v) else default
 
 
+def _accent_array(raw, key, source_length):
+    """the optional `accent_type` bytes feature: raw little-endian int64, exactly source_length entries"""
+    if raw is None:
+        return None
+    if len(raw) % 8 or len(raw) // 8 != source_length:
+        raise ValueError("source record %s: accent_type holds %d bytes, source_length = %d needs %d"
+                         % (key, len(raw), source_length, 8 * source_length))
+    return np.frombuffer(raw, dtype="<i8").astype(np.int64)
+
+
 def decode_source_record(payload):
-    """`<key>.source.tfrecord` payload: id, key, source (raw int64 bytes), source_length, text [, speaker_id, age, gender]"""
+    """`<key>.source.tfrecord` payload: id, key, source (raw int64 bytes), source_length, text [, speaker_id, age, gender]
+    [, accent_type (raw int64 bytes, source_length entries)]"""
     f = tfrecord.parse_example(payload)
     src = np.frombuffer(f["source"][0], dtype="<i8").astype(np.int64)
-    return SourceData(id=_scalar(f["id"]), key=f["key"][0].decode("utf-8"), source=src,
+    acc = _accent_array(f["accent_type"][0] if f.get("accent_type") else None, f["key"][0].decode("utf-8"), _scalar(f["source_length"]))
+    return SourceData(accent_type=acc, id=_scalar(f["id"]), key=f["key"][0].decode("utf-8"), source=src,
                       source_length=_scalar(f["source_length"]), text=f["text"][0].decode("utf-8") if "text" in f else "",
                       speaker_id=_scalar(f.get("speaker_id", []), -1), age=_scalar(f.get("age", []), -1),
                       gender=_scalar(f.get("gender", []), -1))
@@ -89,7 +104,10 @@ def decode_source_view(payload):
     """decode_source_record over the C index of the payload (bytes or memoryview)"""
     idx = _io.example_index(payload)
     src = np.frombuffer(_first(payload, idx, "source"), dtype="<i8").astype(np.int64)
-    return SourceData(id=_int(payload, idx, "id"), key=bytes(_first(payload, idx, "key")).decode("utf-8"), source=src,
+    key = bytes(_first(payload, idx, "key")).decode("utf-8")
+    has_acc = "accent_type" in idx and idx["accent_type"][2]
+    acc = _accent_array(bytes(_first(payload, idx, "accent_type")) if has_acc else None, key, _int(payload, idx, "source_length"))
+    return SourceData(accent_type=acc, id=_int(payload, idx, "id"), key=key, source=src,
                       source_length=_int(payload, idx, "source_length"),
                       text=bytes(_first(payload, idx, "text")).decode("utf-8") if "text" in idx and idx["text"][2] else "",
                       speaker_id=_int(payload, idx, "speaker_id", -1), age=_int(payload, idx, "age", -1),
@@ -200,6 +218,24 @@ class PinnedBatch(dict):
     pinned = None
 
 
+def resolve_accent_types(s, hparams):
+    """the accent ids of one utterance as the model takes them: a record without the field is an error naming the key; ids
+    outside [accent_type_offset, accent_type_offset + num_accent_type) become accent_type_unknown when that lies in the range and
+    are an error otherwise"""
+    if s.accent_type is None:
+        raise ValueError("source record %s has no accent_type feature (use_accent_type=True needs one per utterance)" % s.key)
+    lo, hi = hparams.accent_type_offset, hparams.accent_type_offset + hparams.num_accent_type
+    acc = s.accent_type
+    bad = (acc < lo) | (acc >= hi)
+    if bad.any():
+        unk = hparams.accent_type_unknown
+        if not lo <= unk < hi:
+            raise ValueError("source record %s: accent_type %d outside [%d, %d) and accent_type_unknown = %d is outside it too"
+                             % (s.key, int(acc[bad][0]), lo, hi, unk))
+        acc = np.where(bad, unk, acc)
+    return acc
+
+
 def pad_batch(pairs, hparams, ring=None):
     """list of (SourceData, MelData | RawTarget) -> the engine's batch dict (padding values of group_by_batch, :264-281).
     RawTarget elements are normalised and silence-padded straight into their row of the batch tensor (satt_prepare_mel);
@@ -216,6 +252,9 @@ def pad_batch(pairs, hparams, ring=None):
     else:
         new = lambda name, shape, dtype: np.empty(shape, dtype)
     source = new("source", (B, Ti), np.int64); source.fill(0)
+    accent = None
+    if getattr(hparams, "use_accent_type", False):       # padded with accent_type_offset (table row 0) where source pads with 0
+        accent = new("accent_type", (B, Ti), np.int64); accent.fill(hparams.accent_type_offset)
     mel = new("mel", (B, Tm, W), np.float32)
     done = new("done", (B, Tm // r), np.float32); done.fill(1.0)
     smask = new("spec_loss_mask", (B, Tm), np.float32); smask.fill(0.0)
@@ -223,6 +262,8 @@ def pad_batch(pairs, hparams, ring=None):
     tables = None
     for b, (s, m) in enumerate(pairs):
         source[b, :len(s.source)] = s.source
+        if accent is not None:
+            accent[b, :s.source_length] = resolve_accent_types(s, hparams)
         L = m.target_length
         if isinstance(m, RawTarget):
             if tables is None:
@@ -246,6 +287,8 @@ def pad_batch(pairs, hparams, ring=None):
                  spec_loss_mask=smask, binary_loss_mask=bmask,
                  id=np.array([s.id for s, _ in pairs], np.int64), key=[s.key for s, _ in pairs],
                  text=[s.text for s, _ in pairs])
+    if accent is not None:
+        batch["accent_type"] = accent
     if pairs[0][0].speaker_id >= 0:
         batch["speaker_id"] = np.array([s.speaker_id for s, _ in pairs], np.int64)
     if ring is not None:
@@ -467,7 +510,9 @@ class Dataset:
                         source=np.frombuffer(mv[u.source_off:u.source_off + 8 * u.source_count], dtype="<i8").astype(np.int64),
                         source_length=int(u.source_length),
                         text=bytes(mv[u.text_off:u.text_off + u.text_len]).decode("utf-8") if u.text_len else "",
-                        speaker_id=int(u.speaker_id), age=int(u.age), gender=int(u.gender))
+                        speaker_id=int(u.speaker_id), age=int(u.age), gender=int(u.gender),
+                        accent_type=np.frombuffer(mv[u.accent_off:u.accent_off + 8 * u.accent_count], dtype="<i8").astype(np.int64)
+                        if u.accent_count >= 0 else None)
         mel = np.frombuffer(mv[u.mel_off:u.mel_off + 4 * u.mel_count], dtype="<f4").reshape(T, W)
         return s_, RawTarget(int(u.target_id), key, mel, W, int(u.prepared_length), T, lease)
 

@@ -26,6 +26,7 @@ S_DEC_PRENET0, S_DEC_PRENET1 = 8, 9
 S_ATT_C, S_ATT_H, S_L1_C, S_L1_H, S_L2_C, S_L2_H = 10, 11, 12, 13, 14, 15
 S_DEC_SA = 16
 S_POSTNET0 = 17   # + layer index
+S_ACCENT_PRENET0, S_ACCENT_PRENET1 = 40, 41      # accent pre-net layers (csrc/common.h SATT_STREAM_ACCENT_PRENET0 / 1)
 
 
 class Engine:
@@ -663,24 +664,45 @@ class Engine:
         slen = batch["source_length"]
         # batch["embedded"] ([B, Ti, embedding_dim]): the already embedded inputs, as the reference's encoder layers receive
         # them (modules/module.py:425: call(inputs, input_lengths)) - used by the callable module contracts (modules/module.py)
-        B, Ti = batch["embedded"].shape[:2] if "embedded" in batch else batch["source"].shape
+        if "embedded" in batch:
+            e0 = batch["embedded"]
+            B, Ti = (e0[0] if isinstance(e0, (tuple, list)) else e0).shape[:2]
+        else:
+            B, Ti = batch["source"].shape
         M = B * Ti
         seed = self.seed
         rate = (lambda r: r) if training else (lambda r: 0.0)
         self._wait_shadows()      # bf16 weight shadows refreshed on a side stream after the last update
         # ---- encoder (reference modules/module.py:425-438, :77-110)
+        acc_emb = None
         if "embedded" in batch:
-            emb = batch["embedded"].to(torch.float32).reshape(M, c.embedding_dim).contiguous()
+            emb = batch["embedded"]
+            if c.accent:       # the reference's accent encoder is called with the tuple (embedded, accent_embedded), module.py:507-508
+                if not isinstance(emb, (tuple, list)) or len(emb) != 2:
+                    raise ValueError("an accent-type encoder takes inputs = (embedded [B, Ti, %d], accent_embedded [B, Ti, %d])"
+                                     % (c.embedding_dim, c.accent_dim))
+                emb, acc_emb = emb
+                acc_emb = acc_emb.to(torch.float32).reshape(M, c.accent_dim).contiguous()
+            emb = emb.to(torch.float32).reshape(M, c.embedding_dim).contiguous()
         else:
+            if c.accent and "accent_type" not in batch:
+                raise KeyError("accent_type: a model with use_accent_type=True needs batch['accent_type'] (int64 [B, Ti])")
             emb = self._e(M, c.embedding_dim)
             ops.embedding_fwd(batch["source"], P["embedding"], emb)
+        # with accent types the two pre-net stacks share ONE output buffer [M, Wp + Wa] (module.py:510: concat): the last phoneme
+        # GEMM writes columns [0, Wp) through its leading dimension, the accent kernel columns [Wp, Wp + Wa)
+        Wp = c.enc_prenet[-1]
+        shared = self._e(M, c.prenet_width) if c.accent else None
         x = emb
         pre = []
         for n, o in enumerate(c.enc_prenet):
-            y = self._e(M, o)
+            y = shared[:, :Wp] if (shared is not None and n == len(c.enc_prenet) - 1) else self._e(M, o)
             ops.linear(x, self.W(f"enc.prenet{n}.W"), P[f"enc.prenet{n}.b"], y, act=ACT_RELU,
                        drop=Drop(rate(c.enc_prenet_drop), (S_ENC_PRENET0, S_ENC_PRENET1)[n], seed))
             pre.append(y); x = y
+        if c.accent:
+            self._accent_fwd(batch, acc_emb, shared[:, Wp:], rate(c.enc_prenet_drop), ctx)
+            x = shared
         p1 = x
         CC, K = c.conv_channels, c.max_filter_width
         nb = CC * K
@@ -770,10 +792,72 @@ class Engine:
                 enc_aligns.append(al)
             enc_align = enc_aligns[0]
             ctx["enc_aligns"] = enc_aligns
-        ctx.update(emb=emb, pre=pre, bank_pre=bank_pre, bank=bank, mp=mp, pr1_pre=pr1_pre, pr1=pr1, pr2_pre=pr2_pre,
+        ctx.update(emb=emb, pre=pre, p1=p1, bank_pre=bank_pre, bank=bank, mp=mp, pr1_pre=pr1_pre, pr1=pr1, pr2_pre=pr2_pre,
                    bn_st=bn_st, hws=hws, zs=zs, enc_lstm=(eg, ecn, ecs, ehs), lstm_out=lstm_out, sa_in=sa_in,
                    sa_out=sa_out, enc_align=enc_align)
         return lstm_out, sa_out
+
+    fused_accent = True     # False: the accent branch is composed from embedding_fwd + linear (what the kernel's cap falls back to)
+
+    def _accent_drops(self, r):
+        return [Drop(r, (S_ACCENT_PRENET0, S_ACCENT_PRENET1)[n], self.seed) for n in range(len(self.cfg.accent_prenet))]
+
+    def _accent_fwd(self, batch, acc_emb, out, r, ctx):
+        """accent_embedding -> PreNet stack (modules/module.py:470-472,509: same PreNet, same drop rate, is_training) -> `out`, the
+        trailing columns of the shared pre-net buffer.  One launch (csrc/accent_prenet.hip) when the ids are given and the shape is
+        within the kernel's cap; otherwise composed from embedding_fwd + linear, the activations kept for the backward."""
+        c, P = self.cfg, self.P
+        L = len(c.accent_prenet)
+        Ws = [P[f"enc.accent_prenet{n}.W"] for n in range(L)]
+        bs = [P[f"enc.accent_prenet{n}.b"] for n in range(L)]
+        drops = self._accent_drops(r)
+        ctx["accent_fused"] = False
+        if acc_emb is None and self.fused_accent and \
+                ops.accent_prenet_fwd(batch["accent_type"], P["accent_embedding"], c.accent_offset, Ws, bs, out, drops):
+            ctx["accent_fused"] = True
+            return
+        M = out.shape[0]
+        if acc_emb is None:
+            acc_emb = self._e(M, c.accent_dim)
+            ops.embedding_fwd(batch["accent_type"], P["accent_embedding"], acc_emb, offset=c.accent_offset)
+        x, acts = acc_emb, [acc_emb]
+        for n, o in enumerate(c.accent_prenet):
+            y = out if n == L - 1 else self._e(M, o)
+            ops.linear(x, Ws[n], bs[n], y, act=ACT_RELU, drop=drops[n])
+            acts.append(y); x = y
+        ctx["accent_acts"] = acts
+
+    def _accent_bwd(self, ctx, dout, r):
+        """gradients of the accent branch from dout = columns [Wp, Wp + Wa) of the pre-net output gradient (a strided view that
+        nothing later in the backward overwrites): runs on the weight-gradient side streams"""
+        c, P, G = self.cfg, self.P, self.G
+        L = len(c.accent_prenet)
+        Ws = [P[f"enc.accent_prenet{n}.W"] for n in range(L)]
+        bs = [P[f"enc.accent_prenet{n}.b"] for n in range(L)]
+        ids = ctx["batch"].get("accent_type")
+        if ctx["accent_fused"]:
+            def fused():
+                ok = ops.accent_prenet_bwd(ids, P["accent_embedding"], c.accent_offset, Ws, bs, dout, self._accent_drops(r),
+                                           G["accent_embedding"], [G[f"enc.accent_prenet{n}.W"] for n in range(L)],
+                                           [G[f"enc.accent_prenet{n}.b"] for n in range(L)])
+                if not ok:
+                    raise RuntimeError("accent_prenet_bwd declined a shape accent_prenet_fwd accepted")
+            self._wgrad(fused)
+            return
+        acts = ctx["accent_acts"]
+
+        def composed():
+            _, sc = ops.rate_thresh(r)
+            dx = dout
+            for n in reversed(range(L)):
+                dp = self._e(dx.shape[0], c.accent_prenet[n])
+                ops.act_bwd(dx, acts[n + 1], dp, ACT_RELU, sc)
+                ops.linear_dw(acts[n], dp, G[f"enc.accent_prenet{n}.W"], db=G[f"enc.accent_prenet{n}.b"])
+                dx = self._e(dp.shape[0], acts[n].shape[1])
+                ops.linear_dx(dp, Ws[n], dx)
+            if ids is not None:         # (the module-contract path is given embedded inputs: no table gradient)
+                ops.embedding_bwd(ids, dx, G["accent_embedding"], offset=c.accent_offset)
+        self._wgrad(composed)
 
     def forward(self, batch, training=True):
         c, P = self.cfg, self.P
@@ -1662,7 +1746,7 @@ class Engine:
         self._mark("highway bwd")
         # dhw = gradient wrt (proj2_bn + prenet_out)
         bn_st = ctx["bn_st"]
-        p1 = ctx["pre"][-1]
+        p1 = ctx["p1"]          # what the CBHG read: the phoneme pre-net output (+ the accent columns behind it)
         CC, K = c.conv_channels, c.max_filter_width
         nb = CC * K
 
@@ -1717,6 +1801,10 @@ class Engine:
         # ---- encoder pre-net + embedding
         xin = [ctx["emb"]] + ctx["pre"]
         dx = dp1
+        if c.accent:        # dp1 = [M, Wp + Wa]: the accent branch reads its trailing columns, the phoneme branch the leading ones
+            Wp = c.enc_prenet[-1]
+            self._accent_bwd(ctx, dp1[:, Wp:], rate(c.enc_prenet_drop))
+            dx = dp1[:, :Wp]
         for n in reversed(range(len(c.enc_prenet))):
             dp = self._e(M, c.enc_prenet[n])
             _, sc = ops.rate_thresh(rate(c.enc_prenet_drop))

@@ -393,8 +393,9 @@ class DecodeSession:
 
 
 def infer(eng, source, source_length, max_steps=None, teacher=None, speaker_id=None, min_steps=10, stop_threshold=0.5,
-          check_every=8, teacher_alignments=None, use_graph=True, dropout_seed=None, encoder_outputs=None, speaker_embed=None):
+          check_every=8, teacher_alignments=None, use_graph=True, dropout_seed=None, encoder_outputs=None, speaker_embed=None, accent_type=None):
     """eng: Engine.  source int64 [B,Ti], source_length int64 [B] (device tensors or array-likes).
+    accent_type int64 [B,Ti]: required by a model with accent types (use_accent_type=True), ignored otherwise.
     teacher=None: free running, at most max_steps decoder steps, stops when sigmoid(stop) > stop_threshold for every
     sample and t > min_steps (evaluated on the device every step; the host reads the flag once per graph replay =
     `check_every` steps, one replay behind).
@@ -415,6 +416,13 @@ def infer(eng, source, source_length, max_steps=None, teacher=None, speaker_id=N
     if c.num_speakers > 0 and speaker_embed is None:
         batch["speaker_id"] = torch.as_tensor(speaker_id).to(dev).contiguous()
     B, Ti = batch["source"].shape
+    if c.accent and encoder_outputs is None:
+        if accent_type is None:
+            raise ValueError("infer: accent_type ([B, Ti] int64) is required by a model with use_accent_type=True")
+        batch["accent_type"] = torch.as_tensor(accent_type).to(dev).contiguous()
+        if batch["accent_type"].shape != batch["source"].shape:
+            raise ValueError("infer: accent_type must have the shape of source %s (got %s)"
+                             % (tuple(batch["source"].shape), tuple(batch["accent_type"].shape)))
     slen = batch["source_length"]
     nm, r = c.num_mels, c.r
     feed = nm * c.n_feed_frame
@@ -569,9 +577,10 @@ def evaluate(eng, batch, speaker_id=None):
         ops.loss_fwd_bwd(y, NO, b["mel"], b["spec_loss_mask"], y[:, NO - 1:], NO, b["done"], b["binary_loss_mask"],
                          B, Tm, nm, Td, eng.loss_l2, ls, dy, NO, dy[:, NO - 1:], NO, eng._loss_ws)
         return [float(x) for x in ls.cpu()]
-    free = infer(eng, b["source"], b["source_length"], max_steps=Td, min_steps=1 << 30, speaker_id=spk)
+    free = infer(eng, b["source"], b["source_length"], max_steps=Td, min_steps=1 << 30, speaker_id=spk,
+                 accent_type=b.get("accent_type"))
     mel_loss, done_loss, loss = score(free)
-    tf = infer(eng, b["source"], b["source_length"], teacher=b["mel"], speaker_id=spk)
+    tf = infer(eng, b["source"], b["source_length"], teacher=b["mel"], speaker_id=spk, accent_type=b.get("accent_type"))
     mel_t, done_t, loss_t = score(tf)
     return dict(mel_loss=mel_loss, done_loss=done_loss, loss=loss, mel_loss_with_teacher=mel_t,
                 done_loss_with_teacher=done_t, loss_with_teacher=loss_t, mel=free["mel"], stop=free["stop"],

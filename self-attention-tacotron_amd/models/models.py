@@ -64,15 +64,47 @@ def encoder_factory(params, is_training):
                            params.projection1_out_channels, params.projection2_out_channels, params.num_highway,
                            0, 0, tuple(params.encoder_prenet_out_units), params.encoder_prenet_drop_rate,
                            params.zoneout_factor_cell, params.zoneout_factor_output, 0.0, 0)._with_params(params)
-    if params.encoder != "SelfAttentionCBHGEncoder":
+    accent = params.encoder == "SelfAttentionCBHGEncoderWithAccentType" and params.use_accent_type
+    if params.encoder != "SelfAttentionCBHGEncoder" and not accent:
         raise UnsupportedConfiguration(f"encoder {params.encoder} is not built for MI355X (only SelfAttentionCBHGEncoder, "
-                                       "modules/module.py:374-441, and ZoneoutEncoderV1, :293-342)")
+                                       "modules/module.py:374-441, SelfAttentionCBHGEncoderWithAccentType with "
+                                       "use_accent_type=True, :444-527, and ZoneoutEncoderV1, :293-342)")
     if params.self_attention_num_hop < 1:
         raise ValueError("self_attention_num_hop must be >= 1")
+    prenet = tuple(params.encoder_prenet_out_units)
+    if accent:          # reference models/models.py:1181-1199: the phoneme pre-net takes encoder_prenet_out_units_if_accent
+        prenet = tuple(params.encoder_prenet_out_units_if_accent)
+        aprenet = tuple(params.accent_type_prenet_out_units)
+        E, A = params.embedding_dim, params.accent_type_embedding_dim
+        if params.num_accent_type < 1 or not prenet or not aprenet:
+            raise UnsupportedConfiguration(f"accent-type input needs num_accent_type >= 1 (got {params.num_accent_type}) and "
+                                           f"non-empty pre-nets (got {prenet}, {aprenet})")
+        if len(aprenet) > 2:      # two dropout streams are declared for the accent pre-net (csrc/common.h)
+            raise UnsupportedConfiguration(f"accent_type_prenet_out_units={aprenet}: at most 2 accent pre-net layers are built "
+                                           f"(got {len(aprenet)})")
+        # the reference's own build-time assertions (modules/module.py:502-505)
+        if prenet[0] != E:
+            raise UnsupportedConfiguration(f"encoder_prenet_out_units_if_accent[0]={prenet[0]} must equal embedding_dim={E} "
+                                           "(modules/module.py:502)")
+        if aprenet[0] != A:
+            raise UnsupportedConfiguration(f"accent_type_prenet_out_units[0]={aprenet[0]} must equal "
+                                           f"accent_type_embedding_dim={A} (modules/module.py:503)")
+        if params.cbhg_out_units + params.self_attention_out_units != E + A:
+            raise UnsupportedConfiguration(f"cbhg_out_units + self_attention_out_units = {params.cbhg_out_units} + "
+                                           f"{params.self_attention_out_units} must equal embedding_dim + "
+                                           f"accent_type_embedding_dim = {E} + {A} (modules/module.py:504-505)")
+        # ZoneoutCBHG inserts a Dense `adjustment_layer` when the residual sum is not cbhg_out_units // 2 wide
+        # (modules/module.py:88-89); that layer is not built, and the residual itself needs projection2's width
+        width = prenet[-1] + aprenet[-1]
+        if width != params.cbhg_out_units // 2 or width != params.projection2_out_channels:
+            raise UnsupportedConfiguration(f"pre-net widths {prenet[-1]} + {aprenet[-1]} = {width} must equal cbhg_out_units // 2 "
+                                           f"= {params.cbhg_out_units // 2} and projection2_out_channels = "
+                                           f"{params.projection2_out_channels}: the CBHG adjustment_layer "
+                                           "(modules/module.py:88-89) is not built for MI355X")
     return EncoderSpec(params.encoder, is_training, params.cbhg_out_units, params.conv_channels, params.max_filter_width,
                        params.projection1_out_channels, params.projection2_out_channels, params.num_highway,
                        params.self_attention_out_units, params.self_attention_num_heads,
-                       tuple(params.encoder_prenet_out_units), params.encoder_prenet_drop_rate,
+                       prenet, params.encoder_prenet_drop_rate,
                        params.zoneout_factor_cell, params.zoneout_factor_output, params.self_attention_drop_rate,
                        params.self_attention_num_hop)._with_params(params)
 
@@ -117,6 +149,8 @@ def validate_params(params):
     baseline = params.tacotron_model == "ExtendedTacotronV1Model"
     # the reference wires the single-source model_fn to any encoder / decoder pair; the pairs the kernels implement:
     want = ("ZoneoutEncoderV1", "ExtendedDecoder") if baseline else ("SelfAttentionCBHGEncoder", "DualSourceTransformerDecoder")
+    if not baseline and params.use_accent_type:     # models/models.py:361-364: the accent encoder takes (embedded, accent_embedded)
+        want = ("SelfAttentionCBHGEncoderWithAccentType", want[1])
     if (enc.name, dec.name) != want:
         raise UnsupportedConfiguration(f"{params.tacotron_model} is built with encoder={want[0]}, decoder={want[1]} "
                                        f"(got {enc.name}, {dec.name})")
@@ -130,7 +164,10 @@ def validate_params(params):
     if a2 is not None and a2.options.attention != "additive":
         raise UnsupportedConfiguration(f"attention2={a2.options.attention}: only additive (BahdanauAttention) is built "
                                        "for the second source")
-    for flag in ("use_accent_type", "use_external_speaker_embedding", "speaker_embedd_to_decoder",
+    if params.use_accent_type and baseline:
+        raise UnsupportedConfiguration("use_accent_type=True is not built for MI355X with ExtendedTacotronV1Model (only "
+                                       "DualSourceSelfAttentionTacotronModel + SelfAttentionCBHGEncoderWithAccentType)")
+    for flag in ("use_external_speaker_embedding", "speaker_embedd_to_decoder",
                  "speaker_embedd_to_postnet", "channel_id_to_postnet", "use_language_embedding"):
         if getattr(params, flag):
             raise UnsupportedConfiguration(f"{flag}=True is not built for MI355X")
@@ -419,16 +456,18 @@ class DualSourceSelfAttentionTacotronModel:
             b = eng.to_device_batch(_tensor_items(batch))
             spk = b.get("speaker_id")
             B = b["source"].shape[0]
+            acc = dict(accent_type=b.get("accent_type")) if eng.cfg.accent else {}
             if hp.use_forced_alignment_mode:
                 # pass 1 (models/models.py:387-390): validation decode fed with the GROUND TRUTH mel, exactly Td steps;
                 # pass 2 (:411-428): free feeding, both mechanisms return pass 1's alignments (TeacherForcing*Attention)
                 if "mel" not in b:
                     raise ValueError("use_forced_alignment_mode needs the target mel (--target-data-root)")
-                first = infer(eng, b["source"], b["source_length"], teacher=b["mel"], speaker_id=spk)
+                first = infer(eng, b["source"], b["source_length"], teacher=b["mel"], speaker_id=spk, **acc)
                 out = infer(eng, b["source"], b["source_length"], max_steps=first["steps"], speaker_id=spk,
-                            min_steps=1 << 30, teacher_alignments=(first["alignment1"], first["alignment2"] if eng.cfg.dual else None))
+                            min_steps=1 << 30, teacher_alignments=(first["alignment1"], first["alignment2"] if eng.cfg.dual else None),
+                            **acc)
             else:
-                out = infer(eng, b["source"], b["source_length"], max_steps=hp.max_iters, speaker_id=spk)
+                out = infer(eng, b["source"], b["source_length"], max_steps=hp.max_iters, speaker_id=spk, **acc)
             mel_post = postnet_infer(eng, out["mel"]) if eng.cfg.use_postnet_v2 else None
             enc_al = out.get("enc_alignment")
             for i in range(B):
@@ -445,6 +484,8 @@ class DualSourceSelfAttentionTacotronModel:
                     for h in range(enc_al.shape[1]):
                         p["alignment%d" % (5 + h)] = enc_al[i, h].cpu().numpy().T
                 p["source"] = np.asarray(batch["source"][i])
+                if eng.cfg.accent:                                              # models/models.py:585
+                    p["accent_type"] = np.asarray(batch["accent_type"][i])
                 p["text"] = batch["text"][i] if "text" in batch else ""
                 yield p
 

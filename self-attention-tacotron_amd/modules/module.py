@@ -64,13 +64,21 @@ class EncoderModule(_Bound):
     def __call__(self, inputs, input_lengths=None):
         eng = self.engine
         c = eng.cfg
+        xa = None
+        if c.accent:      # SelfAttentionCBHGEncoderWithAccentType.call (module.py:507-508): inputs = (embedded, accent_embedded)
+            if not isinstance(inputs, (tuple, list)) or len(inputs) != 2:
+                raise ValueError("an accent-type encoder takes inputs = (embedded [batch, time, %d], accent_embedded [batch, time, %d])"
+                                 % (c.embedding_dim, c.accent_dim))
+            inputs, xa = inputs[0], _dev(eng, inputs[1], torch.float32)
         x = _dev(eng, inputs, torch.float32)
         if x.dim() != 3 or x.shape[2] != c.embedding_dim:
             raise ValueError("encoder inputs must be [batch, time, %d] embedded symbols (got %s)" % (c.embedding_dim, tuple(x.shape)))
+        if xa is not None and (xa.dim() != 3 or xa.shape[:2] != x.shape[:2] or xa.shape[2] != c.accent_dim):
+            raise ValueError("accent_embedded must be [%d, %d, %d] (got %s)" % (x.shape[0], x.shape[1], c.accent_dim, tuple(xa.shape)))
         B, Ti = x.shape[:2]
         if input_lengths is None:
             input_lengths = np.full(B, Ti, np.int64)
-        batch = {"embedded": x, "source_length": _dev(eng, input_lengths, torch.int64)}
+        batch = {"embedded": x if xa is None else (x, xa), "source_length": _dev(eng, input_lengths, torch.int64)}
         ctx = {"training": bool(self.is_training), "batch": batch}
         lstm_out, sa_out = eng._encode(batch, bool(self.is_training), ctx)
         self.__dict__["last_ctx"] = ctx

@@ -344,6 +344,44 @@ def embedding_bwd(ids, dout, dtable, offset=0, atomic=True):
                                                       dtable.shape[0], _s()))
 
 
+def _accent_args(ids, table, offset, Ws, bs):
+    l = len(Ws)
+    W1, b1 = (Ws[1], bs[1]) if l == 2 else (None, None)
+    return (_p(ids), _p(table), table.shape[0], offset, table.shape[1], l, _p(Ws[0]), _p(bs[0]), Ws[0].shape[1], _p(W1), _p(b1),
+            W1.shape[1] if l == 2 else 0)
+
+
+def accent_prenet_fwd(ids, table, offset, Ws, bs, out, drops):
+    """out[:, :] = PreNet stack (Ws, bs: fp32 [in, out] / [out] per layer) over table[ids - offset] in ONE launch; `out` is a
+    row-major view (normally the trailing columns of the shared pre-net buffer).  drops: one Drop per layer (same rate).
+    False (nothing launched) when the shape is beyond the kernel's cap (> 2 layers, widths > 64, LDS): compose it from
+    embedding_fwd + linear then."""
+    if len(Ws) > 2:
+        return False
+    d0, d1 = drops[0], drops[-1]
+    rc = _lib.lib().satt_accent_prenet_fwd(*_accent_args(ids, table, offset, Ws, bs), _p(out), _ld(out), ids.numel(), d0.thresh,
+                                           d0.scale, d0.stream, d1.stream, _p(d0.seed), _s())
+    if rc == -2:
+        return False
+    _lib.check(rc, "accent_prenet_fwd")
+    return True
+
+
+def accent_prenet_bwd(ids, table, offset, Ws, bs, dout, drops, dtable, dWs, dbs):
+    """backward of accent_prenet_fwd in ONE launch: dWs / dbs / dtable += (float atomics).  False when beyond the cap."""
+    if len(Ws) > 2:
+        return False
+    d0, d1 = drops[0], drops[-1]
+    two = len(Ws) == 2
+    rc = _lib.lib().satt_accent_prenet_bwd(*_accent_args(ids, table, offset, Ws, bs), _p(dout), _ld(dout), ids.numel(), d0.thresh,
+                                           d0.scale, d0.stream, d1.stream, _p(d0.seed), _p(dtable), _p(dWs[0]), _p(dbs[0]),
+                                           _p(dWs[1]) if two else None, _p(dbs[1]) if two else None, _s())
+    if rc == -2:
+        return False
+    _lib.check(rc, "accent_prenet_bwd")
+    return True
+
+
 def act_bwd(dy, y, dx, act, scale=1.0):
     rows, cols = y.shape
     _lib.check(_lib.lib().satt_act_bwd(_p(dy), _ld(dy), _p(y), _ld(y), _p(dx), _ld(dx), rows, cols, act, scale, _s()))

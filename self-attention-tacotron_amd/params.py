@@ -15,6 +15,10 @@ class ModelConfig:
     def __init__(self, **kw):
         self.num_symbols = 256; self.embedding_dim = 256
         self.enc_prenet = (256, 128); self.enc_prenet_drop = 0.5
+        # accent-type input of SelfAttentionCBHGEncoderWithAccentType (reference modules/module.py:444-527, models/models.py
+        # :285-288,361-364): a second embedding (num_accent_type rows, looked up by id - accent_offset) and a second PreNet stack
+        # (same drop rate) whose output is concatenated behind the phoneme pre-net's in front of the CBHG.  0 types = off.
+        self.num_accent_type = 0; self.accent_dim = 32; self.accent_offset = 0; self.accent_prenet = (32, 16)
         self.conv_channels = 128; self.max_filter_width = 16
         self.proj1 = 128; self.proj2 = 128; self.num_highway = 4; self.cbhg_out_units = 256
         self.sa_units = 32; self.sa_heads = 2; self.sa_drop = 0.05
@@ -49,10 +53,21 @@ class ModelConfig:
             if not hasattr(self, k):
                 raise KeyError(k)
             setattr(self, k, v)
+        if self.accent and not 1 <= len(self.accent_prenet) <= 2:
+            raise ValueError("accent_prenet: 1 or 2 layers (two dropout streams are declared, csrc/common.h)")
         if self.sa_num_hop < 1 or self.dec_sa_num_hop < 1:
             raise ValueError("sa_num_hop / dec_sa_num_hop must be >= 1")
         if (self.sa_units > 0) != (self.att2_units > 0):
             raise ValueError("sa_units and att2_units are both zero (single attention source) or both positive")
+
+    @property
+    def accent(self):
+        return self.num_accent_type > 0
+
+    @property
+    def prenet_width(self):
+        """channels the CBHG reads: the phoneme pre-net's output (+ the accent pre-net's, concatenated behind it)"""
+        return self.enc_prenet[-1] + (self.accent_prenet[-1] if self.accent else 0)
 
     @property
     def ctx_dim(self):
@@ -86,7 +101,12 @@ class ModelConfig:
             # the dual-source model_fn never reads use_l2_regularization (models/models.py:278-515): no effect there
             l2_weight=float(hp.l2_regularization_weight) if (baseline and hp.use_l2_regularization) else 0.0,
             num_symbols=hp.num_symbols, embedding_dim=hp.embedding_dim,
-            enc_prenet=tuple(hp.encoder_prenet_out_units), enc_prenet_drop=hp.encoder_prenet_drop_rate,
+            # encoder_factory hands SelfAttentionCBHGEncoderWithAccentType encoder_prenet_out_units_if_accent (models/models.py:1195)
+            enc_prenet=tuple(hp.encoder_prenet_out_units_if_accent if hp.use_accent_type else hp.encoder_prenet_out_units),
+            enc_prenet_drop=hp.encoder_prenet_drop_rate,
+            **(dict(num_accent_type=int(hp.num_accent_type), accent_dim=int(hp.accent_type_embedding_dim),
+                    accent_offset=int(hp.accent_type_offset), accent_prenet=tuple(hp.accent_type_prenet_out_units))
+               if hp.use_accent_type else {}),
             conv_channels=hp.conv_channels, max_filter_width=hp.max_filter_width,
             proj1=hp.projection1_out_channels, proj2=hp.projection2_out_channels, num_highway=hp.num_highway,
             cbhg_out_units=hp.cbhg_out_units,
@@ -126,7 +146,13 @@ def param_shapes(c):
     for n, o in enumerate(c.enc_prenet):
         L += [(f"enc.prenet{n}.W", (i, o)), (f"enc.prenet{n}.b", (o,))]
         i = o
-    cin = c.enc_prenet[-1]
+    if c.accent:        # inside the encoder range of the flat buffer: same DP bucket, clip and Adam as the phoneme pre-net
+        L.append(("accent_embedding", (c.num_accent_type, c.accent_dim)))
+        i = c.accent_dim
+        for n, o in enumerate(c.accent_prenet):
+            L += [(f"enc.accent_prenet{n}.W", (i, o)), (f"enc.accent_prenet{n}.b", (o,))]
+            i = o
+    cin = c.prenet_width
     for k in range(1, c.max_filter_width + 1):
         L.append((f"enc.bank{k}.W", (k, cin, c.conv_channels)))
     nb = c.max_filter_width * c.conv_channels
@@ -194,7 +220,7 @@ def l2_regularized(c):
     out = []
     for name, _ in param_shapes(c):
         last = name.rsplit(".", 1)[-1]
-        if name in ("embedding", "speaker_embedding") or last in ("b", "bs", "b2", "bF", "ba", "gamma", "beta"):
+        if name in ("embedding", "speaker_embedding", "accent_embedding") or last in ("b", "bs", "b2", "bF", "ba", "gamma", "beta"):
             continue
         if "lstm" in name or name.startswith("dec.out."):
             continue
@@ -230,7 +256,7 @@ def init_params(c, seed=0):
         elif last == "v":
             lim = math.sqrt(6.0 / (shp[0] + 1))
             a = g.uniform(-lim, lim, shp)
-        elif name in ("embedding", "speaker_embedding"):
+        elif name in ("embedding", "speaker_embedding", "accent_embedding"):
             a = g.normal(0, 0.5, shp)
         else:
             fan_in, fan_out = (shp[0] * shp[1], shp[0] * shp[2]) if len(shp) == 3 else (shp[0], shp[1])

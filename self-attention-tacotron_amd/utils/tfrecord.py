@@ -220,6 +220,22 @@ def make_example(features):
     return _ld(1, entries)
 
 
+def make_source_example(id_, key, source, text="", accent_type=None, **extra):
+    """payload of a `<key>.source.tfrecord` record (reference datasets/ljspeech/dataset.py:52-60 fields).  accent_type (optional):
+    one accentual-type id per symbol, stored as the bytes feature `accent_type`, raw little-endian int64, source_length entries -
+    this project's definition of the field."""
+    src = np.ascontiguousarray(source, dtype="<i8")
+    f = {"id": int(id_), "key": key if isinstance(key, bytes) else key.encode("utf-8"), "source": src.tobytes(),
+         "source_length": int(src.shape[0]), "text": text if isinstance(text, bytes) else text.encode("utf-8")}
+    if accent_type is not None:
+        acc = np.ascontiguousarray(accent_type, dtype="<i8")
+        if acc.shape != src.shape:
+            raise ValueError("accent_type needs one id per source symbol (%d), got %s" % (src.shape[0], acc.shape))
+        f["accent_type"] = acc.tobytes()
+    f.update(extra)
+    return make_example(f)
+
+
 def write_prediction_result(id_, key, alignments, mel, ground_truth_mel, text, source, accent_type, filename):
     """One prediction as a single-record TFRecord file with the reference's feature names and encodings
     (reference utils/tfrecord.py:135-152): arrays as raw little-endian bytes, alignments as a bytes list."""
@@ -266,4 +282,6 @@ def parse_prediction_result(payload):
                ground_truth_mel=np.frombuffer(f["ground_truth_mel"][0], "<f4").reshape(int(f["ground_truth_mel_length"][0]), w),
                source=np.frombuffer(f["source"][0], "<i8"),
                alignment=[np.frombuffer(a, "<f4").reshape(sl, -1) for a in f["alignment"]] if n_align else [])
+    if f.get("accent_type"):
+        out["accent_type"] = np.frombuffer(f["accent_type"][0], "<i8")
     return out
