@@ -145,6 +145,20 @@ int satt_accent_prenet_bwd(const int64_t* ids, const float* table, int ntypes, i
                            uint32_t stream0, uint32_t stream1, const uint32_t* seed, float* dtable, float* dW0, float* db0,
                            float* dW1, float* db1, void* stream);
 
+/* Speaker term of the multi-speaker decoder pre-net WITH the resize layer (speaker_embedding_projection_out_dim > -1; reference
+ * models/models.py:307-312, modules/multi_speaker_modules.py:27-32), forward, in one launch:
+ *   semb = table[id - offset] [B, E];  rs = relu(semb Wr + br) [B, R];  sproj = softsign(rs Ws + bs) [B, P0]  - all three written
+ *   (the backward, a chain of satt_act_bwd / satt_gemm / satt_embedding_bwd, reads them).
+ * mode 0: ids[B] (int64; ids outside the nspk-row table are clamped - memory safety only);  mode 1: emb_in [B, E] is the embedding
+ * itself (table / ids unused);  mode 2: scalar_id for every row (speaker_for_synthesis; ids unused).
+ * Wr [E, R], br [R], Ws [R, P0], bs [P0], all contiguous fp32.  One workgroup, activations in LDS, fp32 throughout.
+ * Cap (satt_speaker_cond_supported == 1): B <= 256, E <= 256, R <= 256, P0 <= 512 and an LDS footprint 4 * B * (E + R) bytes
+ * <= 64 KB; beyond it SATT_E_UNSUPPORTED and nothing is launched (compose the term from satt_embedding_fwd + satt_gemm). */
+int satt_speaker_cond_supported(int B, int E, int R, int P0);
+int satt_speaker_cond_fwd(int mode, const int64_t* ids, int64_t scalar_id, const float* emb_in, int B, const float* table,
+                          int nspk, int offset, int E, const float* Wr, const float* br, int R, const float* Ws,
+                          const float* bs, int P0, float* semb, float* rs, float* sproj, void* stream);
+
 /* dx = dy * act'(y) (* scale where y != 0 for dropout-after-relu); y is the POST-activation(-dropout) output */
 int satt_act_bwd(const float* dy, int64_t lddy, const float* y, int64_t ldy, float* dx, int64_t lddx,
                  int rows, int cols, int act, float scale, void* stream);

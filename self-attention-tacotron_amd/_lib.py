@@ -144,6 +144,8 @@ SIGNATURES = {
     "satt_accent_prenet_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, c_i64, _I, c_u32, _F, c_u32, c_u32, _P, _P]),
     "satt_accent_prenet_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, c_i64, _I, c_u32, _F, c_u32, c_u32, _P,
                                     _P, _P, _P, _P, _P, _P]),
+    "satt_speaker_cond_supported": (_I, [_I, _I, _I, _I]),
+    "satt_speaker_cond_fwd": (_I, [_I, _P, c_i64, _P, _I, _P, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P]),
     "satt_act_bwd": (_I, [_P, c_i64, _P, c_i64, _P, c_i64, _I, _I, _I, _F, _P]),
     "satt_act_bwd_res": (_I, [_P, c_i64, _P, c_i64, _P, c_i64, _P, c_i64, _I, _I, _I, _F, _P]),
     "satt_bn_ws_floats": (c_i64, [_I, _I]),

@@ -859,6 +859,79 @@ class Engine:
                 ops.embedding_bwd(ids, dx, G["accent_embedding"], offset=c.accent_offset)
         self._wgrad(composed)
 
+    # False: the forward of the speaker term with the resize layer is composed from embedding_fwd + linear too (the cap's fallback).
+    # Only the FORWARD has a kernel of its own: a one-workgroup backward kernel measured 75 us per call against 49 us for the chain
+    # of generic ops below (profiles/speaker_cond_bench_and_kernel_times.txt) and was not kept
+    fused_speaker = True
+
+    def speaker_source(self, batch, B):
+        """who speaks in every row: the embedded vectors of the decoder call contract (batch["speaker_embed"], float [B, E]; they
+        come from below the model function and are taken as given), else the ONE id of speaker_for_synthesis (an int; reference
+        models/models.py:334-336 - it replaces batch["speaker_id"] in every mode), else batch["speaker_id"] (int64 [B])"""
+        c = self.cfg
+        if "speaker_embed" in batch:
+            return batch["speaker_embed"].to(torch.float32).reshape(B, c.speaker_dim).contiguous()
+        if c.speaker_for_synthesis > -1:
+            return int(c.speaker_for_synthesis)
+        if batch.get("speaker_id") is None:
+            raise KeyError("speaker_id: a model with a speaker embedding needs batch['speaker_id'] (int64 [B]) unless "
+                           "speaker_for_synthesis is set")
+        return batch["speaker_id"]
+
+    def speaker_term(self, src, spk, shadows=True):
+        """spk["sproj"] = softsign(f(speaker) Ws + bs), the time-constant term of MultiSpeakerPreNet, for a model with the resize
+        layer (f = relu(emb Wr + br), reference models/models.py:307-312; the reference composes it behind the embedding, so a
+        given embedding is resized too) and / or speaker_for_synthesis.  With the resize layer the forward is ONE launch
+        (csrc/speaker_cond.hip) when the shape is inside the kernel's cap; otherwise the chain of generic ops.  The backward
+        (_speaker_term_bwd) is always the chain.
+        shadows=False: the GEMMs of the chain read the fp32 masters (inference.infer)."""
+        c, P = self.cfg, self.P
+        B = spk["semb"].shape[0]
+        W = self.W if shadows else (lambda n: P[n])
+        spk["src"], spk["fused"] = src, False
+        if c.speaker_resize and self.fused_speaker and \
+                ops.speaker_cond_fwd(src, P["speaker_embedding"], c.speaker_offset, P["speaker_resize.W"], P["speaker_resize.b"],
+                                     P["dec.prenet0.Ws"], P["dec.prenet0.bs"], spk["semb"], spk["rs"], spk["sproj"]):
+            spk["fused"] = True
+            return
+        ids = self._speaker_ids(src, B)
+        if ids is None:
+            spk["semb"].copy_(src)
+        else:
+            ops.embedding_fwd(ids, P["speaker_embedding"], spk["semb"], offset=c.speaker_offset)
+        x = spk["semb"]
+        if c.speaker_resize:
+            ops.linear(x, W("speaker_resize.W"), P["speaker_resize.b"], spk["rs"], act=ACT_RELU)
+            x = spk["rs"]
+        ops.linear(x, W("dec.prenet0.Ws"), P["dec.prenet0.bs"], spk["sproj"], act=ACT_SOFTSIGN)
+
+    def _speaker_ids(self, src, B):
+        """int64 [B] ids of a speaker source for the generic ops (None for embedded vectors).  The scalar of speaker_for_synthesis
+        broadcasts over the batch: the same numbers as this id in every row"""
+        if isinstance(src, int):
+            return torch.full((B,), src, dtype=torch.int64, device=self.dev)
+        return None if src.is_floating_point() else src
+
+    def _speaker_term_bwd(self, spk, ds):
+        """parameter gradients of speaker_term() from ds = d sproj [B, P0]: generic ops (7 launches with the resize layer)"""
+        c, G = self.cfg, self.G
+        B = ds.shape[0]
+        dsp = self._e(B, c.dec_prenet[0])
+        ops.act_bwd(ds, spk["sproj"], dsp, ACT_SOFTSIGN)
+        x = spk["rs"] if c.speaker_resize else spk["semb"]
+        ops.linear_dw(x, dsp, G["dec.prenet0.Ws"], db=G["dec.prenet0.bs"])
+        dx = self._e(B, c.speaker_feat)
+        ops.linear_dx(dsp, self.W("dec.prenet0.Ws"), dx)
+        if c.speaker_resize:
+            drs = self._e(B, c.speaker_proj_dim)
+            ops.act_bwd(dx, spk["rs"], drs, ACT_RELU)
+            ops.linear_dw(spk["semb"], drs, G["speaker_resize.W"], db=G["speaker_resize.b"])
+            dx = self._e(B, c.speaker_dim)
+            ops.linear_dx(drs, self.W("speaker_resize.W"), dx)
+        ids = self._speaker_ids(spk["src"], B)
+        if ids is not None:
+            ops.embedding_bwd(ids, dx, G["speaker_embedding"], offset=c.speaker_offset)
+
     def forward(self, batch, training=True):
         c, P = self.cfg, self.P
         ctx = {"training": training, "batch": batch}
@@ -893,6 +966,8 @@ class Engine:
         if c.num_speakers > 0:
             spk = dict(semb=self._e(B, c.speaker_dim), sproj=self._e(B, c.dec_prenet[0]),
                        r0=self._e(Md, c.dec_prenet[0]), d0=self._e(Md, c.dec_prenet[0]))
+            if c.speaker_resize:
+                spk["rs"] = self._e(B, c.speaker_proj_dim)
 
         def teacher_branch():
             dec_in3[:, :1].zero_()                                              # go frame
@@ -900,11 +975,14 @@ class Engine:
             if spk is not None:
                 # MultiSpeakerPreNet (reference modules/multi_speaker_modules.py:27-32; models/models.py:298-301,
                 # 338-339): dense0 = relu(x W0 + b0) + softsign(emb[speaker] Ws + bs); dense = relu(dense0 W2 + b2)
-                if "speaker_embed" in batch:      # the embedded speaker vectors themselves (decoder call contract: speaker_embed=)
-                    spk["semb"].copy_(batch["speaker_embed"].reshape(B, c.speaker_dim))
+                if c.speaker_resize or c.speaker_for_synthesis > -1:
+                    self.speaker_term(self.speaker_source(batch, B), spk)
                 else:
-                    ops.embedding_fwd(batch["speaker_id"], P["speaker_embedding"], spk["semb"], offset=c.speaker_offset)
-                ops.linear(spk["semb"], self.W("dec.prenet0.Ws"), P["dec.prenet0.bs"], spk["sproj"], act=ACT_SOFTSIGN)
+                    if "speaker_embed" in batch:      # the embedded speaker vectors themselves (decoder call contract: speaker_embed=)
+                        spk["semb"].copy_(batch["speaker_embed"].reshape(B, c.speaker_dim))
+                    else:
+                        ops.embedding_fwd(batch["speaker_id"], P["speaker_embedding"], spk["semb"], offset=c.speaker_offset)
+                    ops.linear(spk["semb"], self.W("dec.prenet0.Ws"), P["dec.prenet0.bs"], spk["sproj"], act=ACT_SOFTSIGN)
                 ops.linear(dec_in, self.W("dec.prenet0.W"), P["dec.prenet0.b"], spk["r0"], act=ACT_RELU)
                 ops.axpby(spk["r0"], spk["d0"], 1.0, 0.0)
                 ops.bcast_add(spk["sproj"], spk["d0"], B, Td, c.dec_prenet[0])
@@ -1680,12 +1758,15 @@ class Engine:
                     ops.linear_dx(dp, self.W("dec.prenet0.W2"), dd0)
                     ds = self._e(B, c.dec_prenet[0])
                     ops.segment_colsum(dd0, ds, B, Td, c.dec_prenet[0])
-                    dsp = self._e(B, c.dec_prenet[0])
-                    ops.act_bwd(ds, spk["sproj"], dsp, ACT_SOFTSIGN)
-                    self._wgrad(lambda: (ops.linear_dw(spk["semb"], dsp, G["dec.prenet0.Ws"], db=G["dec.prenet0.bs"])))
-                    dsemb = self._e(B, c.speaker_dim)
-                    ops.linear_dx(dsp, self.W("dec.prenet0.Ws"), dsemb)
-                    ops.embedding_bwd(ctx["batch"]["speaker_id"], dsemb, G["speaker_embedding"], offset=c.speaker_offset)
+                    if "src" in spk:         # resize layer and / or speaker_for_synthesis: speaker_term() ran in the forward pass
+                        self._speaker_term_bwd(spk, ds)
+                    else:
+                        dsp = self._e(B, c.dec_prenet[0])
+                        ops.act_bwd(ds, spk["sproj"], dsp, ACT_SOFTSIGN)
+                        self._wgrad(lambda: (ops.linear_dw(spk["semb"], dsp, G["dec.prenet0.Ws"], db=G["dec.prenet0.bs"])))
+                        dsemb = self._e(B, c.speaker_dim)
+                        ops.linear_dx(dsp, self.W("dec.prenet0.Ws"), dsemb)
+                        ops.embedding_bwd(ctx["batch"]["speaker_id"], dsemb, G["speaker_embedding"], offset=c.speaker_offset)
                     dr0 = self._e(Md, c.dec_prenet[0])
                     ops.act_bwd(dd0, spk["r0"], dr0, ACT_RELU)
                     self._wgrad(lambda: (ops.linear_dw(ctx["dec_in"], dr0, G["dec.prenet0.W"], db=G["dec.prenet0.b"])))

@@ -396,6 +396,10 @@ def infer(eng, source, source_length, max_steps=None, teacher=None, speaker_id=N
           check_every=8, teacher_alignments=None, use_graph=True, dropout_seed=None, encoder_outputs=None, speaker_embed=None, accent_type=None):
     """eng: Engine.  source int64 [B,Ti], source_length int64 [B] (device tensors or array-likes).
     accent_type int64 [B,Ti]: required by a model with accent types (use_accent_type=True), ignored otherwise.
+    speaker_id int64 [B] (multi-speaker model).  With the hparam speaker_for_synthesis > -1 EVERY row is synthesised with that
+    speaker and speaker_id is overridden (it may be None): the reference's model function replaces features.speaker_id the same
+    way in every mode (models/models.py:334-339).  speaker_embed float [B, speaker_embedding_dim] (decoder call contract) is
+    taken as given; with speaker_embedding_projection_out_dim > -1 it goes through the resize layer like a looked-up embedding.
     teacher=None: free running, at most max_steps decoder steps, stops when sigmoid(stop) > stop_threshold for every
     sample and t > min_steps (evaluated on the device every step; the host reads the flag once per graph replay =
     `check_every` steps, one replay behind).
@@ -413,7 +417,7 @@ def infer(eng, source, source_length, max_steps=None, teacher=None, speaker_id=N
     f32 = dict(dtype=torch.float32, device=dev)
     batch = {"source": torch.as_tensor(source).to(dev).contiguous(),
              "source_length": torch.as_tensor(source_length).to(dev).contiguous()}
-    if c.num_speakers > 0 and speaker_embed is None:
+    if c.num_speakers > 0 and speaker_embed is None and (speaker_id is not None or c.speaker_for_synthesis < 0):
         batch["speaker_id"] = torch.as_tensor(speaker_id).to(dev).contiguous()
     B, Ti = batch["source"].shape
     if c.accent and encoder_outputs is None:
@@ -468,11 +472,19 @@ def infer(eng, source, source_length, max_steps=None, teacher=None, speaker_id=N
         ops.linear(ses.values2, P["dec.att2.Wm"], None, ses.keys2)
     if c.num_speakers > 0:      # multi-speaker pre-net term (constant over time): softsign(emb[speaker] Ws + bs)
         semb = torch.empty(B, c.speaker_dim, **f32)
-        if speaker_embed is not None:
-            semb.copy_(torch.as_tensor(speaker_embed, **f32).reshape(B, c.speaker_dim))
+        if c.speaker_resize or c.speaker_for_synthesis > -1:      # resize layer / one speaker for every row: Engine.speaker_term
+            if speaker_embed is not None:
+                batch["speaker_embed"] = torch.as_tensor(speaker_embed, **f32)
+            spk = dict(semb=semb, sproj=ses.sproj)
+            if c.speaker_resize:
+                spk["rs"] = torch.empty(B, c.speaker_proj_dim, **f32)
+            eng.speaker_term(eng.speaker_source(batch, B), spk, shadows=False)
         else:
-            ops.embedding_fwd(batch["speaker_id"], P["speaker_embedding"], semb, offset=c.speaker_offset)
-        ops.linear(semb, P["dec.prenet0.Ws"], P["dec.prenet0.bs"], ses.sproj, act=ACT_SOFTSIGN)
+            if speaker_embed is not None:
+                semb.copy_(torch.as_tensor(speaker_embed, **f32).reshape(B, c.speaker_dim))
+            else:
+                ops.embedding_fwd(batch["speaker_id"], P["speaker_embedding"], semb, offset=c.speaker_offset)
+            ops.linear(semb, P["dec.prenet0.Ws"], P["dec.prenet0.bs"], ses.sproj, act=ACT_SOFTSIGN)
     if teacher is not None:
         tg = teacher.view(B, Td, nm * r)
         ses.tin[:, 0].zero_()
@@ -561,7 +573,8 @@ def evaluate(eng, batch, speaker_id=None):
     """EVAL double pass of the reference's model_fn (models/models.py:517-564): (1) the free-running decode over
     exactly Td = Tm/r steps (ValidationHelper with teacher_forcing=False: own outputs fed back, no stop rule) and
     (2) the teacher-fed validation pass, each scored with the training losses (spec_loss + binary_loss with the
-    batch's masks).  Returns the scalars under the reference's metric names plus the free run's outputs."""
+    batch's masks).  Returns the scalars under the reference's metric names plus the free run's outputs.
+    speaker_id replaces the batch's own; with the hparam speaker_for_synthesis > -1 both are overridden by that speaker (see infer)."""
     b = eng.to_device_batch({k: v for k, v in batch.items() if hasattr(v, "dtype") or isinstance(v, torch.Tensor)})
     c = eng.cfg
     B, Tm = b["mel"].shape[0], b["mel"].shape[1]

@@ -173,6 +173,24 @@ def validate_params(params):
             raise UnsupportedConfiguration(f"{flag}=True is not built for MI355X")
     if params.use_speaker_embedding and not params.speaker_embedd_to_prenet:
         raise UnsupportedConfiguration("use_speaker_embedding needs speaker_embedd_to_prenet=True (MultiSpeakerPreNet)")
+    if not baseline:
+        # speaker_embedding_projection_out_dim / speaker_for_synthesis (models/models.py:307-312, :333-339) are read by the dual-source
+        # model_fn only (ExtendedTacotronV1Model, :39-52, never looks at them).  Without a speaker embedding the reference dies
+        # with a NameError on `speaker_embedding`; a width of 0 or an id outside the table trains / gathers nothing sensible.
+        rdim, sfs = int(params.speaker_embedding_projection_out_dim), int(params.speaker_for_synthesis)
+        if rdim > -1 and not params.use_speaker_embedding:
+            raise ValueError(f"speaker_embedding_projection_out_dim={rdim} needs use_speaker_embedding=True (there is no "
+                             "speaker embedding to resize)")
+        if rdim == 0:
+            raise ValueError("speaker_embedding_projection_out_dim=0: the resize layer needs at least one unit (-1 = off)")
+        if sfs > -1 and not params.use_speaker_embedding:
+            raise ValueError(f"speaker_for_synthesis={sfs} needs use_speaker_embedding=True (there is no speaker embedding "
+                             "to look it up in)")
+        if sfs > -1:
+            lo, hi = int(params.speaker_embedding_offset), int(params.speaker_embedding_offset) + int(params.num_speakers)
+            if not lo <= sfs < hi:
+                raise ValueError(f"speaker_for_synthesis={sfs} is outside the speaker table [{lo}, {hi}) "
+                                 "(speaker_embedding_offset, num_speakers)")
     if params.spec_loss_type not in ("l1", "mse"):
         raise ValueError(f"Unknown loss type: {params.spec_loss_type}")
     return enc, dec, a1, a2

@@ -187,6 +187,12 @@ def all_targets(engine):
     return out
 
 
+# parameters that are never paired automatically: the resize layer behind the speaker embedding is an anonymous tf.layers.Dense of
+# the model function (reference models/models.py:311; TF names it dense, dense_1, ... by creation order), so neither a name
+# pattern nor shape uniqueness identifies it - `suggest` lists both with a "?/..." placeholder for the user's variable map
+MAP_ONLY = ("speaker_resize.W", "speaker_resize.b")
+
+
 def resolve_default_map(engine, reader):
     """A concrete variable map for THIS checkpoint without a user-written one.  (1) every pattern of default_var_patterns
     that selects exactly one not-yet-used checkpoint variable of its target's shape (singleton axes ignored) is taken; (2) of
@@ -213,7 +219,7 @@ def resolve_default_map(engine, reader):
         # shape uniqueness alone can bind a variable of a layer this build does not model: the LEAF of the TF name must also
         # agree with the kind of the target (kernel / bias / gamma / beta / moving statistics / embedding table), and every
         # such pairing is logged with both names so a wrong initialisation cannot pass silently
-        if len(hits) == 1 and shapes_t.count(want) == 1 and _leaf_agrees(hits[0], t, want):
+        if t.get("param") not in MAP_ONLY and len(hits) == 1 and shapes_t.count(want) == 1 and _leaf_agrees(hits[0], t, want):
             vmap[hits[0]] = t; used.add(hits[0])
             logging.warning("warm start: %s <- TF variable %r paired by SHAPE %s only (no name pattern matched); check it, or "
                             "pin it in a variable map (tools/tf_checkpoint.py suggest)", _target_name(t), hits[0], list(want))

@@ -13,6 +13,10 @@ over the hand-written engine:
                                memory2_sequence_length=lengths, target_sequence_length=target_lengths, target=mel_targets,
                                teacher_alignments=(None, None), apply_dropout_on_inference=False)   # module.py:1493-1498
 
+speaker_embed of a multi-speaker decoder: float [B, speaker_embedding_dim] (the embedded vectors) or int64 [B] (ids).  With
+speaker_embedding_projection_out_dim > -1 the model's resize layer (Dense, relu: models/models.py:307-312) is applied behind either
+form, because the reference composes it behind the embedding.  speaker_for_synthesis replaces ids, not embedded vectors.
+
 A module computes with the parameters of the Engine it is bound to: `module.bind(engine)` shares a model's engine (what
 tacotron_model_factory's models do), otherwise the first call builds one from the hparams the factory was given (fresh random
 parameters - the analogue of a layer creating its variables).  These calls are FORWARD passes (TF would differentiate the graph

@@ -382,6 +382,40 @@ def accent_prenet_bwd(ids, table, offset, Ws, bs, dout, drops, dtable, dWs, dbs)
     return True
 
 
+SPK_IDS, SPK_EMBED, SPK_SCALAR = 0, 1, 2      # csrc/speaker_cond.hip: where the speaker of a row comes from
+
+
+def speaker_cond_supported(B, E, R, P0):
+    """True when the one-launch speaker kernel takes the shape (caps and LDS footprint: include/satt_hip.h)"""
+    return bool(_lib.lib().satt_speaker_cond_supported(B, E, R, P0))
+
+
+def _speaker_src(speaker, B):
+    """(mode, ids pointer, scalar id, embedding pointer) of `speaker`: an int (one id for every row), an int64 tensor [B] or
+    a float32 tensor [B, E]"""
+    if isinstance(speaker, int):
+        return SPK_SCALAR, None, speaker, None
+    if speaker.dtype == torch.int64:
+        assert speaker.numel() == B and speaker.is_contiguous()
+        return SPK_IDS, _p(speaker), 0, None
+    assert speaker.dtype == torch.float32 and speaker.shape[0] == B and speaker.is_contiguous()
+    return SPK_EMBED, None, 0, _p(speaker)
+
+
+def speaker_cond_fwd(speaker, table, offset, Wr, br, Ws, bs, semb, rs, sproj):
+    """semb = table[speaker - offset] (or `speaker` itself when it is a float [B, E] tensor, or row `speaker` for every sample when it
+    is an int); rs = relu(semb Wr + br); sproj = softsign(rs Ws + bs): ONE launch.  False (nothing launched) beyond the cap."""
+    B = semb.shape[0]
+    mode, ids, sid, emb = _speaker_src(speaker, B)
+    rc = _lib.lib().satt_speaker_cond_fwd(mode, ids, sid, emb, B, _p(table), 0 if table is None else table.shape[0], offset,
+                                          Wr.shape[0], _p(Wr), _p(br), Wr.shape[1], _p(Ws), _p(bs), Ws.shape[1], _p(semb), _p(rs),
+                                          _p(sproj), _s())
+    if rc == -2:
+        return False
+    _lib.check(rc, "speaker_cond_fwd")
+    return True
+
+
 def act_bwd(dy, y, dx, act, scale=1.0):
     rows, cols = y.shape
     _lib.check(_lib.lib().satt_act_bwd(_p(dy), _ld(dy), _p(y), _ld(y), _p(dx), _ld(dx), rows, cols, act, scale, _s()))

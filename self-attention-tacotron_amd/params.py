@@ -46,6 +46,10 @@ class ModelConfig:
         self.zc = 0.1; self.zh = 0.1
         self.bn_eps = 1e-3; self.bn_momentum = 0.99
         self.num_speakers = 0; self.speaker_dim = 16; self.speaker_offset = 0
+        # speaker_embedding_projection_out_dim (reference models/models.py:307-312): > -1 composes Dense(speaker_proj_dim, relu)
+        # behind the speaker embedding - the pre-net's speaker projection then reads speaker_proj_dim features.
+        # speaker_for_synthesis (:333-339): > -1 replaces the speaker id of every row, in every mode.  Dual-source model only.
+        self.speaker_proj_dim = -1; self.speaker_for_synthesis = -1
         # optional PostNetV2 (reference hparams.py:158-162, models/models.py:92-100; off in the shipped configs)
         self.use_postnet_v2 = False; self.num_postnet_v2_layers = 5; self.postnet_v2_kernel_size = 5
         self.postnet_v2_out_channels = 512; self.postnet_v2_drop_rate = 0.5
@@ -63,6 +67,15 @@ class ModelConfig:
     @property
     def accent(self):
         return self.num_accent_type > 0
+
+    @property
+    def speaker_resize(self):
+        return self.num_speakers > 0 and self.speaker_proj_dim > -1
+
+    @property
+    def speaker_feat(self):
+        """features the multi-speaker pre-net's speaker projection reads: the resize layer's width, or the embedding's"""
+        return self.speaker_proj_dim if self.speaker_resize else self.speaker_dim
 
     @property
     def prenet_width(self):
@@ -122,6 +135,10 @@ class ModelConfig:
             zc=hp.zoneout_factor_cell, zh=hp.zoneout_factor_output,
             num_speakers=hp.num_speakers if hp.use_speaker_embedding else 0, speaker_dim=hp.speaker_embedding_dim,
             speaker_offset=hp.speaker_embedding_offset,
+            # ExtendedTacotronV1Model never reads these two (reference models/models.py:39-52): the baseline ignores them
+            **(dict(speaker_proj_dim=int(hp.speaker_embedding_projection_out_dim),
+                    speaker_for_synthesis=int(hp.speaker_for_synthesis))
+               if (hp.use_speaker_embedding and not baseline) else {}),
             use_postnet_v2=bool(hp.use_postnet_v2), num_postnet_v2_layers=hp.num_postnet_v2_layers,
             postnet_v2_kernel_size=hp.postnet_v2_kernel_size, postnet_v2_out_channels=hp.postnet_v2_out_channels,
             postnet_v2_drop_rate=hp.postnet_v2_drop_rate)
@@ -172,12 +189,14 @@ def param_shapes(c):
                   (pre + ".t.W", (S, S)), (pre + ".t.b", (S,))]
     if c.num_speakers > 0:
         L.append(("speaker_embedding", (c.num_speakers, c.speaker_dim)))
+        if c.speaker_resize:        # behind speaker_embedding: the decoder range of the flat buffer (DP bucket, clip, Adam)
+            L += [("speaker_resize.W", (c.speaker_dim, c.speaker_proj_dim)), ("speaker_resize.b", (c.speaker_proj_dim,))]
     i = c.num_mels * c.n_feed_frame
     for n, o in enumerate(c.dec_prenet):
         L += [(f"dec.prenet{n}.W", (i, o)), (f"dec.prenet{n}.b", (o,))]
         i = o
     if c.num_speakers > 0:
-        L += [("dec.prenet0.Ws", (c.speaker_dim, c.dec_prenet[0])), ("dec.prenet0.bs", (c.dec_prenet[0],)),
+        L += [("dec.prenet0.Ws", (c.speaker_feat, c.dec_prenet[0])), ("dec.prenet0.bs", (c.dec_prenet[0],)),
               ("dec.prenet0.W2", (c.dec_prenet[0], c.dec_prenet[0])), ("dec.prenet0.b2", (c.dec_prenet[0],))]
     A = c.att_rnn_units
     L += [("dec.att_lstm.W", (c.dec_prenet[-1] + c.ctx_dim + A, 4 * A)), ("dec.att_lstm.b", (4 * A,))]

@@ -87,6 +87,10 @@ def main(argv=None):
                                    device="cuda:%d" % local, dp=dp)
     if model.global_step:
         logging.info("resumed from step %d", model.global_step)
+    sfs = model.engine.cfg.speaker_for_synthesis
+    if sfs > -1:
+        logging.warning("speaker_for_synthesis=%d is set during TRAINING: every utterance is conditioned on that one speaker and "
+                        "only its embedding row receives gradient (the reference's model function does the same in every mode)", sfs)
 
     # reference train.py:34-36: reader parallelism of the interleave from the hparams and the host's core count
     interleave_parallelism = get_parallelism(hparams.interleave_cycle_length_cpu_factor, hparams.interleave_cycle_length_min,
