@@ -158,6 +158,15 @@ int satt_speaker_cond_supported(int B, int E, int R, int P0);
 int satt_speaker_cond_fwd(int mode, const int64_t* ids, int64_t scalar_id, const float* emb_in, int B, const float* table,
                           int nspk, int offset, int E, const float* Wr, const float* br, int R, const float* Ws,
                           const float* bs, int P0, float* semb, float* rs, float* sproj, void* stream);
+/* ---- speaker vector fed to the decoder memories (speaker_embedd_to_decoder, reference models/models.py:366-372; csrc/speaker_cond.hip).
+ * The speaker columns of a memory are constant over its rows, so every consumer of the wide context takes a per-sample row:
+ * satt_rows_bcast_add: y[(b * T + t) * ld + n] += v[b * ldv + n] for t0 <= t < t1 (t1 <= T; t0 >= t1: nothing is launched);
+ *   16-byte accesses when N, ld, ldv are multiples of 4 and both bases are 16-byte aligned, one float per lane otherwise.
+ * satt_rows_time_sum: dv[b * lddv + n] = sum over t0 <= t < min(T, lengths[b]) of dy[(b * T + t) * ld + n] (lengths int64 [B] or
+ *   NULL = T; an empty range gives zeros).  Fixed summation order, no atomics: two runs on the same input are bit-equal. */
+int satt_rows_bcast_add(float* y, int64_t ld, const float* v, int64_t ldv, int B, int T, int N, int t0, int t1, void* stream);
+int satt_rows_time_sum(const float* dy, int64_t ld, const int64_t* lengths, float* dv, int64_t lddv, int B, int T, int N, int t0,
+                       void* stream);
 
 /* dx = dy * act'(y) (* scale where y != 0 for dropout-after-relu); y is the POST-activation(-dropout) output */
 int satt_act_bwd(const float* dy, int64_t lddy, const float* y, int64_t ldy, float* dx, int64_t lddx,

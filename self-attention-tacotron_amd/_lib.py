@@ -146,6 +146,8 @@ SIGNATURES = {
                                     _P, _P, _P, _P, _P, _P]),
     "satt_speaker_cond_supported": (_I, [_I, _I, _I, _I]),
     "satt_speaker_cond_fwd": (_I, [_I, _P, c_i64, _P, _I, _P, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P]),
+    "satt_rows_bcast_add": (_I, [_P, c_i64, _P, c_i64, _I, _I, _I, _I, _I, _P]),
+    "satt_rows_time_sum": (_I, [_P, c_i64, _P, _P, c_i64, _I, _I, _I, _I, _P]),
     "satt_act_bwd": (_I, [_P, c_i64, _P, c_i64, _P, c_i64, _I, _I, _I, _F, _P]),
     "satt_act_bwd_res": (_I, [_P, c_i64, _P, c_i64, _P, c_i64, _P, c_i64, _I, _I, _I, _F, _P]),
     "satt_bn_ws_floats": (c_i64, [_I, _I]),

@@ -104,3 +104,88 @@ extern "C" int satt_speaker_cond_fwd(int mode, const int64_t* ids, int64_t scala
   hipLaunchKernelGGL(speaker_cond_fwd_k, dim3(1), dim3(SC_NT), sc_fwd_lds(B, E, R), S_, a, semb, rs, sproj);
   SATT_LAUNCH_CHECK(); return SATT_OK;
 }
+
+// ---- speaker vector fed to the decoder memories (speaker_embedd_to_decoder, reference models/models.py:366-372) ----------------
+// The speaker columns of a memory are the same in every memory row and attention weights sum to one, so the wide memories are
+// never formed (engine.py): every consumer of the wide context receives a per-sample row instead.  Two memory-bound kernels:
+//   rows_bcast_add:  y[b, t, :] += v[b, :]            for t0 <= t < t1       (gate pre-activations, key rows)
+//   rows_time_sum:   dv[b, :]   = sum_t dy[b, t, :]   for t0 <= t < min(T, len_b)   (their gradients)
+// rows_bcast_add: one float4 (or, without 16-byte rows, one float) per thread, the feature index on the lanes.
+// rows_time_sum: a workgroup owns 64 columns of one sample (lanes = columns: coalesced 256-byte row pieces); its RS_NW waves take
+// the time steps t0 + w, t0 + w + RS_NW, ... in ascending order and the partial sums are combined through LDS in wave order -
+// a FIXED summation order, no float atomics: two runs on the same input are bit-equal.  Every LDS word read was written by the
+// same launch (all RS_NW x 64 partials are stored, columns beyond N as zeros).
+namespace {
+
+constexpr int RB_NT = 256;
+constexpr int RS_NW = 8, RS_COLS = 64;
+
+template <bool VEC>
+__global__ __launch_bounds__(RB_NT) void rows_bcast_add_k(float* __restrict__ y, int64_t ld, const float* __restrict__ v, int64_t ldv,
+                                                          int T, int N, int t0, int nt, int64_t total) {
+  const int W = VEC ? N / 4 : N;            // work items per row
+  const int64_t idx = (int64_t)blockIdx.x * RB_NT + threadIdx.x;
+  if (idx >= total) return;
+  const int64_t row = idx / W;
+  const int c = (int)(idx - row * W);
+  const int b = (int)(row / nt), t = t0 + (int)(row - (int64_t)b * nt);
+  float* yp = y + ((int64_t)b * T + t) * ld;
+  const float* vp = v + (int64_t)b * ldv;
+  if (VEC) {
+    float4 a = *reinterpret_cast<float4*>(yp + 4 * c);
+    const float4 s = *reinterpret_cast<const float4*>(vp + 4 * c);
+    a.x += s.x; a.y += s.y; a.z += s.z; a.w += s.w;
+    *reinterpret_cast<float4*>(yp + 4 * c) = a;
+  } else {
+    yp[c] += vp[c];
+  }
+}
+
+__global__ __launch_bounds__(RS_NW * RS_COLS) void rows_time_sum_k(const float* __restrict__ dy, int64_t ld,
+                                                                   const int64_t* __restrict__ lengths, float* __restrict__ dv,
+                                                                   int64_t lddv, int T, int N, int t0) {
+  __shared__ float part[RS_NW][RS_COLS];
+  const int lane = threadIdx.x % RS_COLS, w = threadIdx.x / RS_COLS;
+  const int b = blockIdx.y, n = blockIdx.x * RS_COLS + lane;
+  int te = T;
+  if (lengths) { const int64_t l = lengths[b]; te = (int)(l < 0 ? 0 : (l < T ? l : T)); }
+  float acc = 0.f;
+  if (n < N) {
+    const float* p = dy + (int64_t)b * T * ld + n;
+    for (int t = t0 + w; t < te; t += RS_NW) acc += p[(int64_t)t * ld];
+  }
+  part[w][lane] = acc;
+  __syncthreads();
+  if (w == 0 && n < N) {
+    float s = part[0][lane];
+#pragma unroll
+    for (int i = 1; i < RS_NW; ++i) s += part[i][lane];
+    dv[(int64_t)b * lddv + n] = s;
+  }
+}
+
+inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+extern "C" int satt_rows_bcast_add(float* y, int64_t ld, const float* v, int64_t ldv, int B, int T, int N, int t0, int t1,
+                                   void* stream) {
+  if (!y || !v || B <= 0 || T <= 0 || N <= 0 || ld < N || ldv < N || t0 < 0 || t1 > T) return SATT_E_BADARG;
+  if (t0 >= t1) return SATT_OK;            // empty range: y stays as it is
+  const int nt = t1 - t0;
+  const bool vec = N % 4 == 0 && ld % 4 == 0 && ldv % 4 == 0 && al16(y) && al16(v);
+  const int64_t total = (int64_t)B * nt * (vec ? N / 4 : N);
+  const int64_t blocks = (total + RB_NT - 1) / RB_NT;
+  if (blocks > 0x7fffffffLL) return SATT_E_UNSUPPORTED;
+  if (vec) hipLaunchKernelGGL(rows_bcast_add_k<true>, dim3((unsigned)blocks), dim3(RB_NT), 0, S_, y, ld, v, ldv, T, N, t0, nt, total);
+  else hipLaunchKernelGGL(rows_bcast_add_k<false>, dim3((unsigned)blocks), dim3(RB_NT), 0, S_, y, ld, v, ldv, T, N, t0, nt, total);
+  SATT_LAUNCH_CHECK(); return SATT_OK;
+}
+
+extern "C" int satt_rows_time_sum(const float* dy, int64_t ld, const int64_t* lengths, float* dv, int64_t lddv, int B, int T, int N,
+                                  int t0, void* stream) {
+  if (!dy || !dv || B <= 0 || T <= 0 || N <= 0 || ld < N || lddv < N || t0 < 0 || B > 65535) return SATT_E_BADARG;
+  hipLaunchKernelGGL(rows_time_sum_k, dim3((N + RS_COLS - 1) / RS_COLS, B), dim3(RS_NW * RS_COLS), 0, S_, dy, ld, lengths, dv, lddv,
+                     T, N, t0);
+  SATT_LAUNCH_CHECK(); return SATT_OK;
+}

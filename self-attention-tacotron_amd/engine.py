@@ -94,7 +94,93 @@ class Engine:
         self._shadow_table = torch.tensor(tab, dtype=torch.int64, device=self.dev)
         self._shadow_count = len(tab) // 4
         self.shadow = {}
+        self._init_speaker_to_decoder()
         self.refresh_shadows()
+
+    # ------------------------------------------------------------------ speaker vector fed to the decoder memories
+    def _init_speaker_to_decoder(self):
+        """speaker_to_decoder (reference models/models.py:366-372): the memories are [lstm_out | s] and [sa_out | s].  The speaker
+        columns are the same in every memory row and the alignments sum to one, so the wide memories are never formed:
+          keys_r    = values_r Wm_r[:V_r]  +  s Wm_r[V_r:]                          (a per-sample row added to every key row)
+          [ctx_r|s] W[rows of source r]    = ctx_r W[V_r rows]  +  s W[S rows]      (a per-sample row added to the gates)
+        and the recurrent kernels, their weight packs and the folded context see V1, V2 exactly as without the flag.  They read
+        NARROW copies of the two cell kernels (the wide tensors without their speaker rows, self._nw; re-made after every update
+        with the other shadows); the speaker rows meet s in four [B, S] x [S, N] products per step (forward: _speaker_dec_fwd)."""
+        c = self.cfg
+        S = self._ms = c.mem_speaker
+        self._nw, self._nw_rows, self._spk_w = {}, {}, {}
+        if not S:
+            return
+        pn, V1, V2, A, D = c.dec_prenet[-1], c.cbhg_out_units, c.sa_units, c.att_rnn_units, c.dec_units
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        b16 = dict(dtype=torch.bfloat16, device=self.dev)
+        for name, lead, tail in (("dec.att_lstm.W", pn, A), ("dec.lstm1.W", A, D)):
+            # wide rows [lead | V1 | S | V2 | S | tail] -> kept [lead + V1], [V2], [tail]; speaker rows of source 1 and 2
+            keep = [(0, lead + V1), (lead + V1 + S, lead + V1 + S + V2), (lead + V1 + V2 + 2 * S, lead + V1 + V2 + 2 * S + tail)]
+            rows, N = sum(b - a for a, b in keep), self.P[name].shape[1]
+            self._nw[name] = ops.Weight(torch.empty(rows, N, **f32), torch.empty(N, rows, **b16), torch.empty(rows, N, **b16))
+            self._nw_rows[name] = (keep, (lead + V1, lead + V1 + S), (lead + V1 + S + V2, lead + V1 + V2 + 2 * S))
+            self._spk_w[name] = torch.empty(S, N, **f32)       # W[S rows of source 1] + W[S rows of source 2]
+
+    def _refresh_narrow(self):
+        """the narrow cell kernels and the summed speaker rows from the updated parameters (copies and one addition per tensor)"""
+        for name, Wn in self._nw.items():
+            keep, s1, s2 = self._nw_rows[name]
+            Wp, o = self.P[name], 0
+            for a, b in keep:
+                Wn.w[o:o + b - a].copy_(Wp[a:b]); o += b - a
+            ops.to_bf16(Wn.w, Wn.t, transpose=True)
+            ops.to_bf16(Wn.w, Wn.n, transpose=False)
+            self._spk_w[name].copy_(Wp[s1[0]:s1[1]])
+            ops.axpby(Wp[s2[0]:s2[1]], self._spk_w[name], 1.0, 1.0)
+
+    def Pd(self, name):
+        """fp32 view of a decoder cell kernel as the recurrent kernels read it: without its speaker rows (speaker_to_decoder), else
+        the parameter itself"""
+        return self._nw[name].w if name in self._nw else self.P[name]
+
+    def Wd(self, name):
+        """GEMM operand of Pd(name)"""
+        return self._nw[name] if name in self._nw else self._wref[name]
+
+    def _speaker_dec_fwd(self, spk, B):
+        """the four per-sample rows of speaker_to_decoder from s = the vector the pre-net's speaker projection reads:
+        gs_att [B, 4A], gs_l1 [B, 4D] (gate terms of the two cells), ks1 [B, U1], ks2 [B, U2] (key terms).  4 launches."""
+        c, P = self.cfg, self.P
+        s = spk["rs"] if c.speaker_resize else spk["semb"]
+        V1, V2 = c.cbhg_out_units, c.sa_units
+        d = spk["dec"]
+        d["s"] = s
+        ops.linear(s, self._spk_w["dec.att_lstm.W"], None, d["gs_att"])
+        ops.linear(s, self._spk_w["dec.lstm1.W"], None, d["gs_l1"])
+        ops.linear(s, P["dec.att1.Wm"][V1:], None, d["ks1"])
+        ops.linear(s, P["dec.att2.Wm"][V2:], None, d["ks2"])
+        return d
+
+    def _speaker_dec_bwd(self, ctx, dxga, dxg1, dkeys1, dkeys2, ds):
+        """backward of the four per-sample rows: time sums of the gate / key gradients (keys: rows below source_length only - the
+        reference zeroes the memory past it), the speaker rows of the four weight tensors, and ds [B, S] += the gradient wrt s.
+        4 sums + 6 weight-gradient products + 4 input-gradient products, on the weight-gradient stream."""
+        c, P, G = self.cfg, self.P, self.G
+        B, Ti, Td, _ = ctx["dims"]
+        d = ctx["spk"]["dec"]
+        s, V1, V2 = d["s"], c.cbhg_out_units, c.sa_units
+        slen = ctx["batch"]["source_length"]
+        dgs_att, dgs_l1 = self._e(B, 4 * c.att_rnn_units), self._e(B, 4 * c.dec_units)
+        dks1, dks2 = self._e(B, c.att1_units), self._e(B, c.att2_units)
+        ops.rows_time_sum(dxga, None, dgs_att, B, Td, t0=1)        # step 0 reads the all-zero initial attention: no speaker term
+        ops.rows_time_sum(dxg1, None, dgs_l1, B, Td)
+        ops.rows_time_sum(dkeys1, slen, dks1, B, Ti)
+        ops.rows_time_sum(dkeys2, slen, dks2, B, Ti)
+        for name, dg in (("dec.att_lstm.W", dgs_att), ("dec.lstm1.W", dgs_l1)):
+            _, s1, s2 = self._nw_rows[name]
+            ops.linear_dw(s, dg, G[name][s1[0]:s1[1]])
+            ops.linear_dw(s, dg, G[name][s2[0]:s2[1]])
+            ops.linear_dx(dg, self._spk_w[name], ds, accumulate=True)
+        ops.linear_dw(s, dks1, G["dec.att1.Wm"][V1:])
+        ops.linear_dw(s, dks2, G["dec.att2.Wm"][V2:])
+        ops.linear_dx(dks1, P["dec.att1.Wm"][V1:], ds, accumulate=True)
+        ops.linear_dx(dks2, P["dec.att2.Wm"][V2:], ds, accumulate=True)
 
     # ------------------------------------------------------------------ bf16 shadows of the recurrent weights
     def _shadow(self, name, src):
@@ -115,6 +201,8 @@ class Engine:
         read exist (one launch); the rest - the recurrent kernels' operand layouts - is first needed by the encoder LSTM."""
         c, P = self.cfg, self.P
         ops.shadow_pack(self.flat, self._shadow_table, self._shadow_count, self.st_flat, self.sn_flat)
+        if self._nw:
+            self._refresh_narrow()
         if after_gemm_shadows is not None:
             after_gemm_shadows()
         used = [k for k in getattr(self, "_pack_cache", {})]       # cluster sizes of the last step: re-packed right away
@@ -127,10 +215,10 @@ class Engine:
             ops.to_bf16(P[f"enc.lstm_{n}.W"][H:], self.shadow["enc.Wh"][d], False)
             ops.to_bf16(P[f"enc.lstm_{n}.W"][H:], self.shadow["enc.Wh.T"][d], True)
         pn = c.dec_prenet[-1]
-        self._shadow("att.Wrec", P["dec.att_lstm.W"][pn:])
+        self._shadow("att.Wrec", self.Pd("dec.att_lstm.W")[pn:])
         self._shadow("att.Wq", P["dec.att.Wq"])
         A = c.att_rnn_units
-        self._shadow("l1.Wh", P["dec.lstm1.W"][A + c.ctx_dim:])
+        self._shadow("l1.Wh", self.Pd("dec.lstm1.W")[A + c.ctx_dim:])
         self._shadow("l2.Wh", P["dec.lstm2.W"][c.dec_units:])
         if self._out_pad():             # output projection with zero-padded rows (input-gradient GEMM, see backward())
             NO = P["dec.out.W"].shape[1]
@@ -145,9 +233,9 @@ class Engine:
             elif isinstance(k, tuple) and k[0] == "lstm_in":
                 self.lstm_cluster_in_packs(k[1])
             elif isinstance(k, int):
-                self._pack_cache[k] = ops.attn_cluster_pack(P["dec.att_lstm.W"][c.dec_prenet[-1]:], A, k)
+                self._pack_cache[k] = ops.attn_cluster_pack(self.Pd("dec.att_lstm.W")[c.dec_prenet[-1]:], A, k)
             elif isinstance(k, tuple) and k[0] == "fold":
-                self._pack_cache[k] = ops.attn_cluster_pack(P["dec.att_lstm.W"][c.dec_prenet[-1] + c.cbhg_out_units:], A, k[1])
+                self._pack_cache[k] = ops.attn_cluster_pack(self.Pd("dec.att_lstm.W")[c.dec_prenet[-1] + c.cbhg_out_units:], A, k[1])
         self._refresh_folded()
 
     def _refresh_folded(self):
@@ -366,7 +454,7 @@ class Engine:
             c, P = self.cfg, self.P
             n1, D = c.att_rnn_units + c.ctx_dim, c.dec_units
             ok = lambda k: k <= ops.LSTM_CLUSTER_FUSED_KMAX and k % 4 == 0
-            self._pack_cache[key] = (ops.lstm_cluster_pack_in(P["dec.lstm1.W"][:n1], D, Cn) if ok(n1) else None,
+            self._pack_cache[key] = (ops.lstm_cluster_pack_in(self.Pd("dec.lstm1.W")[:n1], D, Cn) if ok(n1) else None,
                                      ops.lstm_cluster_pack_in(P["dec.lstm2.W"][:D], D, Cn) if ok(D) else None)
         return self._pack_cache[key]
 
@@ -378,7 +466,7 @@ class Engine:
             c, P = self.cfg, self.P
             n1 = c.att_rnn_units + c.ctx_dim
             D = c.dec_units
-            self._pack_cache[key] = (ops.lstm_cluster_pack(P["dec.lstm1.W"][n1:], D, Cn),
+            self._pack_cache[key] = (ops.lstm_cluster_pack(self.Pd("dec.lstm1.W")[n1:], D, Cn),
                                      ops.lstm_cluster_pack(P["dec.lstm2.W"][D:], D, Cn))
         return self._pack_cache[key]
 
@@ -912,16 +1000,18 @@ class Engine:
             return torch.full((B,), src, dtype=torch.int64, device=self.dev)
         return None if src.is_floating_point() else src
 
-    def _speaker_term_bwd(self, spk, ds):
-        """parameter gradients of speaker_term() from ds = d sproj [B, P0]: generic ops (7 launches with the resize layer)"""
+    def _speaker_term_bwd(self, spk, ds, dx_more=None):
+        """parameter gradients of speaker_term() from ds = d sproj [B, P0]: generic ops (7 launches with the resize layer).
+        dx_more [B, speaker_feat]: a gradient wrt the vector the projection reads that arrives from elsewhere (speaker_to_decoder);
+        the projection's own input gradient is accumulated onto it."""
         c, G = self.cfg, self.G
         B = ds.shape[0]
         dsp = self._e(B, c.dec_prenet[0])
         ops.act_bwd(ds, spk["sproj"], dsp, ACT_SOFTSIGN)
         x = spk["rs"] if c.speaker_resize else spk["semb"]
         ops.linear_dw(x, dsp, G["dec.prenet0.Ws"], db=G["dec.prenet0.bs"])
-        dx = self._e(B, c.speaker_feat)
-        ops.linear_dx(dsp, self.W("dec.prenet0.Ws"), dx)
+        dx = self._e(B, c.speaker_feat) if dx_more is None else dx_more
+        ops.linear_dx(dsp, self.W("dec.prenet0.Ws"), dx, accumulate=dx_more is not None)
         if c.speaker_resize:
             drs = self._e(B, c.speaker_proj_dim)
             ops.act_bwd(dx, spk["rs"], drs, ACT_RELU)
@@ -968,6 +1058,9 @@ class Engine:
                        r0=self._e(Md, c.dec_prenet[0]), d0=self._e(Md, c.dec_prenet[0]))
             if c.speaker_resize:
                 spk["rs"] = self._e(B, c.speaker_proj_dim)
+            if self._ms:        # speaker_to_decoder: per-sample gate and key rows (_speaker_dec_fwd)
+                spk["dec"] = dict(gs_att=self._e(B, G4), gs_l1=self._e(B, 4 * c.dec_units), ks1=self._e(B, c.att1_units),
+                                  ks2=self._e(B, c.att2_units))
 
         def teacher_branch():
             dec_in3[:, :1].zero_()                                              # go frame
@@ -997,6 +1090,9 @@ class Engine:
                                drop=Drop(self.dec_prenet_rate(training, plain=True), (S_DEC_PRENET0, S_DEC_PRENET1)[n], seed))
                 x = y
             ops.linear(dpre[-1], self.W("dec.att_lstm.W").rows(0, pn), P["dec.att_lstm.b"], xg_att)
+            if self._ms:        # speaker_to_decoder: + s W[speaker rows] from step 1 on (step 0 reads the all-zero initial attention)
+                sd = self._speaker_dec_fwd(spk, B)
+                ops.rows_bcast_add(xg_att, sd["gs_att"], B, Td, t0=1)
 
         main0 = ops.current_stream()
         side = self._streams() if self.overlap_wgrad else main0
@@ -1058,12 +1154,17 @@ class Engine:
         values1 = self._e(M, V1)
         ops.seq_mask(lstm_out, slen, values1, B, Ti, V1, round_bf16=mem_bf16)
         keys1 = self._e(M, U1)
-        ops.linear(values1, self.W("dec.att1.Wm"), None, keys1)
+        MS = self._ms           # speaker_to_decoder: the memory layers' first V rows meet the memory, the rest the speaker vector
+        Wm1 = self.W("dec.att1.Wm").rows(0, V1) if MS else self.W("dec.att1.Wm")
+        ops.linear(values1, Wm1, None, keys1)
         values2 = keys2 = None
         if c.dual:
             values2, keys2 = self._e(M, V2), self._e(M, U2)
             ops.seq_mask(sa_out, slen, values2, B, Ti, V2, round_bf16=mem_bf16)
-            ops.linear(values2, self.W("dec.att2.Wm"), None, keys2)
+            ops.linear(values2, self.W("dec.att2.Wm").rows(0, V2) if MS else self.W("dec.att2.Wm"), None, keys2)
+        if MS:      # (rows past source_length get the term too: the score masks them, and their gradient is left out in backward())
+            ops.rows_bcast_add(keys1, spk["dec"]["ks1"], B, Ti)
+            ops.rows_bcast_add(keys2, spk["dec"]["ks2"], B, Ti)
         att_out = self._e(Md, A + CT)
         al1, al2, a1 = self._e(B, Td, Ti), self._e(B, Td, Ti), self._e(B, Td, Ti)
         pq = self._e(Md, U1 + U2)
@@ -1100,7 +1201,7 @@ class Engine:
         vw1, fold_pack, ctx1_rows = None, None, None
         if Ca:
             if Ca not in self._pack_cache:
-                self._pack_cache[Ca] = ops.attn_cluster_pack(P["dec.att_lstm.W"][pn:], A, Ca)
+                self._pack_cache[Ca] = ops.attn_cluster_pack(self.Pd("dec.att_lstm.W")[pn:], A, Ca)
             aws = self._cluster_ws("attn", lambda: ops.attn_cluster_ws(ap, Ca, self.dev), (B, Ti, Ca, A, U1, U2, V1, V2))
             if self.fold_context and ops.attn_cluster_fold(ap, Ca):
                 # FOLDED first-source context (csrc/attn_cluster.hip, FOLD): gates += ctx1 Wc1 = alpha (values1 Wc1).  VW1 is one
@@ -1109,7 +1210,7 @@ class Engine:
                 # pipeline chunk on the LSTM1 stream, exact fp32 (the backward kernel's row sums rely on ctx1 = sum alpha v)
                 key = ("fold", Ca)
                 if key not in self._pack_cache:
-                    self._pack_cache[key] = ops.attn_cluster_pack(P["dec.att_lstm.W"][pn + V1:], A, Ca)
+                    self._pack_cache[key] = ops.attn_cluster_pack(self.Pd("dec.att_lstm.W")[pn + V1:], A, Ca)
                 fold_pack = self._pack_cache[key][0]
                 vw1 = self._e(M, G4)
                 ops.linear(values1, self.W("dec.att_lstm.W").rows(pn, pn + V1), None, vw1)
@@ -1183,12 +1284,14 @@ class Engine:
                     if ctx1_rows is not None:
                         ctx1_rows(t0, t1)
                     fuse = lin is not None and t1 - t0 <= self.fuse_xg_steps
-                    if fuse and lin[0] is not None:
+                    if fuse and lin[0] is not None and not MS:      # (the fused input projection has no per-sample term)
                         with self._t("lstm1_fwd"):
                             ops.lstm_cluster_fwd_x(att_out, A + CT, lin[0], P["dec.lstm1.b"], xg1, lp1[0], B, Td, D, Cn, training, c.zc,
                                                    c.zh, seed, S_L1_C, S_L1_H, h1, l1[0], l1[1], l1[2], l1[3], cws1, t0, t1)
                     else:
-                        ops.linear_rows(att_out, self.W("dec.lstm1.W").rows(0, A + CT), P["dec.lstm1.b"], xg1[0], B, Td, t0, t1)
+                        ops.linear_rows(att_out, self.Wd("dec.lstm1.W").rows(0, A + CT), P["dec.lstm1.b"], xg1[0], B, Td, t0, t1)
+                        if MS:
+                            ops.rows_bcast_add(xg1[0], spk["dec"]["gs_l1"], B, Td, t0, t1)
                         with self._t("lstm1_fwd"):
                             ops.lstm_cluster_fwd(xg1, lp1[0], B, Td, D, Cn, training, c.zc, c.zh, seed,
                                                  S_L1_C, S_L1_H, h1, l1[0], l1[1], l1[2], l1[3], cws1, t0, t1)
@@ -1215,7 +1318,9 @@ class Engine:
                     ops.attn_rnn_fwd(ap)
             if ctx1_rows is not None:
                 ctx1_rows(0, Td)
-            ops.linear(att_out, self.W("dec.lstm1.W").rows(0, A + CT), P["dec.lstm1.b"], xg1[0])
+            ops.linear(att_out, self.Wd("dec.lstm1.W").rows(0, A + CT), P["dec.lstm1.b"], xg1[0])
+            if MS:
+                ops.rows_bcast_add(xg1[0], spk["dec"]["gs_l1"], B, Td)
             with self._t("lstm1_fwd"):
                 if Cn:
                     ops.lstm_cluster_fwd(xg1, lp1[0], B, Td, D, Cn, training, c.zc, c.zh, seed, S_L1_C,
@@ -1513,10 +1618,17 @@ class Engine:
             run(lambda: (ops.linear_dw(h1, dxg[0], G["dec.lstm2.W"][:D], db=G["dec.lstm2.b"])))
             run(lambda: (ops.shifted_dw(hs2[0], Td, -1, dxg[0], G["dec.lstm2.W"][D:])))
 
+        MS = self._ms       # speaker_to_decoder: rows of the wide kernels = [lead | V1 | S | V2 | S | tail]
+
         def lstm1_dw(direct=False):
             run = (lambda f: f()) if direct else self._wgrad
-            run(lambda: (ops.linear_dw(att_out, dxg1[0], G["dec.lstm1.W"][:A + CT], db=G["dec.lstm1.b"])))
-            run(lambda: (ops.shifted_dw(hs1[0], Td, -1, dxg1[0], G["dec.lstm1.W"][A + CT:])))
+            G1 = G["dec.lstm1.W"]
+            if MS:
+                run(lambda: (ops.linear_dw(att_out[:, :A + V1], dxg1[0], G1[:A + V1], db=G["dec.lstm1.b"])))
+                run(lambda: (ops.linear_dw(att_out[:, A + V1:], dxg1[0], G1[A + V1 + MS:A + V1 + MS + V2])))
+            else:
+                run(lambda: (ops.linear_dw(att_out, dxg1[0], G1[:A + CT], db=G["dec.lstm1.b"])))
+            run(lambda: (ops.shifted_dw(hs1[0], Td, -1, dxg1[0], G1[A + CT + 2 * MS:])))
 
         if NC > 1:
             main = ops.current_stream()
@@ -1569,7 +1681,7 @@ class Engine:
                     with self._t("lstm1_bwd"):
                         ops.lstm_cluster_bwd(dh1, lp1[1], B, Td, D, Cn, training, c.zc, c.zh, seed,
                                              S_L1_C, S_L1_H, g1, cn1, cs1, dxg1, cws1, t0, t1, bst1)
-                    ops.linear_dx_rows(dxg1[0], self.W("dec.lstm1.W").rows(0, A + CT), datt, B, Td, t0, t1)
+                    ops.linear_dx_rows(dxg1[0], self.Wd("dec.lstm1.W").rows(0, A + CT), datt, B, Td, t0, t1)
                     if single:
                         ops.stream_write_value(ready, pieces_upto[k], ls)     # chunk k of d att_out exists
                         if first:
@@ -1659,7 +1771,7 @@ class Engine:
                     ops.lstm_bwd(dh1, self.shadow["l1.Wh.T"], None, 1, B, Td, D, training, c.zc, c.zh, seed,
                                  (S_L1_C,), (S_L1_H,), g1, cn1, cs1, dxg1)
             lstm1_dw()
-            ops.linear_dx(dxg1[0], self.W("dec.lstm1.W").rows(0, A + CT), datt)
+            ops.linear_dx(dxg1[0], self.Wd("dec.lstm1.W").rows(0, A + CT), datt)
             with self._t("attn_rnn_bwd"):
                 if Ca:
                     ops.attn_cluster_bwd(ctx["att_params"], Ca, self._pack_cache[Ca][1], aws, **attn_kw)
@@ -1691,8 +1803,8 @@ class Engine:
                      sA=(Td * Ti, 0), sB=(Td * CT, 0), sC=(Ti * V1, 0))
             if pg_ev is not None:
                 ops.current_stream().wait_event(pg_ev)
-            ops.linear_dx(dkeys1, self.W("dec.att1.Wm"), dv1, accumulate=True)
-            self._wgrad(lambda: (ops.linear_dw(ctx["values1"], dkeys1, G["dec.att1.Wm"])))
+            ops.linear_dx(dkeys1, self.W("dec.att1.Wm").rows(0, V1) if MS else self.W("dec.att1.Wm"), dv1, accumulate=True)
+            self._wgrad(lambda: (ops.linear_dw(ctx["values1"], dkeys1, G["dec.att1.Wm"][:V1] if MS else G["dec.att1.Wm"])))
             ops.seq_mask(dv1, slen, dlstm_out, B, Ti, V1)
         src1_done = None
         if c.dual and self.overlap_wgrad and self._wg_rr is not None and len(self._wg_rr) > 1:
@@ -1710,8 +1822,8 @@ class Engine:
                      sA=(Td * Ti, 0), sB=(Td * CT, 0), sC=(Ti * V2, 0))
             if pg_ev is not None:
                 ops.current_stream().wait_event(pg_ev)
-            ops.linear_dx(dkeys2, self.W("dec.att2.Wm"), dv2, accumulate=True)
-            self._wgrad(lambda: (ops.linear_dw(ctx["values2"], dkeys2, G["dec.att2.Wm"])), defer=True)
+            ops.linear_dx(dkeys2, self.W("dec.att2.Wm").rows(0, V2) if MS else self.W("dec.att2.Wm"), dv2, accumulate=True)
+            self._wgrad(lambda: (ops.linear_dw(ctx["values2"], dkeys2, G["dec.att2.Wm"][:V2] if MS else G["dec.att2.Wm"])), defer=True)
             dsa_out = self._e(M, V2)
             ops.seq_mask(dv2, slen, dsa_out, B, Ti, V2)
         # location filter: dF[j,0,k] = sum a_{t-1}[t'+j-pl] * dfl[t',k]  (a 1-channel conv weight gradient), dbF
@@ -1734,8 +1846,12 @@ class Engine:
         dpre = ctx["dpre"]
         Wa, Ga = P["dec.att_lstm.W"], G["dec.att_lstm.W"]
         self._wgrad(lambda: (ops.linear_dw(dpre[-1], dxga, Ga[:pn], db=G["dec.att_lstm.b"])), defer=True)
-        self._wgrad(lambda: (ops.shifted_dw(att_out[:, A:], Td, -1, dxga, Ga[pn:pn + CT])), defer=True)
-        self._wgrad(lambda: (ops.shifted_dw(ahs, Td, -1, dxga, Ga[pn + CT:])), defer=True)
+        if MS:
+            self._wgrad(lambda: (ops.shifted_dw(att_out[:, A:A + V1], Td, -1, dxga, Ga[pn:pn + V1])), defer=True)
+            self._wgrad(lambda: (ops.shifted_dw(att_out[:, A + V1:], Td, -1, dxga, Ga[pn + V1 + MS:pn + V1 + MS + V2])), defer=True)
+        else:
+            self._wgrad(lambda: (ops.shifted_dw(att_out[:, A:], Td, -1, dxga, Ga[pn:pn + CT])), defer=True)
+        self._wgrad(lambda: (ops.shifted_dw(ahs, Td, -1, dxga, Ga[pn + CT + 2 * MS:])), defer=True)
         self._wgrad(lambda: (ops.linear_dw(att_out[:, :A], dpq, G["dec.att.Wq"])), defer=True)
         if c.transition_agent:      # d agent weights: sums over steps of d z [ctx1 | processed query 1] (and of d z for the bias)
             pqs = ctx["pq"]
@@ -1758,14 +1874,19 @@ class Engine:
                     ops.linear_dx(dp, self.W("dec.prenet0.W2"), dd0)
                     ds = self._e(B, c.dec_prenet[0])
                     ops.segment_colsum(dd0, ds, B, Td, c.dec_prenet[0])
+                    dsd = None          # speaker_to_decoder: the gradient wrt the speaker vector through keys and gates
+                    if MS:
+                        dsd = self._e(B, c.speaker_feat)
+                        dsd.zero_()
+                        self._speaker_dec_bwd(ctx, dxga, dxg1[0], dkeys1, dkeys2, dsd)
                     if "src" in spk:         # resize layer and / or speaker_for_synthesis: speaker_term() ran in the forward pass
-                        self._speaker_term_bwd(spk, ds)
+                        self._speaker_term_bwd(spk, ds, dsd)
                     else:
                         dsp = self._e(B, c.dec_prenet[0])
                         ops.act_bwd(ds, spk["sproj"], dsp, ACT_SOFTSIGN)
                         self._wgrad(lambda: (ops.linear_dw(spk["semb"], dsp, G["dec.prenet0.Ws"], db=G["dec.prenet0.bs"])))
-                        dsemb = self._e(B, c.speaker_dim)
-                        ops.linear_dx(dsp, self.W("dec.prenet0.Ws"), dsemb)
+                        dsemb = self._e(B, c.speaker_dim) if dsd is None else dsd
+                        ops.linear_dx(dsp, self.W("dec.prenet0.Ws"), dsemb, accumulate=dsd is not None)
                         ops.embedding_bwd(ctx["batch"]["speaker_id"], dsemb, G["speaker_embedding"], offset=c.speaker_offset)
                     dr0 = self._e(Md, c.dec_prenet[0])
                     ops.act_bwd(dd0, spk["r0"], dr0, ACT_RELU)

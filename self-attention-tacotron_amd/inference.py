@@ -39,6 +39,18 @@ class DecodeSession:
         # into LDS: ~10 us) is spread over MEGA_STEPS steps and nothing runs past the stop token but one launch that returns at
         # once.  The hipGraph path keeps `steps_per_graph` (the host polls the stop flag once per replay).
         V1, V2, U1, U2, A, D, Ds = c.cbhg_out_units, c.sa_units, c.att1_units, c.att2_units, c.att_rnn_units, c.dec_units, c.dec_sa_units
+        # speaker_to_decoder (reference models/models.py:366-372): the step kernels are generic in the memory widths, so synthesis
+        # takes the reference's own form - the memories ARE [encoder output | speaker vector] (infer() builds them once per
+        # utterance), the contexts are V + S wide and the cells read the parameters' wide kernels as they are.  The zero initial
+        # attention of step 0 covers the speaker columns as in the reference.  (Training folds the constant columns instead:
+        # Engine._init_speaker_to_decoder.)
+        MS = c.mem_speaker
+        if MS % 4:
+            from .modules.attentions import UnsupportedConfiguration
+            raise UnsupportedConfiguration("speaker_embedd_to_decoder: the decode-step kernels read 16-byte memory rows - the speaker "
+                                           "vector (speaker_embedding_dim or speaker_embedding_projection_out_dim = %d) must be a "
+                                           "multiple of 4 wide" % MS)
+        V1, V2 = V1 + MS, (V2 + MS if c.dual else V2)
         nm, r = c.num_mels, c.r
         feed, NO = nm * c.n_feed_frame, nm * r + 1
         self._mega_shape = None
@@ -465,11 +477,7 @@ def infer(eng, source, source_length, max_steps=None, teacher=None, speaker_id=N
     # ---- memories (same as Engine.forward): values = memory * seq_mask, keys = values W_m
     V1, V2 = c.cbhg_out_units, c.sa_units
     ses.lengths.copy_(slen)
-    ops.seq_mask(lstm_out, slen, ses.values1, B, Ti, V1)
-    ops.linear(ses.values1, P["dec.att1.Wm"], None, ses.keys1)
-    if c.dual:
-        ops.seq_mask(sa_out, slen, ses.values2, B, Ti, V2)
-        ops.linear(ses.values2, P["dec.att2.Wm"], None, ses.keys2)
+    svec = None
     if c.num_speakers > 0:      # multi-speaker pre-net term (constant over time): softsign(emb[speaker] Ws + bs)
         semb = torch.empty(B, c.speaker_dim, **f32)
         if c.speaker_resize or c.speaker_for_synthesis > -1:      # resize layer / one speaker for every row: Engine.speaker_term
@@ -485,6 +493,23 @@ def infer(eng, source, source_length, max_steps=None, teacher=None, speaker_id=N
             else:
                 ops.embedding_fwd(batch["speaker_id"], P["speaker_embedding"], semb, offset=c.speaker_offset)
             ops.linear(semb, P["dec.prenet0.Ws"], P["dec.prenet0.bs"], ses.sproj, act=ACT_SOFTSIGN)
+            spk = dict(semb=semb)
+        svec = spk["rs"] if c.speaker_resize else spk["semb"]
+    MS = c.mem_speaker
+
+    def memory(enc, V, values, Wm, keys):
+        """values = [encoder output | speaker vector (speaker_to_decoder)] * seq_mask, keys = values W_m"""
+        if MS:
+            wide = torch.empty(B * Ti, V + MS, **f32)
+            wide[:, :V].copy_(enc)
+            wide[:, V:].zero_()
+            ops.rows_bcast_add(wide[:, V:], svec, B, Ti)
+            enc = wide
+        ops.seq_mask(enc, slen, values, B, Ti, V + MS)
+        ops.linear(values, Wm, None, keys)
+    memory(lstm_out, V1, ses.values1, P["dec.att1.Wm"], ses.keys1)
+    if c.dual:
+        memory(sa_out, V2, ses.values2, P["dec.att2.Wm"], ses.keys2)
     if teacher is not None:
         tg = teacher.view(B, Td, nm * r)
         ses.tin[:, 0].zero_()

@@ -167,7 +167,7 @@ def validate_params(params):
     if params.use_accent_type and baseline:
         raise UnsupportedConfiguration("use_accent_type=True is not built for MI355X with ExtendedTacotronV1Model (only "
                                        "DualSourceSelfAttentionTacotronModel + SelfAttentionCBHGEncoderWithAccentType)")
-    for flag in ("use_external_speaker_embedding", "speaker_embedd_to_decoder",
+    for flag in ("use_external_speaker_embedding",
                  "speaker_embedd_to_postnet", "channel_id_to_postnet", "use_language_embedding"):
         if getattr(params, flag):
             raise UnsupportedConfiguration(f"{flag}=True is not built for MI355X")
@@ -186,6 +186,16 @@ def validate_params(params):
         if sfs > -1 and not params.use_speaker_embedding:
             raise ValueError(f"speaker_for_synthesis={sfs} needs use_speaker_embedding=True (there is no speaker embedding "
                              "to look it up in)")
+        # speaker_embedd_to_decoder (models/models.py:366-372): the speaker vector is concatenated to both attention memories.  The
+        # baseline model_fn (:20-226) never reads the key.  Without a speaker embedding the reference dies with a NameError.
+        if params.speaker_embedd_to_decoder:
+            if not params.use_speaker_embedding:
+                raise ValueError("speaker_embedd_to_decoder=True needs use_speaker_embedding=True (there is no speaker "
+                                 "embedding to feed to the decoder memories)")
+            if params.use_forward_attention_transition_agent and params.attention == "forward":
+                raise UnsupportedConfiguration("speaker_embedd_to_decoder=True with use_forward_attention_transition_agent=True is "
+                                               "not built for MI355X: the agent reads the first context, and its per-sample "
+                                               "speaker term is not built")
         if sfs > -1:
             lo, hi = int(params.speaker_embedding_offset), int(params.speaker_embedding_offset) + int(params.num_speakers)
             if not lo <= sfs < hi:

@@ -16,6 +16,9 @@ over the hand-written engine:
 speaker_embed of a multi-speaker decoder: float [B, speaker_embedding_dim] (the embedded vectors) or int64 [B] (ids).  With
 speaker_embedding_projection_out_dim > -1 the model's resize layer (Dense, relu: models/models.py:307-312) is applied behind either
 form, because the reference composes it behind the embedding.  speaker_for_synthesis replaces ids, not embedded vectors.
+With speaker_embedd_to_decoder=True the decoder still takes the UNCONCATENATED memories (lstm_out [B, Ti, cbhg_out_units], sa_out
+[B, Ti, self_attention_out_units]) plus speaker_embed: the reference concatenates the speaker vector to the memories in its
+model_fn (models/models.py:366-372), in front of the decoder call; here the bound engine applies the same term from speaker_embed.
 
 A module computes with the parameters of the Engine it is bound to: `module.bind(engine)` shares a model's engine (what
 tacotron_model_factory's models do), otherwise the first call builds one from the hparams the factory was given (fresh random

@@ -416,6 +416,23 @@ def speaker_cond_fwd(speaker, table, offset, Wr, br, Ws, bs, semb, rs, sproj):
     return True
 
 
+def rows_bcast_add(y, v, B, T, t0=0, t1=None):
+    """y[b, t, :] += v[b, :] for t0 <= t < t1 (default T); y [B*T, N] and v [B, N] row-major 2-D views (leading dimensions taken
+    from the views).  An empty range launches nothing.  csrc/speaker_cond.hip"""
+    N = v.shape[1]
+    assert y.shape == (B * T, N) and v.shape[0] == B
+    _lib.check(_lib.lib().satt_rows_bcast_add(_p(y), _ld(y), _p(v), _ld(v), B, T, N, t0, T if t1 is None else t1, _s()),
+               "rows_bcast_add")
+
+
+def rows_time_sum(dy, lengths, dv, B, T, t0=0):
+    """dv[b, :] = sum of dy[b, t, :] over t0 <= t < min(T, lengths[b]) (lengths int64 [B] or None = T); dy [B*T, N], dv [B, N]
+    row-major 2-D views.  Deterministic (fixed summation order).  csrc/speaker_cond.hip"""
+    N = dv.shape[1]
+    assert dy.shape == (B * T, N) and dv.shape[0] == B and (lengths is None or (lengths.dtype == torch.int64 and lengths.numel() == B))
+    _lib.check(_lib.lib().satt_rows_time_sum(_p(dy), _ld(dy), _p(lengths), _p(dv), _ld(dv), B, T, N, t0, _s()), "rows_time_sum")
+
+
 def act_bwd(dy, y, dx, act, scale=1.0):
     rows, cols = y.shape
     _lib.check(_lib.lib().satt_act_bwd(_p(dy), _ld(dy), _p(y), _ld(y), _p(dx), _ld(dx), rows, cols, act, scale, _s()))

@@ -50,6 +50,10 @@ class ModelConfig:
         # behind the speaker embedding - the pre-net's speaker projection then reads speaker_proj_dim features.
         # speaker_for_synthesis (:333-339): > -1 replaces the speaker id of every row, in every mode.  Dual-source model only.
         self.speaker_proj_dim = -1; self.speaker_for_synthesis = -1
+        # speaker_embedd_to_decoder (reference models/models.py:366-372, hparams.py:133): the speaker vector (the resize layer's output
+        # when there is one) is concatenated to BOTH encoder outputs before they become the attention memories, so every decoder
+        # tensor sized by a memory width grows by speaker_feat per source.  Dual-source model only.
+        self.speaker_to_decoder = False
         # optional PostNetV2 (reference hparams.py:158-162, models/models.py:92-100; off in the shipped configs)
         self.use_postnet_v2 = False; self.num_postnet_v2_layers = 5; self.postnet_v2_kernel_size = 5
         self.postnet_v2_out_channels = 512; self.postnet_v2_drop_rate = 0.5
@@ -63,6 +67,12 @@ class ModelConfig:
             raise ValueError("sa_num_hop / dec_sa_num_hop must be >= 1")
         if (self.sa_units > 0) != (self.att2_units > 0):
             raise ValueError("sa_units and att2_units are both zero (single attention source) or both positive")
+        if self.speaker_to_decoder and not (self.num_speakers > 0 and self.dual):
+            raise ValueError("speaker_to_decoder needs a speaker embedding (num_speakers > 0) and the dual-source model")
+        if self.speaker_to_decoder and self.transition_agent:
+            from .modules.attentions import UnsupportedConfiguration
+            raise UnsupportedConfiguration("speaker_to_decoder with the transition agent is not built (the agent reads the first "
+                                           "context; its per-sample speaker term is missing)")
 
     @property
     def accent(self):
@@ -85,6 +95,11 @@ class ModelConfig:
     @property
     def ctx_dim(self):
         return self.cbhg_out_units + self.sa_units
+
+    @property
+    def mem_speaker(self):
+        """speaker columns behind each attention memory (speaker_to_decoder): the memories are [V1 + this] and [V2 + this] wide"""
+        return self.speaker_feat if self.speaker_to_decoder else 0
 
     # sa_units = att2_units = 0: ONE attention source (ZoneoutEncoderV1 + AttentionRNN of ExtendedDecoder, reference
     # modules/module.py:293-342,530-623); dec_sa_units = 0: no decoder self-attention block, mel / stop projections read
@@ -135,9 +150,10 @@ class ModelConfig:
             zc=hp.zoneout_factor_cell, zh=hp.zoneout_factor_output,
             num_speakers=hp.num_speakers if hp.use_speaker_embedding else 0, speaker_dim=hp.speaker_embedding_dim,
             speaker_offset=hp.speaker_embedding_offset,
-            # ExtendedTacotronV1Model never reads these two (reference models/models.py:39-52): the baseline ignores them
+            # ExtendedTacotronV1Model never reads these three (reference models/models.py:20-226): the baseline ignores them
             **(dict(speaker_proj_dim=int(hp.speaker_embedding_projection_out_dim),
-                    speaker_for_synthesis=int(hp.speaker_for_synthesis))
+                    speaker_for_synthesis=int(hp.speaker_for_synthesis),
+                    speaker_to_decoder=bool(hp.speaker_embedd_to_decoder))
                if (hp.use_speaker_embedding and not baseline) else {}),
             use_postnet_v2=bool(hp.use_postnet_v2), num_postnet_v2_layers=hp.num_postnet_v2_layers,
             postnet_v2_kernel_size=hp.postnet_v2_kernel_size, postnet_v2_out_channels=hp.postnet_v2_out_channels,
@@ -199,18 +215,22 @@ def param_shapes(c):
         L += [("dec.prenet0.Ws", (c.speaker_feat, c.dec_prenet[0])), ("dec.prenet0.bs", (c.dec_prenet[0],)),
               ("dec.prenet0.W2", (c.dec_prenet[0], c.dec_prenet[0])), ("dec.prenet0.b2", (c.dec_prenet[0],))]
     A = c.att_rnn_units
-    L += [("dec.att_lstm.W", (c.dec_prenet[-1] + c.ctx_dim + A, 4 * A)), ("dec.att_lstm.b", (4 * A,))]
+    # speaker_to_decoder: the memories are [V1 | S] and [V2 | S] wide, so the context rows of the two cells read
+    # [ctx1 (V1) | S | ctx2 (V2) | S] and the memory layers V + S rows each (the shapes of the reference's variables)
+    MS = c.mem_speaker
+    ctxw = c.ctx_dim + (2 * MS if c.dual else MS)
+    L += [("dec.att_lstm.W", (c.dec_prenet[-1] + ctxw + A, 4 * A)), ("dec.att_lstm.b", (4 * A,))]
     L += [("dec.att.Wq", (A, c.att1_units + c.att2_units)),
-          ("dec.att1.Wm", (c.cbhg_out_units, c.att1_units)),
+          ("dec.att1.Wm", (c.cbhg_out_units + MS, c.att1_units)),
           ("dec.att1.F", (c.att_kernel, 1, c.att_filters)), ("dec.att1.bF", (c.att_filters,)),
           ("dec.att1.U", (c.att_filters, c.att1_units)), ("dec.att1.v", (c.att1_units,)),
           ("dec.att1.b", (c.att1_units,))]
     if c.transition_agent:
         L += [("dec.att1.Wa", (c.cbhg_out_units + c.att1_units, 1)), ("dec.att1.ba", (1,))]
     if c.dual:
-        L += [("dec.att2.Wm", (c.sa_units, c.att2_units)), ("dec.att2.v", (c.att2_units,))]
+        L += [("dec.att2.Wm", (c.sa_units + MS, c.att2_units)), ("dec.att2.v", (c.att2_units,))]
     D = c.dec_units
-    L += [("dec.lstm1.W", (A + c.ctx_dim + D, 4 * D)), ("dec.lstm1.b", (4 * D,))]
+    L += [("dec.lstm1.W", (A + ctxw + D, 4 * D)), ("dec.lstm1.b", (4 * D,))]
     L += [("dec.lstm2.W", (D + D, 4 * D)), ("dec.lstm2.b", (4 * D,))]
     S2 = c.dec_sa_units
     if S2 > 0:
