@@ -437,7 +437,10 @@ typedef struct {
   int U2, V2;   /* additive-attention units (32) / memory-2 depth (32) */
   int kernel, filters; /* location conv (10, 5) */
   int training;
-  int keys_lds_bf16;                   /* 1: stage keys1/keys2 once per launch in LDS as bf16 (fast path);
+  int keys_lds_bf16;                   /* 1: the loops see the keys rounded to bf16 - staged once per launch in LDS (fast path),
+                                             or, where the single-workgroup kernels' bf16 image does not fit LDS, read from
+                                             global and rounded as they are loaded (the same numbers: the choice is a function
+                                             of the dimensions and invisible here);
                                           0: read fp32 keys from global every step (exact parity mode) */
   float zc, zh; uint32_t zc_thresh, zh_thresh; const uint32_t* seed; uint32_t stream_c, stream_h;
   const int64_t* lengths;              /* [B] */
@@ -461,16 +464,17 @@ typedef struct {
   float* gates; float* cnew; float* cstate; float* hstate;   /* [B,Td,4A] [B,Td,A] x3 */
   /* forced-alignment mode (use_forced_alignment_mode; modules/teacher_forcing_attention.py:13-78, models/models.py:411-
    * 428): when both are non-NULL the mechanisms return these alignments [B,Td,Ti] instead of their own (contexts, the
-   * recorded alignment histories and everything downstream follow them).  Forward of the cluster kernels only. */
+   * recorded alignment histories and everything downstream follow them).  Forward of the cluster kernels only (the
+   * single-workgroup kernels return SATT_E_UNSUPPORTED). */
   const float* teach1; const float* teach2;
-  /* first-source mechanism options (cluster kernels only; the single-workgroup kernels return SATT_E_UNSUPPORTED):
+  /* first-source mechanism options (both kernel families):
    * att1_mode 0 = ForwardAttention (alpha recursion, modules/forward_attention.py:104-110), 1 = location_sensitive (same
    * score :13-26, the returned alignments are the softmax probabilities; modules/attentions.py:35-42);
    * cumulative != 0: the location convolution sees the running sum of the softmax alignments (:118-119), which the
    * forward pass then saves in acum [B,Td,Ti] (its value AFTER step t = the conv input of step t+1; required). */
   int att1_mode, cumulative; float* acum;
   /* transition agent of the forward attention (use_forward_attention_transition_agent; modules/forward_attention.py:80-86,
-   * 111-116; att1_mode 0, cluster kernels only): agentW != NULL -> the transition probability of step t+1 is
+   * 111-116; att1_mode 0): agentW != NULL -> the transition probability of step t+1 is
    * u = sigmoid([ctx1_t | processed query 1_t] . agentW + agentb[0]) instead of the constant 0.5 (u of step 0 = 0.5);
    * agentW [V1+U1], agentb [1]; ustate [B,Td] receives the u USED at step t (entries t >= 1; saved for backward). */
   const float* agentW; const float* agentb; float* ustate;
@@ -485,6 +489,11 @@ typedef struct {
   void* saf;
 } satt_attn_rnn_params;
 int satt_attn_rnn_fwd(const satt_attn_rnn_params* p, void* stream);
+/* SATT_OK if satt_attn_rnn_fwd AND satt_attn_rnn_bwd accept this problem (host-only check, no launch; each launcher by itself
+ * refuses on its own carve only, and the forward one is the smaller): every first-source option above, any Ti whose carve
+ * without the LDS key image fits 160 KB of LDS; SATT_E_UNSUPPORTED for filters != 5, forced
+ * alignments (teach1 / teach2) and dimensions beyond one workgroup (U1, V1 <= 256, U2, V2 <= 64, A <= 512). */
+int satt_attn_rnn_check(const satt_attn_rnn_params* p);
 
 typedef struct {
   satt_attn_rnn_params f;              /* forward tensors (inputs, outputs and saved) */

@@ -211,6 +211,7 @@ SIGNATURES = {
     "satt_lstm_cluster_residency": (_I, [_I, _I, _I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "satt_attn_rnn_fwd": (_I, [C.POINTER(AttnRnnParams), _P]),
     "satt_attn_rnn_bwd": (_I, [C.POINTER(AttnRnnBwdParams), _P]),
+    "satt_attn_rnn_check": (_I, [C.POINTER(AttnRnnParams)]),
     "satt_attn_param_grads": (_I, [C.POINTER(AttnRnnParams), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "satt_attn_param_grads_range": (_I, [C.POINTER(AttnRnnParams), _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "satt_attn_param_grads_acc_doubles": (c_i64, [C.POINTER(AttnRnnParams)]),

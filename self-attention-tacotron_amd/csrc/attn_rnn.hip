@@ -2,8 +2,11 @@
 // persistent 512-thread workgroup per sample walking all Td teacher-forced steps; samples are independent so no
 // inter-workgroup communication is needed.
 //  * recurrent weights: bf16, streamed from L2 with register double buffering (matvec.h)
-//  * keys (constant over all steps): staged ONCE per launch in LDS as bf16 (KLDS) — or read as fp32 from global
-//    every step in the exact parity mode
+//  * keys (constant over all steps): staged ONCE per launch in LDS as bf16 (KEYS_LDS) — or read as fp32 from global
+//    every step in the exact parity mode (KEYS_GLOBAL) — or, when the bf16 image does not fit LDS, read from global
+//    and rounded to bf16 as they are loaded (KEYS_GLOBAL_BF16: the same numbers as the staged form)
+//  * first-mechanism options (GEN instantiations; the plain ForwardAttention instantiations do not carry them):
+//    location_sensitive (no alpha recursion), cumulative location-conv input, transition agent
 //  * values rows: one wave per memory row, 16 B per lane, 4 rows in flight
 //  * attention state, energies and alignments: fp32 in LDS
 //  * backward: only the RECURRENT gradient flow runs in the serial loop; gradients that are plain sums over
@@ -13,6 +16,24 @@
 #include "attn_common.h"
 
 namespace {
+
+// where the loop kernels take the keys from (see the header comment)
+enum { KEYS_GLOBAL = 0, KEYS_LDS = 1, KEYS_GLOBAL_BF16 = 2 };
+template <int KM>
+__device__ __forceinline__ void loop_key4(const float* __restrict__ kglob, const uint16_t* __restrict__ klds, int tt, int U,
+                                          int d0, bool act, float (&kk)[NQ]) {
+  load_key4<KM == KEYS_LDS>(kglob, klds, tt, U, d0, act, kk);
+  if (KM == KEYS_GLOBAL_BF16) {
+#pragma unroll
+    for (int qq = 0; qq < NQ; ++qq) kk[qq] = bf2f(f2bf(kk[qq]));
+  }
+}
+template <int KM>
+__device__ __forceinline__ float loop_key1(const float* __restrict__ kglob, const uint16_t* __restrict__ klds, int tt, int U,
+                                           int d, bool act) {
+  const float k = load_key1<KM == KEYS_LDS>(kglob, klds, tt, U, d, act);
+  return KM == KEYS_GLOBAL_BF16 ? bf2f(f2bf(k)) : k;
+}
 
 struct SmemF {   // forward LDS carve (in floats); bf16 keys follow at kofs
   int vec, z, q, pq, aprev, alA, alB, e1, e2, fl, Fs, bFs, partial, kofs, total;
@@ -29,9 +50,12 @@ __host__ __device__ inline SmemF carve_fwd(int A, int CT, int UQ, int Ti, int F,
   return s;
 }
 
-template <int F, bool KLDS>
+// GEN: the first-mechanism options of satt_attn_rnn_params (att1_mode, cumulative, agentW), selected by block-uniform
+// flags outside the row loops; GEN == false is the plain ForwardAttention loop.
+template <int F, int KM, bool GEN>
 __global__ __launch_bounds__(ANT) void attn_rnn_fwd_k(const satt_attn_rnn_params p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  constexpr bool KLDS = KM == KEYS_LDS;
   const int A = p.A, G = 4 * A, V1 = p.V1, V2 = p.V2, CT = V1 + V2, U1 = p.U1, U2 = p.U2, UQ = U1 + U2;
   const int Ti = p.Ti, Td = p.Td, KW = p.kernel, PL = (KW - 1) / 2;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
@@ -87,6 +111,13 @@ __global__ __launch_bounds__(ANT) void attn_rnn_fwd_k(const satt_attn_rnn_params
   float c = 0.f, h = 0.f;
   float* alp = alA;  // alpha_{t-1}
   float* aln = alB;  // alpha_t
+  // location_sensitive: the alignments are the softmax probabilities; cumulative: the location conv reads their running sum;
+  // transition agent: u of the recursion is predicted per step (it lives in wave 0, which runs the recursion)
+  const bool unit_w = GEN && p.att1_mode == 1;
+  const bool cumul = GEN && p.cumulative != 0;
+  const bool agent = GEN && p.agentW != nullptr && !unit_w;
+  const float agent_b = agent ? p.agentb[0] : 0.f;
+  float uc = 0.5f;
   __syncthreads();
 
   PROF_DECL;
@@ -162,8 +193,8 @@ __global__ __launch_bounds__(ANT) void attn_rnn_fwd_k(const satt_attn_rnn_params
           float acc = 0.f, acc2 = 0.f;
           if (tt < len) {
             float kk[NQ];
-            load_key4<KLDS>(keys1, K1s, tt, U1, d0, actU, kk);
-            const float k2 = load_key1<KLDS>(keys2, K2s, tt, U2, lane, lane < U2);
+            loop_key4<KM>(keys1, K1s, tt, U1, d0, actU, kk);
+            const float k2 = loop_key1<KM>(keys2, K2s, tt, U2, lane, lane < U2);
             float f[F];
 #pragma unroll
             for (int k = 0; k < F; ++k) f[k] = fl[tt * F + k];
@@ -191,7 +222,34 @@ __global__ __launch_bounds__(ANT) void attn_rnn_fwd_k(const satt_attn_rnn_params
     __syncthreads();
     PROF(5);
     // (6) masked softmax (+ forward-attention recursion for mechanism 1)
-    if (wave == 0) {
+    if (GEN && wave == 0) {
+      wave_softmax(e1, len, Ti, lane);
+      float* o1 = p.align1 + bt * Ti;
+      float* oa = p.a1 + bt * Ti;
+      if (unit_w) {
+        for (int tt = lane; tt < Ti; tt += 64) { const float a = e1[tt]; aln[tt] = a; o1[tt] = a; oa[tt] = a; }
+      } else {
+        float s = 0.f;
+        for (int tt = lane; tt < Ti; tt += 64) {
+          const float w = (1.f - uc) * alp[tt] + uc * (tt > 0 ? alp[tt - 1] : 0.f) + 1e-7f;
+          const float v = w * e1[tt];
+          aln[tt] = v; s += v;
+        }
+        s = wave_sum(s);
+        const float inv = 1.f / s;
+        for (int tt = lane; tt < Ti; tt += 64) {
+          const float v = aln[tt] * inv;
+          aln[tt] = v; o1[tt] = v; oa[tt] = e1[tt];
+        }
+      }
+      // next step's location-conv input; its running sum is saved for the deferred filter gradient
+      float* oc = cumul ? p.acum + bt * Ti : nullptr;
+      for (int tt = lane; tt < Ti; tt += 64) {
+        const float an = cumul ? aprev[tt] + e1[tt] : e1[tt];
+        aprev[tt] = an;
+        if (cumul) oc[tt] = an;
+      }
+    } else if (wave == 0) {
       wave_softmax(e1, len, Ti, lane);
       float s = 0.f;
       for (int tt = lane; tt < Ti; tt += 64) {
@@ -262,13 +320,24 @@ __global__ __launch_bounds__(ANT) void attn_rnn_fwd_k(const satt_attn_rnn_params
     }
     { float* tmp = alp; alp = aln; aln = tmp; }
     __syncthreads();
+    // transition agent: u of the NEXT step from this step's first context (complete behind the barrier above) and processed
+    // query; ustate[t] = the u used at step t.  The barrier behind it keeps the other waves out of the next step until wave 0
+    // has read vec and pq (block-uniform condition).
+    if (agent && wave == 0) {
+      float ua = 0.f;
+      for (int i = lane; i < V1; i += 64) ua += vec[i] * p.agentW[i];
+      for (int d = lane; d < U1; d += 64) ua += pq[d] * p.agentW[V1 + d];
+      uc = sigmoidf_(wave_sum(ua) + agent_b);
+      if (lane == 0 && t + 1 < Td) p.ustate[(size_t)b * Td + t + 1] = uc;
+    }
+    if (agent) __syncthreads();
     PROF(7);
   }
   PROF_STORE(0);
 }
 
 struct SmemB {
-  int dz, dvec, dq, dpq, pqv, dctx, alprev, a, al, a2, dal, da2, de1, dac, dalc, fl, dfl, Fs, partial, kofs, total;
+  int dz, dvec, dq, dpq, pqv, dctx, alprev, a, al, a2, dal, da2, de1, dac, dalc, fl, dfl, Fs, partial, du, kofs, total;
 };
 __host__ __device__ inline SmemB carve_bwd(int A, int CT, int UQ, int Ti, int F, int KW, int U1, int U2, bool klds) {
   auto u = [](int x) { return (x + 3) & ~3; };
@@ -280,14 +349,16 @@ __host__ __device__ inline SmemB carve_bwd(int A, int CT, int UQ, int Ti, int F,
   s.de1 = o; o += T4; s.dac = o; o += T4; s.dalc = o; o += T4;
   s.fl = o; o += u(Ti * F); s.dfl = o; o += u(Ti * F); s.Fs = o; o += u(KW * F);
   s.partial = o; o += ANT * 8;
+  s.du = o; o += 4;                 // transition agent: d u carried from step t+1 to step t
   s.kofs = o; if (klds) o += u((Ti * (U1 + U2) + 1) / 2);
   s.total = o;
   return s;
 }
 
-template <int F, bool KLDS>
+template <int F, int KM, bool GEN>
 __global__ __launch_bounds__(ANT) void attn_rnn_bwd_k(const satt_attn_rnn_bwd_params pb) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  constexpr bool KLDS = KM == KEYS_LDS;
   const satt_attn_rnn_params& p = pb.f;
   const int A = p.A, G = 4 * A, V1 = p.V1, V2 = p.V2, CT = V1 + V2, U1 = p.U1, U2 = p.U2, UQ = U1 + U2;
   const int Ti = p.Ti, Td = p.Td, KW = p.kernel, PL = (KW - 1) / 2;
@@ -312,8 +383,12 @@ __global__ __launch_bounds__(ANT) void attn_rnn_bwd_k(const satt_attn_rnn_bwd_pa
   float* dfl = smem + L.dfl;        // [Ti*F]
   float* Fs = smem + L.Fs;          // [KW*F]
   float* partial = smem + L.partial;  // [ANT*8]
+  float* du_s = smem + L.du;        // [1]  d u_{t+1} (GEN, transition agent)
   uint16_t* K1s = reinterpret_cast<uint16_t*>(smem + L.kofs);
   uint16_t* K2s = K1s + Ti * U1;
+  const bool unit_w = GEN && p.att1_mode == 1;      // location_sensitive: d align1 goes straight into the softmax backward
+  const bool cumul = GEN && p.cumulative != 0;      // the conv input of step t feeds every later step: its gradient accumulates
+  const bool agent = GEN && p.agentW != nullptr && !unit_w;
 
   const int len = (int)p.lengths[b];
   const uint32_t seed = p.seed ? *p.seed : 0u;
@@ -345,12 +420,20 @@ __global__ __launch_bounds__(ANT) void attn_rnn_bwd_k(const satt_attn_rnn_bwd_pa
     for (int i = tid; i < len * U2; i += ANT) K2s[i] = f2bf(keys2[i]);
   }
   float dc_state = 0.f, dh_state = 0.f;
+  if (GEN && tid == 0) du_s[0] = 0.f;
   __syncthreads();
 
   PROF_DECL;
   for (int t = Td - 1; t >= 0; --t) {
     PROF(0);
     const size_t bt = (size_t)b * Td + t;
+    // transition agent: u of this step's recursion, and d z of this step's prediction of u_{t+1}
+    float ut = 0.5f, dzu = 0.f;
+    if (agent) {
+      if (t > 0) ut = p.ustate[bt];
+      if (t + 1 < Td) { const float un = p.ustate[bt + 1]; dzu = du_s[0] * un * (1.f - un); }
+      if (tid == 0) pb.dz[bt] = dzu;
+    }
     // (a) load forward state of this step, total context gradient
     for (int i = tid; i < Ti; i += ANT) {
       alprev[i] = t > 0 ? p.align1[(bt - 1) * Ti + i] : (i == 0 ? 1.f : 0.f);
@@ -364,7 +447,8 @@ __global__ __launch_bounds__(ANT) void attn_rnn_bwd_k(const satt_attn_rnn_bwd_pa
     }
     if (tid < UQ) pqv[tid] = p.pq[bt * UQ + tid];
     if (tid < CT) {
-      const float g = dout[(size_t)t * OW + A + tid] + dvec[tid];
+      float g = dout[(size_t)t * OW + A + tid] + dvec[tid];
+      if (agent && tid < V1) g += dzu * p.agentW[tid];          // d ctx1 through the agent's Dense
       dctx[tid] = g;
       pb.dctx[bt * CT + tid] = g;
     }
@@ -414,7 +498,37 @@ __global__ __launch_bounds__(ANT) void attn_rnn_bwd_k(const satt_attn_rnn_bwd_pa
     __syncthreads();
     PROF(2);
     // (c) forward-attention recursion + softmax backward (wave 0), additive softmax backward (wave 1)
-    if (wave == 0) {
+    if (GEN && wave == 0) {
+      float s2 = 0.f;
+      if (unit_w) {
+        for (int tt = lane; tt < Ti; tt += 64) {
+          const float da = dal[tt] + dac[tt];              // total d a_t
+          dal[tt] = 0.f;                                   // d w: nothing flows back into alpha_{t-1}
+          de1[tt] = da;
+          s2 += da * a[tt];
+        }
+      } else {
+        float S = 0.f, s1 = 0.f;
+        for (int tt = lane; tt < Ti; tt += 64) {
+          const float w = (1.f - ut) * alprev[tt] + ut * (tt > 0 ? alprev[tt - 1] : 0.f) + 1e-7f;
+          S += w * a[tt];
+          s1 += dal[tt] * al[tt];
+        }
+        S = wave_sum(S); s1 = wave_sum(s1);
+        const float invS = 1.f / S;
+        for (int tt = lane; tt < Ti; tt += 64) {
+          const float w = (1.f - ut) * alprev[tt] + ut * (tt > 0 ? alprev[tt - 1] : 0.f) + 1e-7f;
+          const float dalp = (dal[tt] - s1) * invS;       // d alpha'
+          const float da = dalp * w + dac[tt];             // total d a_t
+          dal[tt] = dalp * a[tt];                          // d w
+          de1[tt] = da;
+          s2 += da * a[tt];
+        }
+      }
+      s2 = wave_sum(s2);
+      float* g1 = pb.de1 + bt * Ti;
+      for (int tt = lane; tt < Ti; tt += 64) { const float v = a[tt] * (de1[tt] - s2); de1[tt] = v; g1[tt] = v; }
+    } else if (wave == 0) {
       float S = 0.f, s1 = 0.f;
       for (int tt = lane; tt < Ti; tt += 64) {
         const float w = 0.5f * alprev[tt] + 0.5f * (tt > 0 ? alprev[tt - 1] : 0.f) + 1e-7f;
@@ -444,8 +558,18 @@ __global__ __launch_bounds__(ANT) void attn_rnn_bwd_k(const satt_attn_rnn_bwd_pa
     }
     __syncthreads();
     PROF(3);
-    // new carry for alpha_{t-1}: d alpha_prev[s] = 0.5*dw[s] + 0.5*dw[s+1]
-    for (int i = tid; i < Ti; i += ANT) dalc[i] = 0.5f * dal[i] + 0.5f * (i + 1 < Ti ? dal[i + 1] : 0.f);
+    // new carry for alpha_{t-1}: d alpha_prev[s] = (1 - u)*dw[s] + u*dw[s+1]  (u = 0.5 without the transition agent)
+    if (GEN) {
+      for (int i = tid; i < Ti; i += ANT) dalc[i] = (1.f - ut) * dal[i] + ut * (i + 1 < Ti ? dal[i + 1] : 0.f);
+      if (agent && wave == AW - 1) {      // d u_t = sum d w * d w / d u (every thread read du_s[0] at the top of the step)
+        float sdu = 0.f;
+        for (int tt = lane; tt < Ti; tt += 64) sdu += dal[tt] * ((tt > 0 ? alprev[tt - 1] : 0.f) - alprev[tt]);
+        sdu = wave_sum(sdu);
+        if (lane == 0) du_s[0] = sdu;
+      }
+    } else {
+      for (int i = tid; i < Ti; i += ANT) dalc[i] = 0.5f * dal[i] + 0.5f * (i + 1 < Ti ? dal[i + 1] : 0.f);
+    }
     // (d) energy backward (recurrent part only): d pq and d location-features
     {
       float pqb[NQ], dpqa[NQ];
@@ -470,7 +594,7 @@ __global__ __launch_bounds__(ANT) void attn_rnn_bwd_k(const satt_attn_rnn_bwd_pa
 #pragma unroll
             for (int k = 0; k < F; ++k) f[k] = fl[tt * F + k];
             float kk[NQ];
-            load_key4<KLDS>(keys1, K1s, tt, U1, d0, actU, kk);
+            loop_key4<KM>(keys1, K1s, tt, U1, d0, actU, kk);
 #pragma unroll
             for (int qq = 0; qq < NQ; ++qq) {
               float lf = 0.f;
@@ -483,7 +607,7 @@ __global__ __launch_bounds__(ANT) void attn_rnn_bwd_k(const satt_attn_rnn_bwd_pa
               for (int k = 0; k < F; ++k) dfp[u * F + k] += g * Ur[qq][k];
             }
             if (lane < U2) {
-              const float th2 = tanhf_(load_key1<KLDS>(keys2, K2s, tt, U2, lane, true) + pq2);
+              const float th2 = tanhf_(loop_key1<KM>(keys2, K2s, tt, U2, lane, true) + pq2);
               dpq2a += da2[tt] * v2r * (1.f - th2 * th2);
             }
           }
@@ -508,6 +632,7 @@ __global__ __launch_bounds__(ANT) void attn_rnn_bwd_k(const satt_attn_rnn_bwd_pa
       float s = 0.f;
 #pragma unroll
       for (int w = 0; w < AW; ++w) s += partial[w * UQ + tid];
+      if (agent && tid < U1) s += dzu * p.agentW[V1 + tid];     // d pq1 through the agent's Dense
       dpq[tid] = s;
       pb.dpq[bt * UQ + tid] = s;
     }
@@ -521,7 +646,7 @@ __global__ __launch_bounds__(ANT) void attn_rnn_bwd_k(const satt_attn_rnn_bwd_pa
           for (int k = 0; k < F; ++k) g += dfl[tt * F + k] * Fs[jj * F + k];
         }
       }
-      dac[s] = g;
+      dac[s] = cumul ? dac[s] + g : g;
     }
     __syncthreads();
     PROF(5);
@@ -814,8 +939,10 @@ __global__ __launch_bounds__(256) void attn_param_grads_finish_k(const double* _
 
 inline int check(const satt_attn_rnn_params& p, bool loop = true) {
   if (p.B <= 0 || p.Td <= 0 || p.Ti <= 0) return SATT_E_BADARG;
-  // location_sensitive / cumulative: cluster kernels only (the deferred parameter gradients do not depend on either)
-  if (loop && (p.att1_mode != 0 || p.cumulative != 0 || p.agentW != nullptr)) return SATT_E_UNSUPPORTED;
+  if (loop) {     // (the deferred parameter gradients do not depend on the first-mechanism options)
+    if (p.att1_mode < 0 || p.att1_mode > 1 || (p.cumulative && !p.acum)) return SATT_E_BADARG;
+    if (p.agentW && (!p.agentb || !p.ustate)) return SATT_E_BADARG;
+  }
   if (p.filters != 5) return SATT_E_UNSUPPORTED;
   if (p.U1 > 64 * NQ || p.V1 > 64 * NQ || p.U2 > 64 || p.V2 > 64 || p.U1 % 4 || p.V1 % 4) return SATT_E_UNSUPPORTED;
   if ((4 * p.A) % 8 || (p.U1 + p.U2) % 8 || (p.V1 + p.V2 + p.A) % 8 || p.A % 8) return SATT_E_UNSUPPORTED;
@@ -824,58 +951,86 @@ inline int check(const satt_attn_rnn_params& p, bool loop = true) {
   return SATT_OK;
 }
 
+constexpr size_t LDS_LIMIT = 160 * 1024;
+inline size_t lds_fwd(const satt_attn_rnn_params& p, bool klds) {
+  return sizeof(float) * carve_fwd(p.A, p.V1 + p.V2, p.U1 + p.U2, p.Ti, 5, p.kernel, p.U1, p.U2, klds).total;
+}
+inline size_t lds_bwd(const satt_attn_rnn_params& p, bool klds) {
+  return sizeof(float) * carve_bwd(p.A, p.V1 + p.V2, p.U1 + p.U2, p.Ti, 5, p.kernel, p.U1, p.U2, klds).total;
+}
+// Where BOTH loop kernels of a problem take the keys from: the bf16 image in LDS if it fits beside the forward AND the backward
+// carve, global keys rounded on load otherwise - a function of the problem alone, so the two passes (and the deferred
+// gradients, which round the same way) always see the same keys.  SATT_ATTN_RNN_GLOBAL_KEYS (tests; read at every call) forces
+// the global form.  Exact parity mode (keys_lds_bf16 == 0): fp32 keys from global.
+inline int key_mode(const satt_attn_rnn_params& p) {
+  if (!p.keys_lds_bf16) return KEYS_GLOBAL;
+  if (getenv("SATT_ATTN_RNN_GLOBAL_KEYS") != nullptr) return KEYS_GLOBAL_BF16;
+  return lds_fwd(p, true) <= LDS_LIMIT && lds_bwd(p, true) <= LDS_LIMIT ? KEYS_LDS : KEYS_GLOBAL_BF16;
+}
+inline bool general(const satt_attn_rnn_params& p) { return p.att1_mode != 0 || p.cumulative != 0 || p.agentW != nullptr; }
+// the acceptance rule of satt_attn_rnn_fwd (fwd), satt_attn_rnn_bwd (bwd) and satt_attn_rnn_check (both): each launcher refuses
+// on its OWN carve only - a forward-only caller is not held to the larger backward carve
+inline int check_loop(const satt_attn_rnn_params& p, bool fwd, bool bwd) {
+  if (p.teach1 || p.teach2) return SATT_E_UNSUPPORTED;   // forced alignments: cluster kernels only
+  const int rc = check(p);
+  if (rc) return rc;
+  const bool klds = key_mode(p) == KEYS_LDS;
+  if ((fwd && lds_fwd(p, klds) > LDS_LIMIT) || (bwd && lds_bwd(p, klds) > LDS_LIMIT)) return SATT_E_UNSUPPORTED;
+  return SATT_OK;
+}
+
+template <typename K, typename P>
+inline void launch_loop(K kernel, const P& prm, int B, size_t smem, hipStream_t s) {
+  if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(ANT), smem, s, prm);
+}
+template <bool GEN>
+inline void launch_fwd(const satt_attn_rnn_params& p, int km, size_t smem, hipStream_t s) {
+  if (km == KEYS_LDS) launch_loop(attn_rnn_fwd_k<5, KEYS_LDS, GEN>, p, p.B, smem, s);
+  else if (km == KEYS_GLOBAL_BF16) launch_loop(attn_rnn_fwd_k<5, KEYS_GLOBAL_BF16, GEN>, p, p.B, smem, s);
+  else launch_loop(attn_rnn_fwd_k<5, KEYS_GLOBAL, GEN>, p, p.B, smem, s);
+}
+template <bool GEN>
+inline void launch_bwd(const satt_attn_rnn_bwd_params& q, int km, size_t smem, hipStream_t s) {
+  if (km == KEYS_LDS) launch_loop(attn_rnn_bwd_k<5, KEYS_LDS, GEN>, q, q.f.B, smem, s);
+  else if (km == KEYS_GLOBAL_BF16) launch_loop(attn_rnn_bwd_k<5, KEYS_GLOBAL_BF16, GEN>, q, q.f.B, smem, s);
+  else launch_loop(attn_rnn_bwd_k<5, KEYS_GLOBAL, GEN>, q, q.f.B, smem, s);
+}
+
 }  // namespace
+
+extern "C" int satt_attn_rnn_check(const satt_attn_rnn_params* pp) {
+  if (!pp) return SATT_E_BADARG;
+  return check_loop(*pp, true, true);
+}
 
 extern "C" int satt_attn_rnn_fwd(const satt_attn_rnn_params* pp, void* stream) {
   if (!pp) return SATT_E_BADARG;
-  if (pp->teach1 || pp->teach2) return SATT_E_UNSUPPORTED;   // forced alignments: cluster kernels only
-  int rc = check(*pp);
+  int rc = check_loop(*pp, true, false);
   if (rc) return rc;
   satt_attn_rnn_params p = *pp;
   single_source_fixup(p);
-  const int CT = p.V1 + p.V2, UQ = p.U1 + p.U2;
-  const bool klds = p.keys_lds_bf16 != 0;
-  const size_t smem = sizeof(float) * carve_fwd(p.A, CT, UQ, p.Ti, 5, p.kernel, p.U1, p.U2, klds).total;
-  if (smem > 160 * 1024) return SATT_E_UNSUPPORTED;
+  const int km = key_mode(p);
+  const size_t smem = lds_fwd(p, km == KEYS_LDS);
   hipStream_t s = (hipStream_t)stream;
-  if (klds) {
-    if (smem > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)attn_rnn_fwd_k<5, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)smem);
-    hipLaunchKernelGGL((attn_rnn_fwd_k<5, true>), dim3(p.B), dim3(ANT), smem, s, p);
-  } else {
-    if (smem > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)attn_rnn_fwd_k<5, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)smem);
-    hipLaunchKernelGGL((attn_rnn_fwd_k<5, false>), dim3(p.B), dim3(ANT), smem, s, p);
-  }
+  if (general(p)) launch_fwd<true>(p, km, smem, s);
+  else launch_fwd<false>(p, km, smem, s);
   SATT_LAUNCH_CHECK();
   return SATT_OK;
 }
 
 extern "C" int satt_attn_rnn_bwd(const satt_attn_rnn_bwd_params* pp, void* stream) {
   if (!pp) return SATT_E_BADARG;
-  int rc = check(pp->f);
+  int rc = check_loop(pp->f, false, true);
   if (rc) return rc;
+  if (pp->f.agentW && !pp->dz) return SATT_E_BADARG;
   satt_attn_rnn_bwd_params q = *pp;
   single_source_fixup(q.f);
-  const satt_attn_rnn_params& p = q.f;
-  const int CT = p.V1 + p.V2, UQ = p.U1 + p.U2;
-  const bool klds = p.keys_lds_bf16 != 0;
-  const size_t smem = sizeof(float) * carve_bwd(p.A, CT, UQ, p.Ti, 5, p.kernel, p.U1, p.U2, klds).total;
-  if (smem > 160 * 1024) return SATT_E_UNSUPPORTED;
+  const int km = key_mode(q.f);
+  const size_t smem = lds_bwd(q.f, km == KEYS_LDS);
   hipStream_t s = (hipStream_t)stream;
-  if (klds) {
-    if (smem > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)attn_rnn_bwd_k<5, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)smem);
-    hipLaunchKernelGGL((attn_rnn_bwd_k<5, true>), dim3(p.B), dim3(ANT), smem, s, q);
-  } else {
-    if (smem > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)attn_rnn_bwd_k<5, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)smem);
-    hipLaunchKernelGGL((attn_rnn_bwd_k<5, false>), dim3(p.B), dim3(ANT), smem, s, q);
-  }
+  if (general(q.f)) launch_bwd<true>(q, km, smem, s);
+  else launch_bwd<false>(q, km, smem, s);
   SATT_LAUNCH_CHECK();
   return SATT_OK;
 }

@@ -1190,7 +1190,7 @@ class Engine:
             ustate = self._e(B, Td)
             ap.agentW, ap.agentb, ap.ustate = P["dec.att1.Wa"].data_ptr(), P["dec.att1.ba"].data_ptr(), ustate.data_ptr()
         Ca = ops.attn_cluster_size(ap) if self.use_clusters else 0
-        if not Ca and (c.attention != "forward" or c.cumulative_weights or c.transition_agent):
+        if not Ca and (c.attention != "forward" or c.cumulative_weights or c.transition_agent) and not ops.attn_rnn_accepts(ap):
             from .modules.attentions import UnsupportedConfiguration
             raise UnsupportedConfiguration("attention=%s cumulative_weights=%s transition_agent=%s needs the cluster attention "
                                            "kernels, which do not accept this problem (B=%d, Ti=%d)"

@@ -815,6 +815,11 @@ def attn_rnn_bwd(fwd_params, **kw):
     _lib.check(_lib.lib().satt_attn_rnn_bwd(C.byref(pb), _s()), "attn_rnn_bwd")
 
 
+def attn_rnn_accepts(fwd_params):
+    """True if the single-workgroup attention kernels take this problem (satt_attn_rnn_check: host-only, no launch)"""
+    return _lib.lib().satt_attn_rnn_check(C.byref(fwd_params)) == 0
+
+
 ATTN_CLUSTER_SIZES = (4, 8, 2)  # candidate workgroups per sample in order of preference (B * C <= 256; 4 leaves
                                 # half of the CUs to the LSTM kernels that run concurrently on the other streams)
 
