@@ -732,7 +732,7 @@ int satt_dec_attention(const satt_dec_attention_params* p, void* stream);
  * Same math and the same buffers as the launch-per-layer path above (the caller may switch between the two from one LAUNCH to the
  * next: recurrent state, contexts, location input and forward variable are handed over at the last step of a launch).  Supported
  * (otherwise satt_dec_mega_supported() == 0 and the caller uses satt_dec_linear / satt_dec_attention / satt_dec_self_attn): the
- * dual-source model with a plain two-layer pre-net, no transition agent, no forced alignments, bf16 weight shadows, B <= 2,
+ * dual-source model with a two-layer pre-net - plain, or with MultiSpeakerPreNet as its first layer (sproj below) -, no transition agent, no forced alignments, bf16 weight shadows, B <= 2,
  * Ti <= 256, A = D = Ds = 256, one causal self-attention hop of 2 or 4 heads.  Replaces, per step: reference
  * modules/module.py:762-778, modules/rnn_wrappers.py:47-124,188-214, modules/forward_attention.py:88-136,
  * modules/helpers.py:58-166 (mirrors). */
@@ -772,10 +772,25 @@ typedef struct {
   int* flag;                              /* stop flag (number of steps taken when the stop rule fired) or NULL */
   unsigned int* err;                      /* sticky error word (an exchange timed out): zeroed by the caller once */
   int nsteps;
+  /* multi-speaker pre-net (MultiSpeakerPreNet, reference modules/multi_speaker_modules.py:27-32; all three NULL: the plain
+   * pre-net).  Its first layer is  relu((relu(x Wp0 + bp0) + sproj) Wp02 + bp02):  sproj [B][P0] fp32 is the speaker term
+   * softsign(s Ws + bs), constant over the utterance and computed by the caller (the buffer is read at the start of every
+   * launch: the caller may rewrite it in place between utterances); Wp02 bf16 [P0][P0] and bp02 [P0] are the layer's second
+   * Dense.  With the folded feedback, sproj is added behind the ReLU of the folded form too.  One more split product and one
+   * more exchange per step than the plain pre-net; the kernels of the plain pre-net are not touched by it. */
+  const uint16_t* Wp02; const float* bp02;
+  const float* sproj;
 } satt_dec_mega_params;
 int satt_dec_mega_supported(const satt_dec_mega_params* p);
 int64_t satt_dec_mega_scratch_floats(int B, int heads, int head_dim);
 int satt_dec_mega(const satt_dec_mega_params* p, void* stream);
+/* which instantiation of the kernel satt_dec_mega launches for the block (diagnostics, tests): an OR of the bits below, or -1
+ * where satt_dec_mega_supported() == 0 */
+#define SATT_MEGA_VAR_TABLES_LDS 1   /* context tables resident in LDS (B = 1, Ti <= 112) */
+#define SATT_MEGA_VAR_LJ 2           /* the dimensions of examples/ljspeech/self-attention-tacotron.json as compile-time constants */
+#define SATT_MEGA_VAR_SPEAKER 4      /* multi-speaker pre-net (sproj != NULL) */
+#define SATT_MEGA_VAR_TWO_SAMPLES 8  /* B = 2 */
+int satt_dec_mega_variant(const satt_dec_mega_params* p);
 /* new query row of the causal self-attention over the K|V|Q cache kvq [B,Td,3D] (row *step must hold K|V|Q of the step):
  * out [B,D] = softmax(q K^T * scale over rows 0..*step) V, heads side by side (modules/self_attention.py:45-65) */
 int satt_dec_self_attn(const float* kvq, float* out, const int* step, int B, int Td, int D, int heads, float scale,

@@ -124,7 +124,8 @@ class DecMegaParams(C.Structure):
                                            "keys1", "values1", "keys2", "values2",
                                            "ca", "ha", "c1", "h1", "c2", "h2", "a_state", "alpha_state", "ctx", "yout", "tin",
                                            "align1", "align2", "kvq", "part", "ctab", "Wfh", "Wfl", "bfb", "step", "flag", "err")] +
-                [("nsteps", C.c_int)])
+                [("nsteps", C.c_int)] +
+                [(n, C.c_void_p) for n in ("Wp02", "bp02", "sproj")])      # multi-speaker pre-net (NULL: the plain one)
 
 # name -> (restype, argtypes); must list EVERY symbol declared in include/satt_hip.h
 _P = C.c_void_p
@@ -241,6 +242,7 @@ SIGNATURES = {
     "satt_dec_mega_supported": (_I, [C.POINTER(DecMegaParams)]),
     "satt_dec_mega_scratch_floats": (c_i64, [_I, _I, _I]),
     "satt_dec_mega": (_I, [C.POINTER(DecMegaParams), _P]),
+    "satt_dec_mega_variant": (_I, [C.POINTER(DecMegaParams)]),
     "satt_dec_self_attn": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "satt_l2_reg": (_I, [_P, _P, _P, _I, _F, _P, _P, _P]),
     "satt_sumsq": (_I, [_P, c_i64, _P, _P]),

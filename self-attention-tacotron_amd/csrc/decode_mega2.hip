@@ -7,6 +7,7 @@
 //     for a write-through acknowledgement and there is no separate barrier.  Eleven exchanges per step:
 //       p0 -> p1 -> [attention LSTM] hq -> pq -> [energies] e1 | e2 -> [softmax, LSTM 1] h1n -> [LSTM 2] dout ->
 //       [K|V|Q] row t -> [cached self-attention partials] -> [merge, output transform] tr -> [projection] y
+//     (the multi-speaker pre-net, template flag SPK, has a twelfth: p0 -> p02 -> p1)
 //   * the CONTEXTS are never formed inside a step: what the cells need of them is  ctx W_c = sum_r alpha_r (values_r W_c), and
 //     values W_c (`ctab`: [B][Ti][4][1024], built once per utterance by the caller with one GEMM per table) turns the 128 KB stream of
 //     the value rows per workgroup per step into 2 x 2 x Ti x 32 floats and the [K x 32] slices of the two cells lose their 320
@@ -67,12 +68,13 @@ __device__ __forceinline__ float lane_xor32(float v, int lane) { return __int_as
 __device__ __forceinline__ float lane_get(float v, int src) { return __int_as_float(__builtin_amdgcn_ds_bpermute(src << 2, __float_as_int(v))); }
 
 // granule layout (u64 words) per sample
-struct GL { int p0, p1, hq, pq, e, h1, dout, kvq, part, tr, y, hs, total; };
-__host__ __device__ inline GL gl_of(int hd) {
+struct GL { int p0, p1, hq, pq, e, h1, dout, kvq, part, tr, y, hs, p02, total; };
+__host__ __device__ inline GL gl_of(int hd, bool spk = false) {
   GL g; int o = 0;
   g.p0 = o; o += M2N; g.p1 = o; o += M2N; g.hq = o; o += M2N; g.pq = o; o += M2N; g.e = o; o += 2 * M2TI; g.h1 = o; o += M2N; g.dout = o; o += M2N;
   g.kvq = o; o += 3 * M2N; g.part = o; o += M2G * (hd + 2); g.tr = o; o += M2N; g.y = o; o += M2NO;
   g.hs = o; o += M2G;            // placement handshake of a launch (sample 0's area): the XCC id of every workgroup
+  g.p02 = o; if (spk) o += M2N;  // multi-speaker pre-net only (behind everything else: the plain pre-net's layout is what it was)
   g.total = o;
   return g;
 }
@@ -153,9 +155,11 @@ __device__ __forceinline__ float slice_total(const float* src, int lane) {
 // ---- split layer: the workgroup's 8 columns [8 wg, 8 wg + 8) of act(x W + bias) (+ res); thread k < 256 (waves 0..3: K <= 256)
 // holds row k of them; the publishing wave finishes and publishes granules dst[b * bs + 8 wg + j] (columns >= N are not published).
 // bias8: LDS (a global load here would sit on the step's dependency chain).  rs is free again after the caller's next barrier.
-template <int NB>
+// EX (multi-speaker pre-net): the publishing lane's register `ex` is added 1: behind the activation (the speaker term), 2: in front
+// of it (a bias that has no place in LDS; bias8 then points at zeros).
+template <int NB, int EX = 0>
 __device__ __forceinline__ void split_mul(uint4 wr, const float* x, int xs_, int N, const float* bias8, int act, const float* res, int rs_,
-                                          u64* dst, int64_t bs, uint32_t tag, int wg, int B, float* rs, int tid, bool sx) {
+                                          u64* dst, int64_t bs, uint32_t tag, int wg, int B, float* rs, int tid, bool sx, float ex = 0.f) {
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (wave < 4) {
     float xv[NB];
@@ -178,9 +182,11 @@ __device__ __forceinline__ void split_mul(uint4 wr, const float* x, int xs_, int
     const float s0 = rs[(b * 4 + 0) * 8 + j], s1 = rs[(b * 4 + 1) * 8 + j], s2 = rs[(b * 4 + 2) * 8 + j], s3 = rs[(b * 4 + 3) * 8 + j];
     const float bj = bias8[j], rv = res ? res[b * rs_ + min(n, M2N - 1)] : 0.f;
     float s = ((s0 + s1) + (s2 + s3)) + bj;
+    if constexpr (EX == 2) s += ex;
     if (act == SATT_ACT_RELU) s = fmaxf(s, 0.f);
     else if (act == SATT_ACT_TANH) s = tanhf_(s);
     s += rv;
+    if constexpr (EX == 1) s += ex;
     if (b < B && n < N) gput(dst + b * bs + n, tag, s, sx);
   }
 }
@@ -193,10 +199,11 @@ __device__ __forceinline__ uint4 split_fill(const uint16_t* __restrict__ W, int 
 
 // ---- folded feedback (r6): from the SAME vector x (the output transform's result) the workgroup's 8 columns of the mel | stop
 // projection (published as y with `tag`) AND of relu(x Wf + bf) = the first pre-net layer of the NEXT step (published as p0 with
-// tag + 1; Wf as bf16 hi + lo).  One barrier; wave PUTW publishes y, wave AUXW p0.
-template <int NB>
+// tag + 1; Wf as bf16 hi + lo).  One barrier; wave PUTW publishes y, wave AUXW p0.  SPK (multi-speaker pre-net): p0 is
+// relu(x Wf + bf) + spk, the speaker term of the publishing lane's (sample, column).
+template <int NB, bool SPK = false>
 __device__ __forceinline__ void split_mul_fb(uint4 wy, uint4 wh, uint4 wl, const float* x, int NO_, int P0_, const float* by8, const float* bf8,
-                                             u64* dy, u64* dp, int64_t bs, uint32_t tag, int wg, float* rs, int tid, bool sx) {
+                                             u64* dy, u64* dp, int64_t bs, uint32_t tag, int wg, float* rs, int tid, bool sx, float spk = 0.f) {
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (wave < 4) {
     float xv[NB];
@@ -219,7 +226,11 @@ __device__ __forceinline__ void split_mul_fb(uint4 wy, uint4 wh, uint4 wl, const
     const float* r = rs + (wave == AUXW ? NB * 32 : 0);
     const float s0 = r[(b * 4 + 0) * 8 + j], s1 = r[(b * 4 + 1) * 8 + j], s2 = r[(b * 4 + 2) * 8 + j], s3 = r[(b * 4 + 3) * 8 + j];
     float s = ((s0 + s1) + (s2 + s3)) + (wave == AUXW ? bf8[j] : by8[j]);
-    if (wave == AUXW) { s = fmaxf(s, 0.f); if (n < P0_) gput(dp + b * bs + n, tag + 1u, s, sx); }
+    if (wave == AUXW) {
+      s = fmaxf(s, 0.f);
+      if constexpr (SPK) s += spk;
+      if (n < P0_) gput(dp + b * bs + n, tag + 1u, s, sx);
+    }
     else if (n < NO_) gput(dy + b * bs + n, tag, s, sx);
   }
 }
@@ -312,7 +323,11 @@ __host__ __device__ inline size_t mega2_lds_bytes(int NB, int Ti) {
 // LJ (r6): the dimensions of examples/ljspeech/self-attention-tacotron.json as compile-time constants (checked by the launcher).  The
 // step body is ~12 000 instructions with ~100 wave-uniform values live across it; with run-time dimensions 1 600 of them were
 // v_readlane / v_writelane traffic of SPILLED scalars (486 spilled SGPRs) in phases that are instruction-issue bound.
-template <int NB, bool TRES, bool LJ>
+// SPK: the multi-speaker pre-net (p.sproj, p.Wp02, p.bp02: include/satt_hip.h) - the speaker term behind the ReLU of BOTH forms of
+// pre-net 0 (unfolded and folded feedback) and the layer's second Dense as one more split product and exchange per step.  The speaker
+// term and that Dense's bias are read ONCE per launch, into a register of the lanes that publish (no LDS word, no global load on the
+// step's chain).  Nothing of it exists in the SPK = false instantiations.
+template <int NB, bool TRES, bool LJ, bool SPK>
 __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p, const int spread) {
   // r6: ONE XCD.  Workgroups are dealt to the 8 XCDs round robin in launch order, so with spread = 8 the grid is 8 x 32 and only the
   // workgroups with blockIdx % 8 == 0 stay: all 32 on the same XCD (32 CUs: one each).  Every weight is register resident, so the one
@@ -358,7 +373,7 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p,
   const int U1 = LJ ? 224 : p.U1, U2 = LJ ? 32 : p.U2, UQ = U1 + U2, V1 = LJ ? 256 : p.V1, V2 = LJ ? 32 : p.V2, CT = V1 + V2;
   const int NO = LJ ? 161 : p.NO, KW = LJ ? 10 : p.kernel, F = LJ ? 5 : p.filters, PL = (KW - 1) / 2, heads = LJ ? 2 : p.heads, hd = M2N / heads;
   const int P0 = LJ ? 256 : p.P0, P1 = LJ ? 128 : p.P1, FEED = LJ ? 80 : p.feed;
-  const GL G = gl_of(hd);
+  const GL G = gl_of(hd, SPK);
   u64* gr = reinterpret_cast<u64*>(p.part);
   const int64_t gbs = G.total;                       // granules per sample
   const int R = (Ti + M2G - 1) / M2G, r0 = wg * R;
@@ -472,6 +487,12 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p,
     const int64_t o = ((int64_t)(t & 1) * B + b) * M2N + eu;
     cA = p.ca[o]; hA = p.ha[o]; c1 = p.c1[o]; h1 = p.h1[o]; c2 = p.c2[o]; h2 = p.h2[o];
   }
+  // multi-speaker pre-net: speaker term and second bias of the own (sample, column): lanes < 8 NB of the publishing wave and its helper
+  float spk = 0.f, bp02 = 0.f;
+  if constexpr (SPK) {
+    const int l = threadIdx.x & 63, w = threadIdx.x >> 6, n = 8 * wg + (l & 7);
+    if ((w == PUTW || w == AUXW) && l < 8 * NB && n < P0) { spk = p.sproj[(l >> 3) * P0 + n]; bp02 = p.bp02[n]; }
+  }
   // ---- resident weights (registers for the whole launch)
   SliceR<4> sa, s1, s2; SliceR<2> sk;
   slice_fill(sa, p.Wa, 4 * M2N, 32 * wg, P1 + M2N, P1, CT, (int)threadIdx.x);
@@ -484,6 +505,8 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p,
   const bool fold = p.Wfh && p.Wfl && p.bfb && !p.tin;      // folded feedback (free running only)
   uint4 wfh = fold ? split_fill(p.Wfh, P0, M2N, wg, (int)threadIdx.x) : make_uint4(0u, 0u, 0u, 0u);
   uint4 wfl = fold ? split_fill(p.Wfl, P0, M2N, wg, (int)threadIdx.x) : make_uint4(0u, 0u, 0u, 0u);
+  uint4 wp02 = make_uint4(0u, 0u, 0u, 0u);
+  if constexpr (SPK) wp02 = split_fill(p.Wp02, P0, P0, wg, (int)threadIdx.x);
   bool have_p0 = false;                                     // the step's first pre-net layer is already in `vb` (previous step of this launch)
   __syncthreads();
   if constexpr (tres) {
@@ -517,6 +540,7 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p,
     int oz = 0;
     asm volatile("" : "+v"(oz));
     pin(sa); pin(s1); pin(s2); pin(sk); pin(wp0); pin(wp1); pin(wqr); pin(wot); pin(wou); pin(wfh); pin(wfl);
+    if constexpr (SPK) pin(wp02);
     const int tid = (int)threadIdx.x + oz, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     __builtin_assume(tid >= 0 && tid < M2T && wave >= 0 && wave < XW);
     const int par = t & 1;
@@ -537,9 +561,15 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p,
     }
     MPROF(0);
     if (!have_p0) {      // (folded feedback: the previous step of this launch published and gathered this step's p0 behind its projection)
-      split_mul<NB>(wp0, fed, fstr, P0, bt, SATT_ACT_RELU, nullptr, 0, gr + G.p0, gbs, tag, wg, B, rs, tid, sx);
+      split_mul<NB, SPK ? 1 : 0>(wp0, fed, fstr, P0, bt, SATT_ACT_RELU, nullptr, 0, gr + G.p0, gbs, tag, wg, B, rs, tid, sx, spk);
       MPROF(1);
       gather_vec<NB>(gr + G.p0, gbs, P0, tag, B, tid, err, dead, [&](int b, int i, float v) { vb[b * M2N + i] = v; });
+    }
+    if constexpr (SPK) {
+      // second Dense of the multi-speaker pre-net's first layer, relu(vb Wp02 + bp02), back into vb: every thread's read of vb lies in
+      // front of the barrier inside split_mul, the gather's writes behind it.  (bt + 16: the query layer's bias slot - zeros)
+      split_mul<NB, 2>(wp02, vb, M2N, P0, bt + 16, SATT_ACT_RELU, nullptr, 0, gr + G.p02, gbs, tag, wg, B, rs, tid, sx, bp02);
+      gather_vec<NB>(gr + G.p02, gbs, P0, tag, B, tid, err, dead, [&](int b, int i, float v) { vb[b * M2N + i] = v; });
     }
     MPROF(2);
     // ================= A2: pre-net 1 (split)
@@ -1012,7 +1042,7 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p,
     // ================= G2: mel | stop projection (split) -> y, the next step's fed frame
     have_p0 = fold && !last;      // (the last step of a launch hands over through yout: the next launch starts unfolded)
     if (have_p0) {
-      split_mul_fb<NB>(wou, wfh, wfl, vc, NO, P0, bt + 32, bt + 168, gr + G.y, gr + G.p0, gbs, tag, wg, rs, tid, sx);
+      split_mul_fb<NB, SPK>(wou, wfh, wfl, vc, NO, P0, bt + 32, bt + 168, gr + G.y, gr + G.p0, gbs, tag, wg, rs, tid, sx, spk);
       MPROF(21);
       // y (waves 0..2: NO <= 192) and the next step's p0 (waves 3..6) in ONE gather phase
       if (wave < 3) {
@@ -1086,7 +1116,7 @@ extern "C" int satt_dec_mega2_prof_read(unsigned long long* host32, int reset) {
 // floats of the exchange buffer `part` of satt_dec_mega_params (two floats per granule)
 extern "C" int64_t satt_dec_mega_scratch_floats(int B, int heads, int hd) {
   if (heads < 1 || B < 1 || heads * hd != M2N) return 0;
-  return 2 * (int64_t)B * gl_of(hd).total;
+  return 2 * (int64_t)B * gl_of(hd, true).total;      // (the multi-speaker layout: the plain one is a prefix of it per sample)
 }
 
 // shapes the kernel takes (pointers are checked by satt_dec_mega)
@@ -1104,6 +1134,16 @@ extern "C" int satt_dec_mega_supported(const satt_dec_mega_params* pp) {
          mega2_lds_bytes(p.B <= 1 ? 1 : 2, p.Ti) <= 160 * 1024;
 }
 
+// the instantiation satt_dec_mega launches for a block (satt_hip.h: SATT_MEGA_VAR_*), -1 where the kernel does not take it
+extern "C" int satt_dec_mega_variant(const satt_dec_mega_params* pp) {
+  if (!pp || !satt_dec_mega_supported(pp)) return -1;
+  const satt_dec_mega_params& p = *pp;
+  const bool lj = p.U1 == 224 && p.U2 == 32 && p.V1 == 256 && p.V2 == 32 && p.heads == 2 && p.NO == 161 && p.feed == 80 && p.P0 == 256 &&
+                  p.P1 == 128 && p.kernel == 10 && p.filters == 5 && getenv("SATT_DECODE_GENERIC") == nullptr;
+  return (p.B <= 1 && p.Ti <= M2TR ? SATT_MEGA_VAR_TABLES_LDS : 0) | (lj ? SATT_MEGA_VAR_LJ : 0) | (p.sproj ? SATT_MEGA_VAR_SPEAKER : 0) |
+         (p.B > 1 ? SATT_MEGA_VAR_TWO_SAMPLES : 0);
+}
+
 extern "C" int satt_dec_mega(const satt_dec_mega_params* pp, void* stream) {
   if (!pp || !satt_dec_mega_supported(pp) || pp->nsteps < 1) return SATT_E_UNSUPPORTED;
   const satt_dec_mega_params& p = *pp;
@@ -1111,26 +1151,29 @@ extern "C" int satt_dec_mega(const satt_dec_mega_params* pp, void* stream) {
       !p.b2l || !p.bkvq || !p.bot || !p.bout || !p.locF || !p.locFb || !p.locU || !p.v1 || !p.b1 || !p.v2 || !p.lengths || !p.keys1 ||
       !p.values1 || !p.keys2 || !p.values2 || !p.ca || !p.ha || !p.c1 || !p.h1 || !p.c2 || !p.h2 || !p.a_state || !p.alpha_state ||
       !p.ctx || !p.yout || !p.align1 || !p.align2 || !p.kvq || !p.part || !p.ctab || !p.step || !p.err) return SATT_E_BADARG;
+  if (p.sproj && (!p.Wp02 || !p.bp02)) return SATT_E_BADARG;      // multi-speaker pre-net: its second Dense comes with the speaker term
   hipStream_t s = (hipStream_t)stream;
-  const int NB = p.B <= 1 ? 1 : 2;
+  const int var = satt_dec_mega_variant(pp);
+  const bool lj = var & SATT_MEGA_VAR_LJ, spk = var & SATT_MEGA_VAR_SPEAKER;
+  const int NB = (var & SATT_MEGA_VAR_TWO_SAMPLES) ? 2 : 1;
   const size_t smem = mega2_lds_bytes(NB, p.Ti);
   // one XCD (grid 8 x 32, every eighth workgroup works: see the kernel) unless SATT_DECODE_ONE_XCD=0
   static const int spread = [] { const char* e = getenv("SATT_DECODE_ONE_XCD"); return (e && atoi(e) == 0) ? 1 : 8; }();
-  const bool lj = p.U1 == 224 && p.U2 == 32 && p.V1 == 256 && p.V2 == 32 && p.heads == 2 && p.NO == 161 && p.feed == 80 && p.P0 == 256 &&
-                  p.P1 == 128 && p.kernel == 10 && p.filters == 5 && getenv("SATT_DECODE_GENERIC") == nullptr;
-#define SATT_MEGA2_(NBV, TR, LJV)                                                                                          \
-  do {                                                                                                                       \
-    if (hipFuncSetAttribute((const void*)dec_mega2_k<NBV, TR, LJV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) { \
-      (void)hipGetLastError();                                                                                               \
-      return SATT_E_LAUNCH;                                                                                                  \
-    }                                                                                                                        \
-    hipLaunchKernelGGL((dec_mega2_k<NBV, TR, LJV>), dim3(M2G * spread), dim3(M2T), smem, s, p, spread);                      \
+#define SATT_MEGA2_(NBV, TR, LJV, SP)                                                                                                     \
+  do {                                                                                                                                    \
+    if (hipFuncSetAttribute((const void*)dec_mega2_k<NBV, TR, LJV, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) { \
+      (void)hipGetLastError();                                                                                                            \
+      return SATT_E_LAUNCH;                                                                                                               \
+    }                                                                                                                                     \
+    hipLaunchKernelGGL((dec_mega2_k<NBV, TR, LJV, SP>), dim3(M2G * spread), dim3(M2T), smem, s, p, spread);                               \
   } while (0)
-#define SATT_MEGA2(NBV, TR) do { if (lj) SATT_MEGA2_(NBV, TR, true); else SATT_MEGA2_(NBV, TR, false); } while (0)
-  if (NB == 1 && p.Ti <= M2TR) SATT_MEGA2(1, true);
+#define SATT_MEGA2L(NBV, TR, SP) do { if (lj) SATT_MEGA2_(NBV, TR, true, SP); else SATT_MEGA2_(NBV, TR, false, SP); } while (0)
+#define SATT_MEGA2(NBV, TR) do { if (spk) SATT_MEGA2L(NBV, TR, true); else SATT_MEGA2L(NBV, TR, false); } while (0)
+  if (var & SATT_MEGA_VAR_TABLES_LDS) SATT_MEGA2(1, true);
   else if (NB == 1) SATT_MEGA2(1, false);
   else SATT_MEGA2(2, false);
 #undef SATT_MEGA2_
+#undef SATT_MEGA2L
 #undef SATT_MEGA2
   SATT_LAUNCH_CHECK();
   return SATT_OK;

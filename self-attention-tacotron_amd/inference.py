@@ -54,7 +54,7 @@ class DecodeSession:
         nm, r = c.num_mels, c.r
         feed, NO = nm * c.n_feed_frame, nm * r + 1
         self._mega_shape = None
-        if (self.MEGA and use_graph and not forced and c.dual and c.num_speakers == 0 and not c.transition_agent and
+        if (self.MEGA and use_graph and not forced and c.dual and c.mem_speaker == 0 and not c.transition_agent and
                 not c.apply_dropout_on_inference and len(c.dec_prenet) == 2 and Ds and c.dec_sa_num_hop == 1 and
                 ops.get_precision() == "bf16" and B <= self.MEGA_MAX_B):
             shape = dict(B=B, Td=Td, Ti=Ti, A=A, D=D, Ds=Ds, heads=c.dec_sa_heads, U1=U1, V1=V1, U2=U2, V2=V2, kernel=c.att_kernel,
@@ -203,6 +203,10 @@ class DecodeSession:
             # folded feedback (free running): pre-net layer 0 straight from the output transform's result - fed = the last `feed` mel
             # columns of y = vc Wout + bout is linear in vc, so relu(fed Wp0 + bp0) = relu(vc Wf + bf); Wf as bf16 hi + lo (refresh_folded)
             P0w = c.dec_prenet[0]
+            # multi-speaker pre-net: the speaker term of the utterance (self.sproj: infer() rewrites it in place per utterance, the kernel
+            # reads it at the start of every launch) behind the ReLU of pre-net 0 - in the folded form too, whose Wf / bf are those of
+            # the plain pre-net - and the layer's second Dense
+            spk = {} if self.sproj is None else dict(sproj=self.sproj, Wp02=eng.W("dec.prenet0.W2").n, bp02=P["dec.prenet0.b2"])
             self._fb = None if (teacher or not self.MEGA_FOLD_FEEDBACK) else dict(
                 a=Z(Ds, feed), b=Z(feed, P0w), w=Z(Ds, P0w), t=Z(Ds, P0w), bias=Z(1, P0w),
                 hi=torch.zeros(Ds, P0w, dtype=torch.bfloat16, device=dev), lo=torch.zeros(Ds, P0w, dtype=torch.bfloat16, device=dev))
@@ -217,7 +221,7 @@ class DecodeSession:
                 values2=self.values2, ca=ca, ha=ha, c1=c1, h1=h1, c2=c2, h2=h2, a_state=self.a_state,
                 alpha_state=self.alpha_state, ctx=self.ctx, yout=self.yout, tin=self.tin, align1=self.al1, align2=self.al2,
                 kvq=self.kvqs[0], part=self._mega_part, ctab=self.ctab, step=self.steps2, flag=None if teacher else self.flag,
-                err=self._mega_err, **({} if self._fb is None else dict(Wfh=self._fb["hi"], Wfl=self._fb["lo"], bfb=self._fb["bias"])))
+                err=self._mega_err, **spk, **({} if self._fb is None else dict(Wfh=self._fb["hi"], Wfl=self._fb["lo"], bfb=self._fb["bias"])))
             assert ops.dec_mega_supported(self.mega)
             self.kernel_launches = 1          # per K steps
         self.refresh_folded()

@@ -1151,6 +1151,14 @@ def dec_mega_supported(p):
     return bool(_lib.lib().satt_dec_mega_supported(C.byref(p)))
 
 
+MEGA_VAR_TABLES_LDS, MEGA_VAR_LJ, MEGA_VAR_SPEAKER, MEGA_VAR_TWO_SAMPLES = 1, 2, 4, 8      # include/satt_hip.h: SATT_MEGA_VAR_*
+
+
+def dec_mega_variant(p):
+    """the instantiation of the persistent kernel a launch of `p` takes: an OR of MEGA_VAR_*, -1 where the kernel does not take it"""
+    return int(_lib.lib().satt_dec_mega_variant(C.byref(p)))
+
+
 def dec_mega_scratch_floats(B, heads, hd):
     return int(_lib.lib().satt_dec_mega_scratch_floats(B, heads, hd))
 
