@@ -732,7 +732,8 @@ int satt_dec_attention(const satt_dec_attention_params* p, void* stream);
  * Same math and the same buffers as the launch-per-layer path above (the caller may switch between the two from one LAUNCH to the
  * next: recurrent state, contexts, location input and forward variable are handed over at the last step of a launch).  Supported
  * (otherwise satt_dec_mega_supported() == 0 and the caller uses satt_dec_linear / satt_dec_attention / satt_dec_self_attn): the
- * dual-source model with a two-layer pre-net - plain, or with MultiSpeakerPreNet as its first layer (sproj below) -, no transition agent, no forced alignments, bf16 weight shadows, B <= 2,
+ * dual-source model with a two-layer pre-net - plain, or with MultiSpeakerPreNet as its first layer (sproj below) -, no forced
+ * alignments, bf16 weight shadows, B <= 2 (transition agent and pre-net dropout: satt_dec_mega_opt below),
  * Ti <= 256, A = D = Ds = 256, one causal self-attention hop of 2 or 4 heads.  Replaces, per step: reference
  * modules/module.py:762-778, modules/rnn_wrappers.py:47-124,188-214, modules/forward_attention.py:88-136,
  * modules/helpers.py:58-166 (mirrors). */
@@ -791,6 +792,35 @@ int satt_dec_mega(const satt_dec_mega_params* p, void* stream);
 #define SATT_MEGA_VAR_SPEAKER 4      /* multi-speaker pre-net (sproj != NULL) */
 #define SATT_MEGA_VAR_TWO_SAMPLES 8  /* B = 2 */
 int satt_dec_mega_variant(const satt_dec_mega_params* p);
+/* ---- options of the persistent decode step, in a block of their own (satt_dec_mega_params keeps its layout).  Each option is off
+ * while its key field is zero; with both off satt_dec_mega_opt() IS satt_dec_mega().  The instantiations that take options are
+ * siblings of the plain ones (one more template flag): a launch without options runs the kernel it ran before.
+ *  - transition agent (use_forward_attention_transition_agent; reference modules/forward_attention.py:109-116; key: agentW):
+ *    u_{t+1} = sigmoid([context1_t | processed_query1_t] agentW + agentb), u_0 = 0.5, replaces both 0.5 factors of the forward
+ *    recursion.  The kernel forms no context: agent_tab[b][r] = values1[b][r][:V1] . agentW[:V1] (fp32, built by the caller per
+ *    utterance, next to ctab) turns the context part into  sum_r alignment1_t[r] agent_tab[b][r].  Needs att1_mode == 0.  u_state
+ *    [B] carries u from the last step of a launch to the next launch (read when *step > 0: the caller need not reset it).  The
+ *    launch-per-layer path keeps no such word and the kernel hands over no processed query: with the agent on, an utterance stays
+ *    on this entry point from its first step to its last.
+ *  - pre-net dropout that stays on (apply_dropout_on_inference; key: drop_thresh): satt_dec_linear's mask (drop_* of
+ *    satt_dec_linear_params) behind the ReLU of pre-net layer n, element ((b * drop_T + step) * P_n + column) of stream
+ *    drop_stream[n], in both forms of layer 0 (the folded feedback form draws the mask of the step it feeds).  With the
+ *    multi-speaker pre-net (sproj) layer 0 is MultiSpeakerPreNet, which has no dropout: only layer 1 is masked.  *drop_seed is read
+ *    at the start of a launch. */
+typedef struct {
+  const float *agentW, *agentb;           /* [V1 + U1], [1] (fp32 parameters) */
+  const float* agent_tab;                 /* [B][Ti] */
+  float* u_state;                         /* [B] */
+  const uint32_t* drop_seed;
+  uint32_t drop_thresh; float drop_scale; /* keep where hash >= thresh, kept values times scale (satt_dec_linear_params) */
+  int drop_T;                             /* rows per sample of the mask's [B][drop_T][P_n] index space */
+  uint32_t drop_stream[2];                /* stream ids of pre-net layer 0 / 1 */
+} satt_dec_mega_opt_params;
+#define SATT_MEGA_VAR_AGENT 16       /* transition agent (agentW != NULL) */
+#define SATT_MEGA_VAR_DROPOUT 32     /* pre-net dropout (drop_thresh != 0) */
+/* opt == NULL or both options off: satt_dec_mega(p, stream) / satt_dec_mega_variant(p) */
+int satt_dec_mega_opt(const satt_dec_mega_params* p, const satt_dec_mega_opt_params* opt, void* stream);
+int satt_dec_mega_opt_variant(const satt_dec_mega_params* p, const satt_dec_mega_opt_params* opt);
 /* new query row of the causal self-attention over the K|V|Q cache kvq [B,Td,3D] (row *step must hold K|V|Q of the step):
  * out [B,D] = softmax(q K^T * scale over rows 0..*step) V, heads side by side (modules/self_attention.py:45-65) */
 int satt_dec_self_attn(const float* kvq, float* out, const int* step, int B, int Td, int D, int heads, float scale,

@@ -127,6 +127,13 @@ class DecMegaParams(C.Structure):
                 [("nsteps", C.c_int)] +
                 [(n, C.c_void_p) for n in ("Wp02", "bp02", "sproj")])      # multi-speaker pre-net (NULL: the plain one)
 
+
+class DecMegaOptParams(C.Structure):
+    """satt_dec_mega_opt_params (include/satt_hip.h): transition agent and pre-net dropout of the persistent decode step"""
+    _fields_ = ([(n, C.c_void_p) for n in ("agentW", "agentb", "agent_tab", "u_state", "drop_seed")] +
+                [("drop_thresh", C.c_uint32), ("drop_scale", C.c_float), ("drop_T", C.c_int), ("drop_stream", C.c_uint32 * 2)])
+
+
 # name -> (restype, argtypes); must list EVERY symbol declared in include/satt_hip.h
 _P = C.c_void_p
 _I = C.c_int
@@ -243,6 +250,8 @@ SIGNATURES = {
     "satt_dec_mega_scratch_floats": (c_i64, [_I, _I, _I]),
     "satt_dec_mega": (_I, [C.POINTER(DecMegaParams), _P]),
     "satt_dec_mega_variant": (_I, [C.POINTER(DecMegaParams)]),
+    "satt_dec_mega_opt": (_I, [C.POINTER(DecMegaParams), C.POINTER(DecMegaOptParams), _P]),
+    "satt_dec_mega_opt_variant": (_I, [C.POINTER(DecMegaParams), C.POINTER(DecMegaOptParams)]),
     "satt_dec_self_attn": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "satt_l2_reg": (_I, [_P, _P, _P, _I, _F, _P, _P, _P]),
     "satt_sumsq": (_I, [_P, c_i64, _P, _P]),

@@ -152,14 +152,29 @@ __device__ __forceinline__ float slice_total(const float* src, int lane) {
   return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
 }
 
+// ---- options (satt_dec_mega_opt_params: transition agent, pre-net dropout).  Everything of them sits behind ONE template flag OPT:
+// the instantiations without it take an empty option type as their third kernel argument and contain nothing of what follows.
+struct MegaNoOpt {};
+template <bool OPT> struct MegaOptT { typedef MegaNoOpt type; };
+template <> struct MegaOptT<true> { typedef satt_dec_mega_opt_params type; };
+constexpr int AGT = 192;                         // agent weights [0, AGT) live in the unused tail of the v2 row of `tab`, the rest in `agx`
+// dropout of a split layer's epilogue: csrc/decode.hip dec_drop (the same element index, so the same masks); thresh == 0: off
+struct MDrop { uint32_t seed, stream, thresh, dT, step, N; float scale; };
+__device__ __forceinline__ float mega_drop(float s, const MDrop& d, int b, int col) {
+  if (d.thresh == 0u) return s;
+  const uint32_t idx = ((uint32_t)b * d.dT + d.step) * d.N + (uint32_t)col;
+  return satt_keep(d.seed, d.stream, idx, d.thresh) ? s * d.scale : 0.f;
+}
+
 // ---- split layer: the workgroup's 8 columns [8 wg, 8 wg + 8) of act(x W + bias) (+ res); thread k < 256 (waves 0..3: K <= 256)
 // holds row k of them; the publishing wave finishes and publishes granules dst[b * bs + 8 wg + j] (columns >= N are not published).
 // bias8: LDS (a global load here would sit on the step's dependency chain).  rs is free again after the caller's next barrier.
 // EX (multi-speaker pre-net): the publishing lane's register `ex` is added 1: behind the activation (the speaker term), 2: in front
-// of it (a bias that has no place in LDS; bias8 then points at zeros).
-template <int NB, int EX = 0>
+// of it (a bias that has no place in LDS; bias8 then points at zeros).  DR: dropout `dr` behind the activation (in front of EX = 1).
+template <int NB, int EX = 0, bool DR = false>
 __device__ __forceinline__ void split_mul(uint4 wr, const float* x, int xs_, int N, const float* bias8, int act, const float* res, int rs_,
-                                          u64* dst, int64_t bs, uint32_t tag, int wg, int B, float* rs, int tid, bool sx, float ex = 0.f) {
+                                          u64* dst, int64_t bs, uint32_t tag, int wg, int B, float* rs, int tid, bool sx, float ex = 0.f,
+                                          const MDrop& dr = MDrop()) {
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (wave < 4) {
     float xv[NB];
@@ -185,6 +200,7 @@ __device__ __forceinline__ void split_mul(uint4 wr, const float* x, int xs_, int
     if constexpr (EX == 2) s += ex;
     if (act == SATT_ACT_RELU) s = fmaxf(s, 0.f);
     else if (act == SATT_ACT_TANH) s = tanhf_(s);
+    if constexpr (DR) s = mega_drop(s, dr, b, n);
     s += rv;
     if constexpr (EX == 1) s += ex;
     if (b < B && n < N) gput(dst + b * bs + n, tag, s, sx);
@@ -200,10 +216,12 @@ __device__ __forceinline__ uint4 split_fill(const uint16_t* __restrict__ W, int 
 // ---- folded feedback (r6): from the SAME vector x (the output transform's result) the workgroup's 8 columns of the mel | stop
 // projection (published as y with `tag`) AND of relu(x Wf + bf) = the first pre-net layer of the NEXT step (published as p0 with
 // tag + 1; Wf as bf16 hi + lo).  One barrier; wave PUTW publishes y, wave AUXW p0.  SPK (multi-speaker pre-net): p0 is
-// relu(x Wf + bf) + spk, the speaker term of the publishing lane's (sample, column).
-template <int NB, bool SPK = false>
+// relu(x Wf + bf) + spk, the speaker term of the publishing lane's (sample, column).  DR: dropout `dr` (the NEXT step's mask) behind
+// the ReLU of p0 - the mask sits behind the fold, so the fold stays valid.
+template <int NB, bool SPK = false, bool DR = false>
 __device__ __forceinline__ void split_mul_fb(uint4 wy, uint4 wh, uint4 wl, const float* x, int NO_, int P0_, const float* by8, const float* bf8,
-                                             u64* dy, u64* dp, int64_t bs, uint32_t tag, int wg, float* rs, int tid, bool sx, float spk = 0.f) {
+                                             u64* dy, u64* dp, int64_t bs, uint32_t tag, int wg, float* rs, int tid, bool sx, float spk = 0.f,
+                                             const MDrop& dr = MDrop()) {
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (wave < 4) {
     float xv[NB];
@@ -228,6 +246,7 @@ __device__ __forceinline__ void split_mul_fb(uint4 wy, uint4 wh, uint4 wl, const
     float s = ((s0 + s1) + (s2 + s3)) + (wave == AUXW ? bf8[j] : by8[j]);
     if (wave == AUXW) {
       s = fmaxf(s, 0.f);
+      if constexpr (DR) s = mega_drop(s, dr, b, n);
       if constexpr (SPK) s += spk;
       if (n < P0_) gput(dp + b * bs + n, tag + 1u, s, sx);
     }
@@ -314,9 +333,11 @@ __device__ __forceinline__ float lstm_unit(float tot, const float* bias32, float
   return hn;
 }
 
-__host__ __device__ inline size_t mega2_lds_bytes(int NB, int Ti) {
+// opt: the option instantiations' agent table [NB][256] and the 64 agent weights beyond tab's tail
+__host__ __device__ inline size_t mega2_lds_bytes(int NB, int Ti, bool opt = false) {
   const size_t fl = 2 * 8 * NB * 32 + NB * 32 + NB * 16 + 320 + 16 * M2HD + 3 * M2HD + M2PM + (size_t)NB * (3 * 512 + M2N + M2NO + (M2TI + 16) + 3 * M2TI + 3 * M2N) +
-                    8 * M2N + 16 * 8 + 3 * M2N + (size_t)NB * 8 * KLS + 176 + 4 + 4 + (size_t)NB * 2 * 32 * M2HD + ((NB == 1 && Ti <= M2TR) ? (size_t)Ti * TLS : 0);
+                    8 * M2N + 16 * 8 + 3 * M2N + (size_t)NB * 8 * KLS + 176 + 4 + 4 + (size_t)NB * 2 * 32 * M2HD + ((NB == 1 && Ti <= M2TR) ? (size_t)Ti * TLS : 0) +
+                    (opt ? (size_t)NB * M2TI + 64 : 0);
   return fl * sizeof(float);
 }
 
@@ -327,8 +348,15 @@ __host__ __device__ inline size_t mega2_lds_bytes(int NB, int Ti) {
 // pre-net 0 (unfolded and folded feedback) and the layer's second Dense as one more split product and exchange per step.  The speaker
 // term and that Dense's bias are read ONCE per launch, into a register of the lanes that publish (no LDS word, no global load on the
 // step's chain).  Nothing of it exists in the SPK = false instantiations.
-template <int NB, bool TRES, bool LJ, bool SPK>
-__global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p, const int spread) {
+// OPT: the options of satt_dec_mega_opt_params, each a wave-uniform run-time branch (o.agentW != NULL, o.drop_thresh != 0).
+//  * transition agent: the wave that owns (sample b, mechanism 0) in phase C holds the normalised alignment of the step in registers
+//    and finds the step's processed query in `va` (B1's gather): u_{t+1} = sigmoid(sum_r alignment[r] agent_tab[b][r] + pq1 . Wa[V1:]
+//    + ba) is ONE more wave sum there, kept in a wave-uniform register for the next step's recursion.  Every workgroup computes the
+//    softmax redundantly and so every workgroup computes u: no exchange, no granule, no barrier.  agent_tab and the weights are LDS
+//    resident (`agt`, tab's tail | `agx`); u crosses launches through o.u_state.
+//  * dropout: mega_drop in the epilogue of the split pre-net products.
+template <int NB, bool TRES, bool LJ, bool SPK, bool OPT>
+__global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p, const int spread, const typename MegaOptT<OPT>::type o) {
   // r6: ONE XCD.  Workgroups are dealt to the 8 XCDs round robin in launch order, so with spread = 8 the grid is 8 x 32 and only the
   // workgroups with blockIdx % 8 == 0 stay: all 32 on the same XCD (32 CUs: one each).  Every weight is register resident, so the one
   // L2 only has to carry the exchanges - and granules published with PLAIN stores stay in that L2, where the peers' polling loads find
@@ -368,6 +396,8 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p,
   float* Kc = reinterpret_cast<float*>(dead + 4);    // [NB][32][128] key rows of the own (head, chunk) while a chunk is 32 rows (t < 512)
   float* Vc = Kc + NB * 32 * M2HD;                   // [NB][32][128] value rows
   float* TL = Vc + NB * 32 * M2HD;                   // [Ti][TLS] the workgroup's slices of the context tables (B = 1, Ti <= M2TR)
+  [[maybe_unused]] float* agt = TL + (TRES ? p.Ti * TLS : 0);      // OPT only: [NB][256] agent table | [64] agent weights AGT .. of the query part
+  [[maybe_unused]] float* agx = agt + NB * M2TI;
   constexpr int B = NB;          // (the launcher instantiates NB = B: B is 1 or 2; r6 - as a run-time value it kept a guard per sample loop alive)
   const int Ti = p.Ti;
   const int U1 = LJ ? 224 : p.U1, U2 = LJ ? 32 : p.U2, UQ = U1 + U2, V1 = LJ ? 256 : p.V1, V2 = LJ ? 32 : p.V2, CT = V1 + V2;
@@ -391,7 +421,7 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p,
     // (DESIGN.md 3.5): the fed frame is read as yv[NO - 1 - feed + k], k < 256, and yv[NO .. M2NO) was never written.
     {
       float4* z4 = reinterpret_cast<float4*>(smem);
-      const int n4 = (int)(mega2_lds_bytes(NB, TRES ? p.Ti : M2TR + 1) / 16);      // (no LDS-resident tables unless TRES)
+      const int n4 = (int)(mega2_lds_bytes(NB, TRES ? p.Ti : M2TR + 1, OPT) / 16);      // (no LDS-resident tables unless TRES)
       for (int i = tid; i < n4; i += M2T) z4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     __syncthreads();
@@ -416,7 +446,16 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p,
       float v = w == 0 ? (u < U1 ? p.v1[u] : 0.f) : (w == 1 ? (u < U1 ? p.b1[u] : 0.f) : (u < U2 ? p.v2[u] : 0.f));
       if (w == 1 && u < U1)
         for (int f = 0; f < F; ++f) v += p.locFb[f] * p.locU[f * U1 + u];           // (bias of the location convolution, through U)
+      if constexpr (OPT) {      // (v2 ends at U2 <= 64: the row's tail carries the agent's query weights [0, AGT))
+        if (w == 2 && u >= 64 && u - 64 < U1 && o.agentW) v = o.agentW[V1 + u - 64];
+      }
       tab[i] = v;
+    }
+    if constexpr (OPT) {
+      if (o.agentW) {
+        if (tid < 64 && AGT + tid < U1) agx[tid] = o.agentW[V1 + AGT + tid];
+        for (int i = tid; i < NB * Ti; i += M2T) { const int b = i / Ti, r = i - b * Ti; agt[b * M2TI + r] = o.agent_tab[i]; }
+      }
     }
     if (tid < 4) lens[tid] = tid < B ? (int)p.lengths[tid] : 0;
     for (int i = tid; i < NB * 8 * KLS; i += M2T) {
@@ -493,6 +532,16 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p,
     const int l = threadIdx.x & 63, w = threadIdx.x >> 6, n = 8 * wg + (l & 7);
     if ((w == PUTW || w == AUXW) && l < 8 * NB && n < P0) { spk = p.sproj[(l >> 3) * P0 + n]; bp02 = p.bp02[n]; }
   }
+  // options: the transition probability of step t of the own wave's sample (phase C) and the launch's dropout seed
+  [[maybe_unused]] float u_cur = 0.5f, agb = 0.f;
+  [[maybe_unused]] uint32_t dseed = 0u;
+  if constexpr (OPT) {
+    if (o.agentW) {
+      agb = o.agentb[0];
+      if (t > 0) u_cur = o.u_state[min((int)(threadIdx.x >> 7), B - 1)];
+    }
+    if (o.drop_thresh) dseed = *o.drop_seed;
+  }
   // ---- resident weights (registers for the whole launch)
   SliceR<4> sa, s1, s2; SliceR<2> sk;
   slice_fill(sa, p.Wa, 4 * M2N, 32 * wg, P1 + M2N, P1, CT, (int)threadIdx.x);
@@ -533,10 +582,18 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p,
   const int nsteps = p.nsteps;
   const bool sx = __builtin_amdgcn_readfirstlane((int)(spread > 1 && sx_lds != 0.f)) != 0;      // plain-store exchanges (same XCD, verified)
   for (int s = 0; s < nsteps; ++s, ++t) {
-    typedef const __attribute__((address_space(4))) satt_dec_mega_params KArgsM;
+    struct KArgsAll { satt_dec_mega_params p; int spread; typename MegaOptT<OPT>::type o; };      // the kernarg segment
+    typedef const __attribute__((address_space(4))) KArgsAll KArgsM;
     KArgsM* kq = (KArgsM*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(kq));
-    const auto& p = *kq;
+    const auto& p = kq->p;
+    [[maybe_unused]] const auto& o = kq->o;
+    [[maybe_unused]] MDrop dr0 = MDrop(), dr1 = MDrop();
+    if constexpr (OPT) {
+      dr1.seed = dseed; dr1.stream = o.drop_stream[1]; dr1.thresh = o.drop_thresh; dr1.dT = (uint32_t)o.drop_T; dr1.step = (uint32_t)t;
+      dr1.N = (uint32_t)P1; dr1.scale = o.drop_scale;
+      dr0 = dr1; dr0.stream = o.drop_stream[0]; dr0.N = (uint32_t)P0;      // (not used with SPK: MultiSpeakerPreNet has no dropout)
+    }
     int oz = 0;
     asm volatile("" : "+v"(oz));
     pin(sa); pin(s1); pin(s2); pin(sk); pin(wp0); pin(wp1); pin(wqr); pin(wot); pin(wou); pin(wfh); pin(wfl);
@@ -561,7 +618,7 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p,
     }
     MPROF(0);
     if (!have_p0) {      // (folded feedback: the previous step of this launch published and gathered this step's p0 behind its projection)
-      split_mul<NB, SPK ? 1 : 0>(wp0, fed, fstr, P0, bt, SATT_ACT_RELU, nullptr, 0, gr + G.p0, gbs, tag, wg, B, rs, tid, sx, spk);
+      split_mul<NB, SPK ? 1 : 0, OPT && !SPK>(wp0, fed, fstr, P0, bt, SATT_ACT_RELU, nullptr, 0, gr + G.p0, gbs, tag, wg, B, rs, tid, sx, spk, dr0);
       MPROF(1);
       gather_vec<NB>(gr + G.p0, gbs, P0, tag, B, tid, err, dead, [&](int b, int i, float v) { vb[b * M2N + i] = v; });
     }
@@ -573,7 +630,7 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p,
     }
     MPROF(2);
     // ================= A2: pre-net 1 (split)
-    split_mul<NB>(wp1, vb, M2N, P1, bt + 8, SATT_ACT_RELU, nullptr, 0, gr + G.p1, gbs, tag, wg, B, rs, tid, sx);
+    split_mul<NB, 0, OPT>(wp1, vb, M2N, P1, bt + 8, SATT_ACT_RELU, nullptr, 0, gr + G.p1, gbs, tag, wg, B, rs, tid, sx, 0.f, dr1);
     MPROF(3);
     gather_vec<NB>(gr + G.p1, gbs, P1, tag, B, tid, err, dead, [&](int b, int i, float v) { XA[b * 512 + i] = v; });
     MPROF(4);
@@ -675,6 +732,21 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p,
         const int i = lane + 64 * q;
         alv[q] = al[i]; alm[q] = al[max(i - 1, 0)]; apv[q] = ap[i]; ev[q] = 0.f;
       }
+      // transition agent: the query part of the next step's u and the agent table's entries, read before the poll too
+      [[maybe_unused]] float agq = 0.f, agv[4] = {0.f, 0.f, 0.f, 0.f};
+      [[maybe_unused]] bool agent = false;
+      if constexpr (OPT) {
+        agent = o.agentW != nullptr && mech == 0;
+        if (agent) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int i = lane + 64 * q;
+            const float w = 64 * q < AGT ? tab[2 * M2N + 64 + i] : agx[i - AGT], x = va[b * M2N + i];
+            agq += i < U1 ? x * w : 0.f;
+            agv[q] = agt[b * M2TI + i];
+          }
+        }
+      }
       {
         const gu64* g[4];
         u64 x[4];
@@ -713,12 +785,23 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p,
           const float a = x[q] * rsum;
           if (i < Ti) ap[i] = p.cumulative ? a + apv[q] : a;
           keep[q] = a;
-          if (p.att1_mode == 0) { keep[q] = i < Ti ? (0.5f * alv[q] + 0.5f * (i > 0 ? alm[q] : 0.f) + 1e-7f) * a : 0.f; s2_ += keep[q]; }
+          if constexpr (OPT) {      // (u_cur = 0.5 without the agent: the same bits as the constants)
+            if (p.att1_mode == 0) { keep[q] = i < Ti ? ((1.f - u_cur) * alv[q] + u_cur * (i > 0 ? alm[q] : 0.f) + 1e-7f) * a : 0.f; s2_ += keep[q]; }
+          } else {
+            if (p.att1_mode == 0) { keep[q] = i < Ti ? (0.5f * alv[q] + 0.5f * (i > 0 ? alm[q] : 0.f) + 1e-7f) * a : 0.f; s2_ += keep[q]; }
+          }
         }
         if (p.att1_mode == 0) {
           const float r2 = 1.f / wave_sum(s2_);
 #pragma unroll
           for (int q = 0; q < 4; ++q) keep[q] *= r2;
+        }
+        if constexpr (OPT) {
+          if (agent) {      // u of step t + 1 from this step's alignment (agent table: zero beyond Ti) and processed query
+            const float z = wave_sum(agq + ((keep[0] * agv[0] + keep[1] * agv[1]) + (keep[2] * agv[2] + keep[3] * agv[3])));
+            u_cur = 1.f / (1.f + __expf(-(z + agb)));
+            if (last && wg == 2 % M2G && lane == 0) o.u_state[b] = u_cur;      // (next to the forward variable's hand-over)
+          }
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) { al[lane + 64 * q] = keep[q]; e[lane + 64 * q] = keep[q]; }
@@ -1042,7 +1125,8 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p,
     // ================= G2: mel | stop projection (split) -> y, the next step's fed frame
     have_p0 = fold && !last;      // (the last step of a launch hands over through yout: the next launch starts unfolded)
     if (have_p0) {
-      split_mul_fb<NB, SPK>(wou, wfh, wfl, vc, NO, P0, bt + 32, bt + 168, gr + G.y, gr + G.p0, gbs, tag, wg, rs, tid, sx, spk);
+      if constexpr (OPT) dr0.step = (uint32_t)t + 1u;      // (the folded p0 is the NEXT step's)
+      split_mul_fb<NB, SPK, OPT && !SPK>(wou, wfh, wfl, vc, NO, P0, bt + 32, bt + 168, gr + G.y, gr + G.p0, gbs, tag, wg, rs, tid, sx, spk, dr0);
       MPROF(21);
       // y (waves 0..2: NO <= 192) and the next step's p0 (waves 3..6) in ONE gather phase
       if (wave < 3) {
@@ -1144,7 +1228,19 @@ extern "C" int satt_dec_mega_variant(const satt_dec_mega_params* pp) {
          (p.B > 1 ? SATT_MEGA_VAR_TWO_SAMPLES : 0);
 }
 
-extern "C" int satt_dec_mega(const satt_dec_mega_params* pp, void* stream) {
+namespace {
+inline bool opt_agent(const satt_dec_mega_opt_params* o) { return o && o->agentW; }
+inline bool opt_drop(const satt_dec_mega_opt_params* o) { return o && o->drop_thresh != 0u; }
+}  // namespace
+
+// the same with options (satt_hip.h: satt_dec_mega_opt_params); with none on: satt_dec_mega_variant
+extern "C" int satt_dec_mega_opt_variant(const satt_dec_mega_params* pp, const satt_dec_mega_opt_params* opt) {
+  const int var = satt_dec_mega_variant(pp);
+  if (var < 0) return var;
+  return var | (opt_agent(opt) ? SATT_MEGA_VAR_AGENT : 0) | (opt_drop(opt) ? SATT_MEGA_VAR_DROPOUT : 0);
+}
+
+extern "C" int satt_dec_mega_opt(const satt_dec_mega_params* pp, const satt_dec_mega_opt_params* opt, void* stream) {
   if (!pp || !satt_dec_mega_supported(pp) || pp->nsteps < 1) return SATT_E_UNSUPPORTED;
   const satt_dec_mega_params& p = *pp;
   if (!p.Wp0 || !p.Wp1 || !p.Wa || !p.Wq || !p.W1 || !p.W2 || !p.Wkvq || !p.Wot || !p.Wout || !p.bp0 || !p.bp1 || !p.ba || !p.b1l ||
@@ -1152,29 +1248,37 @@ extern "C" int satt_dec_mega(const satt_dec_mega_params* pp, void* stream) {
       !p.values1 || !p.keys2 || !p.values2 || !p.ca || !p.ha || !p.c1 || !p.h1 || !p.c2 || !p.h2 || !p.a_state || !p.alpha_state ||
       !p.ctx || !p.yout || !p.align1 || !p.align2 || !p.kvq || !p.part || !p.ctab || !p.step || !p.err) return SATT_E_BADARG;
   if (p.sproj && (!p.Wp02 || !p.bp02)) return SATT_E_BADARG;      // multi-speaker pre-net: its second Dense comes with the speaker term
+  // options: the agent belongs to the forward recursion and comes with its bias, table and state word; dropout with its seed word
+  if (opt_agent(opt) && (!opt->agentb || !opt->agent_tab || !opt->u_state || p.att1_mode != 0)) return SATT_E_BADARG;
+  if (opt_drop(opt) && (!opt->drop_seed || opt->drop_T < 1)) return SATT_E_BADARG;
   hipStream_t s = (hipStream_t)stream;
-  const int var = satt_dec_mega_variant(pp);
-  const bool lj = var & SATT_MEGA_VAR_LJ, spk = var & SATT_MEGA_VAR_SPEAKER;
+  const int var = satt_dec_mega_opt_variant(pp, opt);
+  const bool lj = var & SATT_MEGA_VAR_LJ, spk = var & SATT_MEGA_VAR_SPEAKER, has_opt = var & (SATT_MEGA_VAR_AGENT | SATT_MEGA_VAR_DROPOUT);
   const int NB = (var & SATT_MEGA_VAR_TWO_SAMPLES) ? 2 : 1;
-  const size_t smem = mega2_lds_bytes(NB, p.Ti);
+  const size_t smem = mega2_lds_bytes(NB, p.Ti, has_opt);
+  if (smem > 160 * 1024) return SATT_E_UNSUPPORTED;      // (B = 2 with options: 163 104 bytes - every supported shape fits)
   // one XCD (grid 8 x 32, every eighth workgroup works: see the kernel) unless SATT_DECODE_ONE_XCD=0
   static const int spread = [] { const char* e = getenv("SATT_DECODE_ONE_XCD"); return (e && atoi(e) == 0) ? 1 : 8; }();
-#define SATT_MEGA2_(NBV, TR, LJV, SP)                                                                                                     \
+#define SATT_MEGA2_(NBV, TR, LJV, SP, OP, OARG)                                                                                           \
   do {                                                                                                                                    \
-    if (hipFuncSetAttribute((const void*)dec_mega2_k<NBV, TR, LJV, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) { \
+    if (hipFuncSetAttribute((const void*)dec_mega2_k<NBV, TR, LJV, SP, OP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) { \
       (void)hipGetLastError();                                                                                                            \
       return SATT_E_LAUNCH;                                                                                                               \
     }                                                                                                                                     \
-    hipLaunchKernelGGL((dec_mega2_k<NBV, TR, LJV, SP>), dim3(M2G * spread), dim3(M2T), smem, s, p, spread);                               \
+    hipLaunchKernelGGL((dec_mega2_k<NBV, TR, LJV, SP, OP>), dim3(M2G * spread), dim3(M2T), smem, s, p, spread, OARG);                     \
   } while (0)
-#define SATT_MEGA2L(NBV, TR, SP) do { if (lj) SATT_MEGA2_(NBV, TR, true, SP); else SATT_MEGA2_(NBV, TR, false, SP); } while (0)
+#define SATT_MEGA2O(NBV, TR, LJV, SP) do { if (has_opt) SATT_MEGA2_(NBV, TR, LJV, SP, true, *opt); else SATT_MEGA2_(NBV, TR, LJV, SP, false, MegaNoOpt()); } while (0)
+#define SATT_MEGA2L(NBV, TR, SP) do { if (lj) SATT_MEGA2O(NBV, TR, true, SP); else SATT_MEGA2O(NBV, TR, false, SP); } while (0)
 #define SATT_MEGA2(NBV, TR) do { if (spk) SATT_MEGA2L(NBV, TR, true); else SATT_MEGA2L(NBV, TR, false); } while (0)
   if (var & SATT_MEGA_VAR_TABLES_LDS) SATT_MEGA2(1, true);
   else if (NB == 1) SATT_MEGA2(1, false);
   else SATT_MEGA2(2, false);
 #undef SATT_MEGA2_
+#undef SATT_MEGA2O
 #undef SATT_MEGA2L
 #undef SATT_MEGA2
   SATT_LAUNCH_CHECK();
   return SATT_OK;
 }
+
+extern "C" int satt_dec_mega(const satt_dec_mega_params* pp, void* stream) { return satt_dec_mega_opt(pp, nullptr, stream); }

@@ -54,8 +54,7 @@ class DecodeSession:
         nm, r = c.num_mels, c.r
         feed, NO = nm * c.n_feed_frame, nm * r + 1
         self._mega_shape = None
-        if (self.MEGA and use_graph and not forced and c.dual and c.mem_speaker == 0 and not c.transition_agent and
-                not c.apply_dropout_on_inference and len(c.dec_prenet) == 2 and Ds and c.dec_sa_num_hop == 1 and
+        if (self.MEGA and use_graph and not forced and c.dual and len(c.dec_prenet) == 2 and Ds and c.dec_sa_num_hop == 1 and
                 ops.get_precision() == "bf16" and B <= self.MEGA_MAX_B):
             shape = dict(B=B, Td=Td, Ti=Ti, A=A, D=D, Ds=Ds, heads=c.dec_sa_heads, U1=U1, V1=V1, U2=U2, V2=V2, kernel=c.att_kernel,
                          filters=c.att_filters, att1_mode=int(c.attention == "location_sensitive"), cumulative=int(c.cumulative_weights),
@@ -189,7 +188,7 @@ class DecodeSession:
         self.graph = None
         # ---- persistent form (csrc/decode_mega2.hip): the same step, ONE launch per K steps on 32 persistent workgroups that exchange
         # {tag, value} granules instead of nine dependent launches - for the configurations satt_dec_mega_supported took above
-        self.mega = None
+        self.mega = self.mega_opt = None
         self.ctab = self._ctw = None
         if self._mega_shape is not None:
             from .params import sa_prefix
@@ -223,6 +222,16 @@ class DecodeSession:
                 kvq=self.kvqs[0], part=self._mega_part, ctab=self.ctab, step=self.steps2, flag=None if teacher else self.flag,
                 err=self._mega_err, **spk, **({} if self._fb is None else dict(Wfh=self._fb["hi"], Wfl=self._fb["lo"], bfb=self._fb["bias"])))
             assert ops.dec_mega_supported(self.mega)
+            # options of the kernel (a block of their own; None: ops.dec_mega as ever).  Transition agent: the kernel forms no
+            # context, so the context part of u's dot product comes from a per-utterance table values1 Wa[:V1]
+            # (build_context_tables) and u crosses launches in u_state.  Dropout that stays on: the launch-per-layer masks (pdrop).
+            if c.transition_agent or (c.apply_dropout_on_inference and c.dec_prenet_drop > 0):
+                agent = {}
+                if c.transition_agent:
+                    self.agent_tab, self.u_state = Z(B * Ti, 1), Z(B)
+                    agent = dict(agentW=P["dec.att1.Wa"], agentb=P["dec.att1.ba"], agent_tab=self.agent_tab, u_state=self.u_state)
+                drop = ops.Drop(c.dec_prenet_drop, 0, self.drop_seed) if c.apply_dropout_on_inference else None
+                self.mega_opt = ops.dec_mega_opt_params(drop=drop, drop_T=Td, drop_streams=(S_DEC_PRENET0, S_DEC_PRENET1), **agent)
             self.kernel_launches = 1          # per K steps
         self.refresh_folded()
         if self.mega is not None:
@@ -371,13 +380,16 @@ class DecodeSession:
         if self.mega is None or self.ctab is None:
             return
         c = self.eng.cfg
-        A, D, V1, V2, P1 = c.att_rnn_units, c.dec_units, c.cbhg_out_units, c.sa_units, c.dec_prenet[1]
+        # (speaker_to_decoder: the memories and the cells' context rows are V + mem_speaker wide)
+        A, D, V1, V2, P1 = c.att_rnn_units, c.dec_units, c.cbhg_out_units + c.mem_speaker, c.sa_units + c.mem_speaker, c.dec_prenet[1]
         W1, Wa = self.lstm_w["dec.lstm1.W"], self.lstm_w["dec.att_lstm.W"]
         rows = ((W1, A, V1), (W1, A + V1, V2), (Wa, P1, V1), (Wa, P1 + V1, V2))
         for q, (W, r0, n) in enumerate(rows):
             self._ctw[q].copy_(W[r0:r0 + n])
             x = self.values1 if q % 2 == 0 else self.values2
             ops.gemm(x.shape[0], 4 * D, n, x, n, self._ctw[q], 4 * D, 1, self.ctab[:, q * 4 * D:], 16 * D, prec=ops.PREC_F32)
+        if c.transition_agent:      # agent_tab[b][r] = values1[b, r] . Wa[:V1] (fp32 parameters, as the launch-per-layer step multiplies)
+            ops.gemm(self.values1.shape[0], 1, V1, self.values1, V1, self.eng.P["dec.att1.Wa"], 1, 1, self.agent_tab, 1, prec=ops.PREC_F32)
 
     def run_step(self):
         for fn, prm in self.launches:
@@ -387,7 +399,11 @@ class DecodeSession:
         """K decoder steps (the persistent kernel: `nsteps` <= K of them - a ragged last launch): one launch of the persistent
         kernel, or one replay of the captured graph"""
         if self.mega is not None:
-            ops.dec_mega(self.mega, self.K if nsteps is None else max(1, min(self.K, int(nsteps))))
+            n = self.K if nsteps is None else max(1, min(self.K, int(nsteps)))
+            if self.mega_opt is not None:
+                ops.dec_mega_opt(self.mega, self.mega_opt, n)
+            else:
+                ops.dec_mega(self.mega, n)
         else:
             self.graph.replay()
 

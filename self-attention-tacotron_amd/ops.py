@@ -1169,6 +1169,33 @@ def dec_mega(p, nsteps):
     _lib.check(_lib.lib().satt_dec_mega(C.byref(p), _s()), "dec_mega")
 
 
+MEGA_VAR_AGENT, MEGA_VAR_DROPOUT = 16, 32      # include/satt_hip.h: SATT_MEGA_VAR_* of the option block
+
+
+def dec_mega_opt_params(agentW=None, agentb=None, agent_tab=None, u_state=None, drop=None, drop_T=0, drop_streams=(0, 0)):
+    """option block of the persistent decode step (satt_dec_mega_opt_params).  agentW .. u_state: the transition agent (None: off);
+    drop (a Drop: rate and the session's seed word; its stream is not used) / drop_T / drop_streams: pre-net dropout that stays on -
+    dec_linear_params' mask, per pre-net layer its own stream."""
+    o = _lib.DecMegaOptParams()
+    ptr = lambda v: v.data_ptr() if isinstance(v, torch.Tensor) else v          # (tensors, or addresses as dec_mega_params takes them)
+    o.agentW, o.agentb, o.agent_tab, o.u_state = ptr(agentW), ptr(agentb), ptr(agent_tab), ptr(u_state)
+    if drop is not None and drop.thresh:
+        o.drop_thresh, o.drop_scale, o.drop_seed, o.drop_T = drop.thresh, drop.scale, ptr(drop.seed), int(drop_T)
+        o.drop_stream[0], o.drop_stream[1] = int(drop_streams[0]), int(drop_streams[1])
+    return o
+
+
+def dec_mega_opt_variant(p, opt):
+    """dec_mega_variant of a launch with the option block `opt` (None: without): plus MEGA_VAR_AGENT / MEGA_VAR_DROPOUT"""
+    return int(_lib.lib().satt_dec_mega_opt_variant(C.byref(p), None if opt is None else C.byref(opt)))
+
+
+def dec_mega_opt(p, opt, nsteps):
+    """dec_mega with the option block `opt`"""
+    p.nsteps = int(nsteps)
+    _lib.check(_lib.lib().satt_dec_mega_opt(C.byref(p), None if opt is None else C.byref(opt), _s()), "dec_mega_opt")
+
+
 def dec_self_attn(kvq, out, step, B, Td, D, heads, scale):
     _lib.check(_lib.lib().satt_dec_self_attn(_p(kvq), _p(out), _p(step), B, Td, D, heads, float(scale), _s()), "dec_self_attn")
 

@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """BASELINE.json config 5: free-running decode (B=1, Ti=100, LJSpeech config) - decoder steps per second.
 --hparams-json: another model, e.g. examples/vctk/self-attention-tacotron.json (speaker ids: the first B of the table).
-usage: python tools/bench_infer.py [--steps 200] [--batch 1] [--hparams-json FILE] [--repeat N]"""
+--hparams "k=v,...": overrides on top of it (on the LJSpeech example's file when no --hparams-json is given), e.g.
+use_forward_attention_transition_agent=True or apply_dropout_on_inference=True.
+usage: python tools/bench_infer.py [--steps 200] [--batch 1] [--hparams-json FILE] [--hparams "k=v,..."] [--repeat N]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -20,16 +22,19 @@ ap.add_argument("--steps-per-graph", type=int, default=8)
 ap.add_argument("--no-graph", action="store_true")
 ap.add_argument("--mega-max-b", type=int, default=None, help="largest batch that takes the persistent step kernel (default: the session's)")
 ap.add_argument("--hparams-json", default=None, help="hparams file of the model (default: the LJSpeech dimensions)")
+ap.add_argument("--hparams", default=None, help='comma-separated name=value overrides of the model\'s hparams')
 ap.add_argument("--repeat", type=int, default=1, help="timed utterances (one JSON line each)")
 a = ap.parse_args()
 ops.set_precision(a.precision)
 if a.mega_max_b is not None:
     from satt_amd.inference import DecodeSession
     DecodeSession.MEGA_MAX_B = a.mega_max_b
-if a.hparams_json:
+if a.hparams_json or a.hparams:
     from satt_amd.hparams import hparams
     hp = hparams.copy()
-    hp.parse_json(open(a.hparams_json).read())
+    hp.parse_json(open(a.hparams_json or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples", "ljspeech",
+                                                      "self-attention-tacotron.json")).read())
+    hp.parse(a.hparams)
     cfg = ModelConfig.from_hparams(hp)
 else:
     cfg = ModelConfig()
@@ -53,7 +58,7 @@ for _ in range(a.repeat):
     ses = eng._decode_sessions[next(reversed(eng._decode_sessions))]
     path = "persistent" if getattr(ses, "mega", None) is not None else "launch-per-layer"
     frames = a.steps * cfg.r * B
-    print(json.dumps({"metric": "free-running decode (config 5)", "model": a.hparams_json or "ljspeech", "path": path, "batch": B, "Ti": Ti, "decoder_steps": out["steps"],
+    print(json.dumps({"metric": "free-running decode (config 5)", "model": (a.hparams_json or "ljspeech") + (" + " + a.hparams if a.hparams else ""), "path": path, "batch": B, "Ti": Ti, "decoder_steps": out["steps"],
                       "ms_per_step": 1e3 * dt / a.steps, "utterance_ms_incl_encoder": 1e3 * dt_all,
                       "steps_per_graph": a.steps_per_graph, "graph": not a.no_graph,
                       "mel_frames_per_sec": frames / dt,
