@@ -736,7 +736,20 @@ int satt_dec_attention(const satt_dec_attention_params* p, void* stream);
  * alignments, bf16 weight shadows, B <= 2 (transition agent and pre-net dropout: satt_dec_mega_opt below),
  * Ti <= 256, A = D = Ds = 256, one causal self-attention hop of 2 or 4 heads.  Replaces, per step: reference
  * modules/module.py:762-778, modules/rnn_wrappers.py:47-124,188-214, modules/forward_attention.py:88-136,
- * modules/helpers.py:58-166 (mirrors). */
+ * modules/helpers.py:58-166 (mirrors).
+ *
+ * SINGLE-SOURCE FORM (the baseline model: ExtendedTacotronV1Model with ZoneoutEncoderV1 and ExtendedDecoder v2 - one attention
+ * mechanism, no decoder self-attention, the mel | stop projection reads the DecoderRNNV2 output).  It is keyed on the block itself:
+ * Ds == 0 && heads == 0 && U2 == 0 && V2 == 0.  Then keys2, values2, v2, align2, Wkvq, bkvq, Wot, bot and kvq are NULL and never
+ * dereferenced; Wout is [D][ldout]; Wfh / Wfl (folded feedback) are [D][P0] with Wf = Wout[:, NO-1-feed : NO-1] Wp0; ctx is [2][B][V1];
+ * `part` has satt_dec_mega_scratch_floats(B, 0, 0) floats; and ctab holds TWO tables, [B][Ti][2][4 * 256]: values1 W1c | values1 Wac
+ * (the rows [A, A + V1) of the regrouped LSTM 1 weight and [P1, P1 + V1) of the attention LSTM weight).  Supported: A = D = 256,
+ * B <= 2, Ti <= 256, U1 % 4 == 0, 8 <= U1 <= 256, 1 <= V1 <= 1024, the pre-net / feed / output / location-layer conditions of the
+ * dual form; plain or multi-speaker pre-net; attention `forward` (att1_mode 0, with or without cumulative) and `location_sensitive`
+ * (att1_mode 1).  A block that is only half single (Ds == 0 with U2 > 0 or V2 > 0, or the reverse) is unsupported.  The single form
+ * takes no options: satt_dec_mega_opt with an option switched on returns SATT_E_UNSUPPORTED, satt_dec_mega_opt_variant -1.  Eight
+ * exchanges per step (p0 -> p1 -> hq -> pq -> e1 -> h1n -> dout -> y) instead of eleven; the hand-over to the launch-per-layer path
+ * at the last step of a launch is the dual form's (context: the V1 columns). */
 typedef struct {
   int B, Td, Ti, A, D, Ds, heads;          /* Td: rows of the histories (yout has Td + 1 rows per sample) */
   int U1, V1, U2, V2, kernel, filters, att1_mode, cumulative;
@@ -783,7 +796,7 @@ typedef struct {
   const float* sproj;
 } satt_dec_mega_params;
 int satt_dec_mega_supported(const satt_dec_mega_params* p);
-int64_t satt_dec_mega_scratch_floats(int B, int heads, int head_dim);
+int64_t satt_dec_mega_scratch_floats(int B, int heads, int head_dim);      /* (B, 0, 0): the single-source form */
 int satt_dec_mega(const satt_dec_mega_params* p, void* stream);
 /* which instantiation of the kernel satt_dec_mega launches for the block (diagnostics, tests): an OR of the bits below, or -1
  * where satt_dec_mega_supported() == 0 */
@@ -791,6 +804,7 @@ int satt_dec_mega(const satt_dec_mega_params* p, void* stream);
 #define SATT_MEGA_VAR_LJ 2           /* the dimensions of examples/ljspeech/self-attention-tacotron.json as compile-time constants */
 #define SATT_MEGA_VAR_SPEAKER 4      /* multi-speaker pre-net (sproj != NULL) */
 #define SATT_MEGA_VAR_TWO_SAMPLES 8  /* B = 2 */
+#define SATT_MEGA_VAR_SINGLE 64      /* the single-source form (Ds == heads == U2 == V2 == 0: the baseline model) */
 int satt_dec_mega_variant(const satt_dec_mega_params* p);
 /* ---- options of the persistent decode step, in a block of their own (satt_dec_mega_params keeps its layout).  Each option is off
  * while its key field is zero; with both off satt_dec_mega_opt() IS satt_dec_mega().  The instantiations that take options are

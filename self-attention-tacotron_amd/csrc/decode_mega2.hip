@@ -21,6 +21,8 @@
 // Same buffers and same math as the launch-per-layer path (csrc/decode.hip); selection: satt_dec_mega_supported (A = D = Ds = 256,
 // B <= 2, ...); granule tags are step + 1, the caller zeroes the granule buffer when it resets the step counter.  Single-buffered granules are
 // safe: between the consumption of X(t) and the production of X(t+1) lies at least one exchange every workgroup contributes to.
+// The baseline model (one attention source, no decoder self-attention) runs the SINGLE-SOURCE form, dec_mega2_single_k below: the same
+// helpers, eight exchanges, its own LDS and granule layout, and the granule argument re-derived for its chain.
 #include <cstdlib>
 #include "cluster_xchg.h"
 
@@ -1183,6 +1185,585 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p,
   }
 }
 
+// =====================================================================================================================================
+// SINGLE-SOURCE FORM: the baseline model (ExtendedTacotronV1Model: ZoneoutEncoderV1 + ExtendedDecoder v2 - one attention mechanism, no
+// decoder self-attention, the mel | stop projection reads the DecoderRNNV2 output).  Keyed on the block itself: Ds == heads == U2 ==
+// V2 == 0 (keys2, values2, v2, align2, Wkvq, bkvq, Wot, bot, kvq are NULL and never read; heads / hd are never touched).  The same
+// machinery as dec_mega2_k - 32 persistent workgroups on one XCD, register-resident weights, sliced cells, split layers, granules
+// tagged step + 1, contexts folded into per-utterance tables - with the phases of the second mechanism and of the self-attention
+// block (E, F, G1) gone.  Eight exchanges per step:
+//       p0 -> p1 -> [attention LSTM] hq -> pq -> [energies] e1 -> [softmax, LSTM 1] h1n -> [LSTM 2] dout -> [projection] y
+// (SPK: p0 -> p02 -> p1 is a ninth).  Folded feedback: the projection's input is dout, so Wf = Wout[:, fed columns] Wp0 has K = D and
+// split_mul_fb works on the gathered dout vector.
+//
+// Context tables of this form: ctab [B][Ti][2][1024] = values1 W1c | values1 Wac (LSTM 1 / attention LSTM rows that multiply the
+// context) - the two tables of the second memory do not exist.  The LDS copy (TRES) has rows of TLS1 = 2 x 32 + 4 floats.
+//
+// SINGLE-BUFFERED GRANULES, re-derived for this chain.  Call an exchange FULL when every one of the 32 workgroups publishes a part
+// of it and every workgroup gathers all of it: hq, h1n and dout are full (A = D = 256 = 32 x 8 columns, whatever the other widths
+// are); p0 / p1 / pq / y (P0, P1, U1, NO columns: the first N / 8 workgroups publish) and e1 (the workgroups whose rows lie below
+// Ti) need not be.  Every workgroup runs the phases of a step in program order, every gather ends in a workgroup barrier and every
+// publication lies behind a later barrier, so a workgroup publishes its part of an exchange only after ALL its waves have finished
+// every earlier gather.  Claim: when any workgroup P overwrites granule X(t) with X(t + 1), every workgroup has finished reading
+// X(t).  P publishes X(t + 1) behind its gathers of everything in front of X in the cyclic order
+//       p0 p1 [hq] pq e1 [h1n] [dout] y | p0 ...
+// Between P's own gather of X(t) and its publication of X(t + 1) the chain goes once round the cycle, so P has gathered a full
+// exchange F that lies behind X(t) and in front of X(t + 1): for X in {p0, p1}: dout(t) (also hq(t), h1n(t)); X = hq: h1n(t), dout(t);
+// X in {pq, e1}: h1n(t), dout(t), hq(t + 1); X = h1n: dout(t), hq(t + 1); X = dout: hq(t + 1), h1n(t + 1); X = y: hq(t + 1), h1n(t + 1),
+// dout(t + 1).  P's gather of F returned only when EVERY workgroup had published its part of F, and each of them did that behind its
+// own gather of X(t).  So nobody still reads X(t).  The same holds for p02 (between p0 and p1).
+// The fold moves the publication of p0(t + 1) forward, next to y(t): both lie behind P's gather of dout(t), which is full and lies
+// behind every workgroup's gather of p0(t) (done in A1 of step t, or - folded - in G2 of step t - 1): hq(t), h1n(t) and dout(t) all
+// lie between.  y(t) and p0(t + 1) carry different tags (t + 1, t + 2) in different granules and are gathered in one phase by
+// different waves in front of one barrier; the next publication of either lies behind the full exchanges of step t + 1.  The last
+// step of a launch is unfolded and the next launch starts behind the end of this one (stream order).  Nothing here depends on timing:
+// no vector needs a second buffer.  (The energies are consumed by the softmax waves only; the barrier behind phase C orders them
+// in front of the workgroup's next publication like a gather's.)
+struct GLS { int p0, p1, hq, pq, e, h1, dout, y, hs, p02, total; };
+__host__ __device__ inline GLS gls_of(bool spk = false) {
+  GLS g; int o = 0;
+  g.p0 = o; o += M2N; g.p1 = o; o += M2N; g.hq = o; o += M2N; g.pq = o; o += M2N; g.e = o; o += M2TI; g.h1 = o; o += M2N; g.dout = o; o += M2N;
+  g.y = o; o += M2NO;
+  g.hs = o; o += M2G;            // placement handshake of a launch (sample 0's area)
+  g.p02 = o; if (spk) o += M2N;  // multi-speaker pre-net only
+  g.total = o;
+  return g;
+}
+constexpr int TLS1 = 68;         // padded row of the LDS copy of the two context tables
+
+// the workgroup's 8 columns of a weight whose row stride is no multiple of 8 (the query layer with U1 % 8 == 4): element loads
+__device__ __forceinline__ uint4 split_fill_any(const uint16_t* __restrict__ W, int ldw, int K, int wg, int tid) {
+  if ((ldw & 7) == 0) return split_fill(W, ldw, K, wg, tid);
+  uint32_t h[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int n = 8 * wg + j;
+    const uint32_t v = W[(int64_t)min(tid, K - 1) * ldw + min(n, ldw - 1)];
+    h[j] = (tid < K && n < ldw) ? v : 0u;
+  }
+  return make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+}
+
+// context tables of the single form: thread (column group tid & 3, row lane tid >> 2) holds rows 127 - rl, 255 - rl (tab_load's
+// order and reasons) of the two tables, 8 columns each
+struct TabR1 { float4 v[8]; };
+__device__ __forceinline__ void tab1_load(TabR1& t, const float* __restrict__ ctab, int b, int Ti, int wg, int tid) {
+  const int cg = tid & 3, rl = tid >> 2;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int r = min(127 - rl + 128 * i, Ti - 1);      // (rows beyond Ti: one shared line, not used)
+    const float* base = ctab + ((int64_t)b * Ti + r) * 2048 + 32 * wg + 8 * cg;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      t.v[(i * 2 + q) * 2] = *reinterpret_cast<const float4*>(base + q * 1024);
+      t.v[(i * 2 + q) * 2 + 1] = *reinterpret_cast<const float4*>(base + q * 1024 + 4);
+    }
+  }
+}
+__device__ __forceinline__ void tab1_mul(const TabR1& t, const float* a1, int Ti, int tid, float (&acc1)[8], float (&acca)[8]) {
+  const int rl = tid >> 2;
+  float w1[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) w1[i] = a1[127 - rl + 128 * i];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    if (127 - rl + 128 * i < Ti) {
+      fma8(acc1, w1[i], t.v[(i * 2 + 0) * 2], t.v[(i * 2 + 0) * 2 + 1]);
+      fma8(acca, w1[i], t.v[(i * 2 + 1) * 2], t.v[(i * 2 + 1) * 2 + 1]);
+    }
+  }
+}
+// the same from the LDS copy (tl[r][2][32], row stride TLS1; Ti <= 128: one row per thread)
+__device__ __forceinline__ void tab1_mul_lds(const float* tl, const float* a1, int Ti, int tid, float (&acc1)[8], float (&acca)[8]) {
+  const int cg = tid & 3, r = min(tid >> 2, Ti - 1);
+  const bool ok = (tid >> 2) < Ti;
+  const float* row = tl + r * TLS1 + 8 * cg;
+  float4 v[4];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) { v[2 * q] = *reinterpret_cast<const float4*>(row + 32 * q); v[2 * q + 1] = *reinterpret_cast<const float4*>(row + 32 * q + 4); }
+  const float w1 = ok ? a1[r] : 0.f;
+  fma8(acc1, w1, v[0], v[1]); fma8(acca, w1, v[2], v[3]);
+}
+
+// LDS of the single form (floats, in the kernel's order): rs | ra | zca | zs | XA | X1 | X2 | XK | yv | aprev | alpha | e1 | va | vb |
+// Us | Fs | tab | kls | bt | lens | dead | TL.  Every term is a multiple of 4 floats: the kernel zeroes the allocation in 16-byte words.
+__host__ __device__ inline size_t mega2s_lds_bytes(int NB, int Ti) {
+  const size_t fl = 2 * 8 * NB * 32 + NB * 32 + NB * 8 + (size_t)NB * (3 * 512 + M2N + M2NO + (M2TI + 16) + 2 * M2TI + 2 * M2N) +
+                    8 * M2N + 16 * 8 + 2 * M2N + (size_t)NB * 8 * M2N + 176 + 4 + 4 + ((NB == 1 && Ti <= M2TR) ? (size_t)Ti * TLS1 : 0);
+  return fl * sizeof(float);
+}
+
+template <int NB, bool TRES, bool SPK>
+__global__ __launch_bounds__(M2T) void dec_mega2_single_k(const satt_dec_mega_params p, const int spread) {
+  if (blockIdx.x % spread) return;       // ONE XCD: see dec_mega2_k
+  const int wg = blockIdx.x / spread;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* rs = smem;                                  // [8 NB 32] wave partials of the slice / split products
+  float* ra = rs + 8 * NB * 32;                      // [8 NB 32] ... of the attention LSTM's context term of the NEXT step
+  float* zca = ra + 8 * NB * 32;                     // [NB][32] that term, summed
+  float* zs = zca + NB * 32;                         // [NB][8] the own rows' energies of the step
+  float* XA = zs + NB * 8;                           // [NB][512] p1 | h of the attention LSTM
+  float* X1 = XA + NB * 512;                         // [NB][512] hq | h of LSTM 1
+  float* X2 = X1 + NB * 512;                         // [NB][512] h1_new | h of LSTM 2
+  float* XK = X2 + NB * 512;                         // [NB][256] decoder LSTM output: the projection's input
+  float* yv = XK + NB * M2N;                         // [NB][168]
+  float* aprev = yv + NB * M2NO;                     // [NB][256 + 16]
+  float* alpha = aprev + NB * (M2TI + 16);           // [NB][256]
+  float* e1 = alpha + NB * M2TI;                     // [NB][256] alignment of the step
+  float* va = e1 + NB * M2TI;                        // [NB][256] scratch vectors
+  float* vb = va + NB * M2N;
+  float* Us = vb + NB * M2N;                         // [8][256]
+  float* Fs = Us + 8 * M2N;                          // [16][8]
+  float* tab = Fs + 16 * 8;                          // [2][256]: v1 | b1 (+ the location layer's bias term)
+  float* kls = tab + 2 * M2N;                        // [NB * 8][256]
+  float* bt = kls + NB * 8 * M2N;                    // [5][8] split-layer biases (slots 2, 3: zeros) | [3][32] cell biases | [168..176) folded bias
+  int* lens = reinterpret_cast<int*>(bt + 176);
+  int* dead = lens + 4;
+  float* TL = reinterpret_cast<float*>(dead + 4);    // [Ti][TLS1] the workgroup's slices of the context tables (B = 1, Ti <= M2TR)
+  constexpr int B = NB;
+  const int Ti = p.Ti;
+  const int U1 = p.U1, V1 = p.V1, NO = p.NO, KW = p.kernel, F = p.filters, PL = (KW - 1) / 2;
+  const int P0 = p.P0, P1 = p.P1, FEED = p.feed;
+  const GLS G = gls_of(SPK);
+  u64* gr = reinterpret_cast<u64*>(p.part);
+  const int64_t gbs = G.total;                       // granules per sample
+  const int R = (Ti + M2G - 1) / M2G, r0 = wg * R;
+  constexpr bool tres = TRES;
+  int t = *p.step;
+  if (p.flag && !p.tin && *p.flag != 0) return;      // the stop rule fired in an earlier launch
+  float sx_lds = 0.f;
+  {
+    const int tid = threadIdx.x, par = t & 1;
+    {      // EVERY word of the allocation starts at zero (dec_mega2_k)
+      float4* z4 = reinterpret_cast<float4*>(smem);
+      const int n4 = (int)(mega2s_lds_bytes(NB, TRES ? p.Ti : M2TR + 1) / 16);
+      for (int i = tid; i < n4; i += M2T) z4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    __syncthreads();
+    if (spread > 1) {      // placement handshake (dec_mega2_k)
+      const uint32_t htag = 0x80000000u | (uint32_t)(t + 1);
+      if (tid == 0) gput(gr + G.hs + wg, htag, __uint_as_float((uint32_t)xcc_id() + 1u), false);
+      if (tid < 64) gather_poll<1>(gr + G.hs, M2G, htag, tid, [&](int i, float v) { rs[i] = v; }, p.err, dead);
+      __syncthreads();
+      if (tid == 0) {
+        bool same = !*dead;
+        for (int i = 1; i < M2G; ++i) same = same && __float_as_uint(rs[i]) == __float_as_uint(rs[0]);
+        rs[M2G] = same ? 1.f : 0.f;
+      }
+      __syncthreads();
+      sx_lds = rs[M2G];
+      __syncthreads();
+    }
+    for (int i = tid; i < 8 * M2N; i += M2T) { const int f = i / M2N, u = i - f * M2N; Us[i] = (f < F && u < U1) ? p.locU[f * U1 + u] : 0.f; }
+    for (int i = tid; i < 2 * M2N; i += M2T) {
+      const int w = i / M2N, u = i - w * M2N;
+      float v = u < U1 ? (w == 0 ? p.v1[u] : p.b1[u]) : 0.f;
+      if (w == 1 && u < U1)
+        for (int f = 0; f < F; ++f) v += p.locFb[f] * p.locU[f * U1 + u];
+      tab[i] = v;
+    }
+    if (tid < 4) lens[tid] = tid < B ? (int)p.lengths[tid] : 0;
+    for (int i = tid; i < NB * 8 * M2N; i += M2T) {
+      const int row = i / M2N, u = i - row * M2N, b = row / 8, rr = row - b * 8, tt = r0 + rr;
+      kls[i] = (b < B && rr < R && tt < Ti && u < U1) ? p.keys1[((int64_t)b * Ti + tt) * U1 + u] : 0.f;
+    }
+    for (int i = tid; i < 16 * 8; i += M2T) { const int j = i >> 3, f = i & 7; Fs[i] = (f < F && j < KW) ? p.locF[j * F + f] : 0.f; }
+    if (tid < 40) {
+      const int l = tid >> 3, n = 8 * wg + (tid & 7);
+      const float* bp = l == 0 ? p.bp0 : (l == 1 ? p.bp1 : (l == 4 ? p.bout : nullptr));
+      const int N = l == 0 ? P0 : (l == 1 ? P1 : (l == 4 ? NO : 0));
+      bt[tid] = (bp && n < N) ? bp[n] : 0.f;
+    } else if (tid >= 64 && tid < 64 + 96) {
+      const int i = tid - 64, l = i >> 5, g = (i >> 3) & 3, u = i & 7;
+      const float* bp = l == 0 ? p.ba : (l == 1 ? p.b1l : p.b2l);
+      bt[40 + i] = bp[g * M2N + 8 * wg + u];
+    } else if (tid >= 224 && tid < 232) {
+      const int n = 8 * wg + tid - 224;
+      bt[168 + tid - 224] = (p.bfb && n < P0) ? p.bfb[n] : 0.f;
+    }
+    __syncthreads();
+    // state of step t: location-conv input, forward variable, recurrent vectors, the previous step's alignment, the fed frame
+    for (int i = tid; i < NB * Ti; i += M2T) {
+      const int b = i / Ti, r = i - b * Ti;
+      if (b < B) {
+        aprev[b * (M2TI + 16) + PL + r] = p.a_state[((int64_t)par * B + b) * Ti + r];
+        alpha[b * M2TI + r] = p.alpha_state[((int64_t)par * B + b) * Ti + r];
+        if (t > 0) e1[b * M2TI + r] = p.align1[((int64_t)b * p.Td + t - 1) * Ti + r];
+      }
+    }
+    for (int i = tid; i < NB * M2N; i += M2T) {
+      const int b = i >> 8, k = i & 255;
+      if (b < B) {
+        XA[b * 512 + P1 + k] = p.ha[((int64_t)par * B + b) * M2N + k];
+        X1[b * 512 + M2N + k] = p.h1[((int64_t)par * B + b) * M2N + k];
+        X2[b * 512 + M2N + k] = p.h2[((int64_t)par * B + b) * M2N + k];
+      }
+    }
+    for (int i = tid; i < NB * NO; i += M2T) { const int b = i / NO, c = i - b * NO; yv[b * M2NO + c] = b < B ? p.yout[((int64_t)b * (p.Td + 1) + t) * NO + c] : 0.f; }
+  }
+#ifdef SATT_MEGA_PROF
+  unsigned long long mp_last = wall_clock64(), mp_clk = clock64();
+#endif
+  // own units' cell state: lanes < 8 NB of the publishing wave
+  float cA = 0.f, hA = 0.f, c1 = 0.f, h1 = 0.f, c2 = 0.f, h2 = 0.f;
+  if ((int)threadIdx.x >= 64 * PUTW && (int)threadIdx.x < 64 * PUTW + 8 * NB) {
+    const int l = threadIdx.x - 64 * PUTW, b = min(l >> 3, B - 1), eu = 8 * wg + (l & 7);
+    const int64_t o = ((int64_t)(t & 1) * B + b) * M2N + eu;
+    cA = p.ca[o]; hA = p.ha[o]; c1 = p.c1[o]; h1 = p.h1[o]; c2 = p.c2[o]; h2 = p.h2[o];
+  }
+  float spk = 0.f, bp02 = 0.f;
+  if constexpr (SPK) {
+    const int l = threadIdx.x & 63, w = threadIdx.x >> 6, n = 8 * wg + (l & 7);
+    if ((w == PUTW || w == AUXW) && l < 8 * NB && n < P0) { spk = p.sproj[(l >> 3) * P0 + n]; bp02 = p.bp02[n]; }
+  }
+  // ---- resident weights (registers for the whole launch)
+  SliceR<4> sa, s1, s2;
+  slice_fill(sa, p.Wa, 4 * M2N, 32 * wg, P1 + M2N, P1, V1, (int)threadIdx.x);
+  slice_fill(s1, p.W1, 4 * M2N, 32 * wg, 2 * M2N, M2N, V1, (int)threadIdx.x);
+  slice_fill(s2, p.W2, 4 * M2N, 32 * wg, 2 * M2N, 2 * M2N, 0, (int)threadIdx.x);
+  uint4 wp0 = split_fill(p.Wp0, P0, FEED, wg, (int)threadIdx.x), wp1 = split_fill(p.Wp1, P1, P0, wg, (int)threadIdx.x);
+  uint4 wqr = split_fill_any(p.Wq, U1, M2N, wg, (int)threadIdx.x);
+  uint4 wou = split_fill(p.Wout, p.ldout, M2N, wg, (int)threadIdx.x);
+  const bool fold = p.Wfh && p.Wfl && p.bfb && !p.tin;      // folded feedback (free running only)
+  uint4 wfh = fold ? split_fill(p.Wfh, P0, M2N, wg, (int)threadIdx.x) : make_uint4(0u, 0u, 0u, 0u);
+  uint4 wfl = fold ? split_fill(p.Wfl, P0, M2N, wg, (int)threadIdx.x) : make_uint4(0u, 0u, 0u, 0u);
+  uint4 wp02 = make_uint4(0u, 0u, 0u, 0u);
+  if constexpr (SPK) wp02 = split_fill(p.Wp02, P0, P0, wg, (int)threadIdx.x);
+  bool have_p0 = false;
+  __syncthreads();
+  if constexpr (tres) {
+    for (int i = threadIdx.x; i < Ti * 64; i += M2T) { const int r = i >> 6, c = i & 63; TL[r * TLS1 + c] = p.ctab[(int64_t)r * 2048 + (c >> 5) * 1024 + 32 * wg + (c & 31)]; }
+    __syncthreads();
+  }
+  {      // context term of the attention LSTM at step t, from the alignment of step t - 1 (zero at t = 0)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float a1[NB][8], aa[NB][8];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { a1[b][j] = 0.f; aa[b][j] = 0.f; }
+      if constexpr (tres) tab1_mul_lds(TL, e1, Ti, tid, a1[b], aa[b]);
+      else { TabR1 tb; tab1_load(tb, p.ctab, b, Ti, wg, tid); tab1_mul(tb, e1 + b * M2TI, Ti, tid, a1[b], aa[b]); }
+    }
+    slice_store<NB>(aa, ra, lane, wave);
+    __syncthreads();
+    if (tid < NB * 32) zca[tid] = slice_total<NB>(ra, tid);
+    __syncthreads();
+  }
+  const int nsteps = p.nsteps;
+  const bool sx = __builtin_amdgcn_readfirstlane((int)(spread > 1 && sx_lds != 0.f)) != 0;
+  for (int s = 0; s < nsteps; ++s, ++t) {
+    struct KArgsAll { satt_dec_mega_params p; int spread; };      // the kernarg segment
+    typedef const __attribute__((address_space(4))) KArgsAll KArgsM;
+    KArgsM* kq = (KArgsM*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kq));
+    const auto& p = kq->p;
+    int oz = 0;
+    asm volatile("" : "+v"(oz));
+    pin(sa); pin(s1); pin(s2); pin(wp0); pin(wp1); pin(wqr); pin(wou); pin(wfh); pin(wfl);
+    if constexpr (SPK) pin(wp02);
+    const int tid = (int)threadIdx.x + oz, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    __builtin_assume(tid >= 0 && tid < M2T && wave >= 0 && wave < XW);
+    const int par = t & 1;
+    const bool last = s == nsteps - 1;
+    const uint32_t tag = (uint32_t)(t + 1);
+    unsigned int* err = p.err;
+    const float zc = p.zc, zh = p.zh;
+    // ================= A1: pre-net 0 (split) on the fed frame
+    const float* fed = yv + (NO - 1 - FEED);
+    int fstr = M2NO;
+    if (p.tin) {
+      for (int i = tid; i < NB * M2N; i += M2T) {
+        const int b = i >> 8, k = i & 255;
+        va[i] = (b < B && k < FEED) ? p.tin[((int64_t)b * p.Td + t) * FEED + k] : 0.f;
+      }
+      lds_barrier();
+      fed = va; fstr = M2N;
+    }
+    MPROF(0);
+    if (!have_p0) {
+      split_mul<NB, SPK ? 1 : 0>(wp0, fed, fstr, P0, bt, SATT_ACT_RELU, nullptr, 0, gr + G.p0, gbs, tag, wg, B, rs, tid, sx, spk);
+      MPROF(1);
+      gather_vec<NB>(gr + G.p0, gbs, P0, tag, B, tid, err, dead, [&](int b, int i, float v) { vb[b * M2N + i] = v; });
+    }
+    if constexpr (SPK) {      // second Dense of the multi-speaker pre-net's first layer (bt + 16: a zero slot)
+      split_mul<NB, 2>(wp02, vb, M2N, P0, bt + 16, SATT_ACT_RELU, nullptr, 0, gr + G.p02, gbs, tag, wg, B, rs, tid, sx, bp02);
+      gather_vec<NB>(gr + G.p02, gbs, P0, tag, B, tid, err, dead, [&](int b, int i, float v) { vb[b * M2N + i] = v; });
+    }
+    MPROF(2);
+    // ================= A2: pre-net 1 (split)
+    split_mul<NB>(wp1, vb, M2N, P1, bt + 8, SATT_ACT_RELU, nullptr, 0, gr + G.p1, gbs, tag, wg, B, rs, tid, sx);
+    MPROF(3);
+    gather_vec<NB>(gr + G.p1, gbs, P1, tag, B, tid, err, dead, [&](int b, int i, float v) { XA[b * 512 + i] = v; });
+    MPROF(4);
+    // ================= A3: attention LSTM slice + cell
+    {
+      float acc[NB][8];
+#pragma unroll
+      for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[b][j] = 0.f;
+      slice_acc<NB, 4>(sa, XA, acc, tid);
+      slice_store<NB>(acc, rs, lane, wave);
+    }
+    lds_barrier();
+    if (wave == PUTW) {
+      const float tot = slice_total<NB>(rs, lane);
+      const float hn = lstm_unit(tot, bt + 40, zca[min(lane, NB * 32 - 1)], lane, cA, hA, zc, zh);
+      if (lane < 8 * B) {
+        const int b = lane >> 3, eu = 8 * wg + (lane & 7);
+        gput(gr + b * gbs + G.hq + eu, tag, hn, sx);
+        if (last) { const int64_t oo = ((int64_t)(par ^ 1) * B + b) * M2N + eu; p.ca[oo] = cA; p.ha[oo] = hA; }
+      }
+    }
+    MPROF(5);
+    gather_vec<NB>(gr + G.hq, gbs, M2N, tag, B, tid, err, dead, [&](int b, int i, float v) {
+      X1[b * 512 + i] = v;
+      float* hs = XA + b * 512 + P1 + i;
+      *hs = (1.f - zh) * v + zh * *hs;
+    });
+    MPROF(6);
+    // ================= B1: query layer (split)
+    split_mul<NB>(wqr, X1, 512, U1, bt + 16, SATT_ACT_NONE, nullptr, 0, gr + G.pq, gbs, tag, wg, B, rs, tid, sx);
+    MPROF(7);
+    gather_vec<NB>(gr + G.pq, gbs, U1, tag, B, tid, err, dead, [&](int b, int i, float v) { va[b * M2N + i] = v; });
+    MPROF(8);
+    // ================= B2: energies of the own rows: row pr on wave 7 - pr
+    for (int pr = 7 - wave; pr < B * R; pr += XW) {
+      const int b = pr / R, rr = pr - b * R, tt = r0 + rr;
+      if (tt < Ti) {
+        const float* kr = kls + (b * 8 + rr) * M2N;
+        const float* pq = va + b * M2N;
+        const int f = lane & 7, jg = lane >> 3;
+        const float* ap = aprev + b * (M2TI + 16) + tt;
+        const float t0 = ap[jg], t1 = ap[jg + 8], f0 = Fs[jg * 8 + f], f1 = Fs[(jg + 8) * 8 + f];      // (Fs rows >= kernel are zero)
+        float part = t0 * f0 + t1 * f1;
+        part += swz_xor(part, 8); part += swz_xor(part, 16);
+        part += lane_xor32(part, lane);
+        float fl[8];
+#pragma unroll
+        for (int ff = 0; ff < 8; ++ff) fl[ff] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(part), ff));
+        float a = 0.f;
+#pragma unroll
+        for (int q0 = 0; q0 < 4; q0 += 2) {
+          if (64 * q0 < U1) {
+            const int d0 = lane + 64 * q0, d1 = d0 + 64;
+            const float ka = kr[d0], kb = kr[d1], ba_ = tab[M2N + d0], bb_ = tab[M2N + d1], pa = pq[d0], pb = pq[d1], wa_ = tab[d0], wb_ = tab[d1];
+            float ua[8], ub[8];
+#pragma unroll
+            for (int ff = 0; ff < 8; ++ff) { ua[ff] = Us[ff * M2N + d0]; ub[ff] = Us[ff * M2N + d1]; }
+            float xa = ka + ba_ + pa, xb = kb + bb_ + pb;
+#pragma unroll
+            for (int ff = 0; ff < 8; ++ff) { xa += fl[ff] * ua[ff]; xb += fl[ff] * ub[ff]; }
+            a += wa_ * tanhf_(xa) + wb_ * tanhf_(xb);          // (v1, U and the keys are zero beyond U1; pq there is finite)
+          }
+        }
+        a = wave_sum(a);
+        if (lane == 0) zs[b * 8 + rr] = a;
+      }
+    }
+    lds_barrier();
+    // the workgroup's R energies of a sample: ONE contiguous run of granules (row index = granule index), one store instruction
+    if (wave == PUTW && lane < R * NB) {
+      const int b = lane / R, rr = lane - b * R;
+      if (b < B && r0 + rr < Ti) gput(gr + b * gbs + G.e + r0 + rr, tag, zs[b * 8 + rr], sx);
+    }
+    MPROF(9);
+    // the context tables of sample 0 do not depend on the alignment: requested before the energy exchange
+    TabR1 tb;
+    if constexpr (!tres) tab1_load(tb, p.ctab, 0, Ti, wg, tid);
+    // ================= C: softmax + forward recursion, one wave per sample: polls its energies into registers
+    if (wave < B) {
+      const int b = wave, len = lens[b];
+      float* al = alpha + b * M2TI;
+      float* ap = aprev + b * (M2TI + 16) + PL;
+      float alv[4], alm[4], apv[4], ev[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int i = lane + 64 * q;
+        alv[q] = al[i]; alm[q] = al[max(i - 1, 0)]; apv[q] = ap[i]; ev[q] = 0.f;
+      }
+      {
+        const gu64* g[4];
+        u64 x[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          g[q] = (const gu64*)(gr + b * gbs + G.e + min(lane + 64 * q, Ti - 1));
+          x[q] = 0;
+        }
+        if (!*dead && !poll_until<4>(g, tag, x)) {
+          if (lane == 0) __hip_atomic_store((gu32*)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          *dead = 1;
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) ev[q] = __uint_as_float((uint32_t)x[q]);
+      }
+      MPROF(24);
+      float m = -INFINITY;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) m = fmaxf(m, lane + 64 * q < len ? ev[q] : -INFINITY);
+      m = wave_max(m);
+      float x[4], sacc = 0.f;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { x[q] = lane + 64 * q < len ? __expf(ev[q] - m) : 0.f; sacc += x[q]; }
+      const float rsum = 1.f / wave_sum(sacc);
+      float* e = e1 + b * M2TI;
+      float keep[4], s2_ = 0.f;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int i = lane + 64 * q;
+        const float a = x[q] * rsum;
+        if (i < Ti) ap[i] = p.cumulative ? a + apv[q] : a;
+        keep[q] = a;
+        if (p.att1_mode == 0) { keep[q] = i < Ti ? (0.5f * alv[q] + 0.5f * (i > 0 ? alm[q] : 0.f) + 1e-7f) * a : 0.f; s2_ += keep[q]; }
+      }
+      if (p.att1_mode == 0) {
+        const float r2 = 1.f / wave_sum(s2_);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) keep[q] *= r2;
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { al[lane + 64 * q] = keep[q]; e[lane + 64 * q] = keep[q]; }
+    }
+    MPROF(25);
+    lds_barrier();
+    MPROF(10);
+    // histories (one workgroup each, stores only)
+    if (wg == 1 % M2G) {
+      for (int i = tid; i < NB * Ti; i += M2T) {
+        const int b = i / Ti, r = i - b * Ti;
+        if (b < B) p.align1[((int64_t)b * p.Td + t) * Ti + r] = e1[b * M2TI + r];
+      }
+    }
+    if (last && wg == 2 % M2G) {
+      for (int i = tid; i < NB * Ti; i += M2T) {
+        const int b = i / Ti, r = i - b * Ti;
+        if (b < B) {
+          p.a_state[((int64_t)(par ^ 1) * B + b) * Ti + r] = aprev[b * (M2TI + 16) + PL + r];
+          p.alpha_state[((int64_t)(par ^ 1) * B + b) * Ti + r] = e1[b * M2TI + r];
+        }
+      }
+    }
+    // ================= C2: LSTM 1 on [hq | h] + the context term; the attention LSTM's context term of the NEXT step
+    {
+      float acc[NB][8], aa[NB][8];
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { acc[b][j] = 0.f; aa[b][j] = 0.f; }
+        if constexpr (tres) tab1_mul_lds(TL, e1, Ti, tid, acc[b], aa[b]);
+        else {
+          if (b > 0) tab1_load(tb, p.ctab, b, Ti, wg, tid);
+          tab1_mul(tb, e1 + b * M2TI, Ti, tid, acc[b], aa[b]);
+        }
+      }
+      slice_acc<NB, 4>(s1, X1, acc, tid);
+      slice_store<NB>(acc, rs, lane, wave);
+      slice_store<NB>(aa, ra, lane, wave);
+    }
+    lds_barrier();
+    if (wave == PUTW) {
+      const float tot = slice_total<NB>(rs, lane);
+      const float hn = lstm_unit(tot, bt + 72, 0.f, lane, c1, h1, zc, zh);
+      if (lane < 8 * B) {
+        const int b = lane >> 3, eu = 8 * wg + (lane & 7);
+        gput(gr + b * gbs + G.h1 + eu, tag, hn, sx);
+        if (last) { const int64_t oo = ((int64_t)(par ^ 1) * B + b) * M2N + eu; p.c1[oo] = c1; p.h1[oo] = h1; }
+      }
+    } else if (wave == AUXW) {
+      const float tot = slice_total<NB>(ra, lane);
+      if (lane < NB * 32) zca[lane] = tot;
+    }
+    MPROF(11);
+    // ================= D: LSTM 2 on [h1_new | h]
+    gather_vec<NB>(gr + G.h1, gbs, M2N, tag, B, tid, err, dead, [&](int b, int i, float v) {
+      X2[b * 512 + i] = v;
+      float* hs = X1 + b * 512 + M2N + i;
+      *hs = (1.f - zh) * v + zh * *hs;
+    });
+    MPROF(12);
+    {
+      float acc[NB][8];
+#pragma unroll
+      for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[b][j] = 0.f;
+      slice_acc<NB, 4>(s2, X2, acc, tid);
+      slice_store<NB>(acc, rs, lane, wave);
+    }
+    lds_barrier();
+    if (wave == PUTW) {
+      const float tot = slice_total<NB>(rs, lane);
+      const float hn = lstm_unit(tot, bt + 104, 0.f, lane, c2, h2, zc, zh);
+      if (lane < 8 * B) {
+        const int b = lane >> 3, eu = 8 * wg + (lane & 7);
+        gput(gr + b * gbs + G.dout + eu, tag, hn, sx);
+        if (last) { const int64_t oo = ((int64_t)(par ^ 1) * B + b) * M2N + eu; p.c2[oo] = c2; p.h2[oo] = h2; }
+      }
+    }
+    MPROF(13);
+    gather_vec<NB>(gr + G.dout, gbs, M2N, tag, B, tid, err, dead, [&](int b, int i, float v) {
+      XK[b * M2N + i] = v;
+      float* hs = X2 + b * 512 + M2N + i;
+      *hs = (1.f - zh) * v + zh * *hs;
+    });
+    MPROF(14);
+    // ================= G2: mel | stop projection (split) of the decoder LSTM output -> y, the next step's fed frame
+    have_p0 = fold && !last;      // (the last step of a launch hands over through yout: the next launch starts unfolded)
+    if (have_p0) {
+      split_mul_fb<NB, SPK>(wou, wfh, wfl, XK, NO, P0, bt + 32, bt + 168, gr + G.y, gr + G.p0, gbs, tag, wg, rs, tid, sx, spk);
+      MPROF(21);
+      // y (waves 0..2: NO <= 192) and the next step's p0 (waves 3..6) in ONE gather phase
+      if (wave < 3) {
+        const int beg = 64 * wave, cnt = min(64, NO - beg);
+#pragma unroll
+        for (int b = 0; b < NB; ++b) gather_poll<1>(gr + b * gbs + G.y + beg, cnt, tag, lane, [&](int i, float v) { yv[b * M2NO + beg + i] = v; }, err, dead);
+      } else if (wave < 7) {
+        const int beg = 64 * (wave - 3), cnt = min(64, P0 - beg);
+#pragma unroll
+        for (int b = 0; b < NB; ++b) gather_poll<1>(gr + b * gbs + G.p0 + beg, cnt, tag + 1u, lane, [&](int i, float v) { vb[b * M2N + beg + i] = v; }, err, dead);
+      }
+      lds_barrier();
+    } else {
+      split_mul<NB>(wou, XK, M2N, NO, bt + 32, SATT_ACT_NONE, nullptr, 0, gr + G.y, gbs, tag, wg, B, rs, tid, sx);
+      MPROF(21);
+      gather_vec<NB>(gr + G.y, gbs, NO, tag, B, tid, err, dead, [&](int b, int i, float v) { yv[b * M2NO + i] = v; });
+    }
+    MPROF(22);
+    if (wg == 3 % M2G) {
+      for (int i = tid; i < NB * NO; i += M2T) { const int b = i / NO, c = i - b * NO; if (b < B) p.yout[((int64_t)b * (p.Td + 1) + t + 1) * NO + c] = yv[b * M2NO + c]; }
+    }
+    // stop rule: every workgroup holds the same frame bits and takes the same decision (dec_mega2_k)
+    bool fire = false;
+    if (p.flag && !p.tin && t > p.min_steps) {
+      fire = true;
+      for (int b = 0; b < B; ++b) fire = fire && (1.f / (1.f + __expf(-yv[b * M2NO + NO - 1])) > p.stop_threshold);
+    }
+    if (wg == 0 && tid == 0) {
+      if (fire) *p.flag = t + 1;
+      *p.step = t + 1; p.step[1] = t + 1;
+    }
+    if (fire) break;
+    if (last) {
+      // hand-over to the launch-per-layer path: the context of the last step (buffer t & 1, V1 columns), column tid >> 4 of the own share
+      const int cw = (V1 + M2G - 1) / M2G, c = wg * cw + (tid >> 4), rp = tid & 15;
+      if ((tid >> 4) < cw && c < V1) {
+        for (int b = 0; b < B; ++b) {
+          const float* vs = p.values1 + (int64_t)b * Ti * V1 + c;
+          const float* al = e1 + b * M2TI;
+          float acc = 0.f;
+          for (int r = rp; r < Ti; r += 16) acc += al[r] * vs[(int64_t)r * V1];
+          SATT_DPP_ADD(acc, 0xB1); SATT_DPP_ADD(acc, 0x4E); SATT_DPP_ADD(acc, 0x141); SATT_DPP_ADD(acc, 0x140);
+          if (rp == 0) p.ctx[((int64_t)par * B + b) * V1 + c] = acc;
+        }
+      }
+    }
+    MPROF(23);
+#ifdef SATT_MEGA_PROF
+    if (wg == satt_mega2_prof_wg && threadIdx.x == 0) { const unsigned long long c_ = clock64(); satt_mega2_prof[30] += c_ - mp_clk; mp_clk = c_; }
+#endif
+  }
+}
 
 }  // namespace
 
@@ -1199,14 +1780,28 @@ extern "C" int satt_dec_mega2_prof_read(unsigned long long* host32, int reset) {
 
 // floats of the exchange buffer `part` of satt_dec_mega_params (two floats per granule)
 extern "C" int64_t satt_dec_mega_scratch_floats(int B, int heads, int hd) {
+  if (B >= 1 && heads == 0 && hd == 0) return 2 * (int64_t)B * gls_of(true).total;      // the single-source form (no heads)
   if (heads < 1 || B < 1 || heads * hd != M2N) return 0;
   return 2 * (int64_t)B * gl_of(hd, true).total;      // (the multi-speaker layout: the plain one is a prefix of it per sample)
 }
+
+namespace {
+// the single-source form is keyed on the block itself; a block that is only half single (Ds == 0 with a second memory, or the
+// reverse) is neither form and is refused by the dual form's conditions
+inline bool mega_single(const satt_dec_mega_params& p) { return p.Ds == 0 && p.heads == 0 && p.U2 == 0 && p.V2 == 0; }
+}  // namespace
 
 // shapes the kernel takes (pointers are checked by satt_dec_mega)
 extern "C" int satt_dec_mega_supported(const satt_dec_mega_params* pp) {
   if (!pp) return 0;
   const satt_dec_mega_params& p = *pp;
+  if (mega_single(p))      // the single-source form (dec_mega2_single_k): its own widths and its own LDS layout
+    return p.B >= 1 && p.B <= 2 && p.Td >= 1 && p.Ti >= 1 && p.Ti <= M2TI && (p.Ti + M2G - 1) / M2G <= 8 && p.A == M2N && p.D == M2N &&
+           p.U1 % 4 == 0 && p.U1 >= 8 && p.U1 <= M2N && p.V1 >= 1 && p.V1 <= 32 * M2G &&
+           p.P0 >= 8 && p.P0 <= M2N && p.P0 % 8 == 0 && p.P1 >= 8 && p.P1 <= M2N && p.P1 % 8 == 0 &&
+           p.feed >= 1 && p.feed <= M2N && p.feed + 1 <= p.NO && p.NO <= M2NO && p.ldout % 8 == 0 && p.ldout >= p.NO &&
+           p.kernel >= 1 && p.kernel <= 16 && p.filters >= 1 && p.filters <= 8 &&
+           mega2s_lds_bytes(p.B <= 1 ? 1 : 2, p.Ti) <= 160 * 1024;
   const int hd = p.heads > 0 ? M2N / p.heads : 0, UQ = p.U1 + p.U2, CT = p.V1 + p.V2;
   return p.B >= 1 && p.B <= 2 && p.Td >= 1 && p.Ti >= 1 && p.Ti <= M2TI && (p.Ti + M2G - 1) / M2G <= 8 &&
          p.A == M2N && p.D == M2N && p.Ds == M2N && p.heads >= 2 && M2G % p.heads == 0 && p.heads * hd == M2N &&
@@ -1222,6 +1817,9 @@ extern "C" int satt_dec_mega_supported(const satt_dec_mega_params* pp) {
 extern "C" int satt_dec_mega_variant(const satt_dec_mega_params* pp) {
   if (!pp || !satt_dec_mega_supported(pp)) return -1;
   const satt_dec_mega_params& p = *pp;
+  if (mega_single(p))
+    return SATT_MEGA_VAR_SINGLE | (p.B <= 1 && p.Ti <= M2TR ? SATT_MEGA_VAR_TABLES_LDS : 0) | (p.sproj ? SATT_MEGA_VAR_SPEAKER : 0) |
+           (p.B > 1 ? SATT_MEGA_VAR_TWO_SAMPLES : 0);
   const bool lj = p.U1 == 224 && p.U2 == 32 && p.V1 == 256 && p.V2 == 32 && p.heads == 2 && p.NO == 161 && p.feed == 80 && p.P0 == 256 &&
                   p.P1 == 128 && p.kernel == 10 && p.filters == 5 && getenv("SATT_DECODE_GENERIC") == nullptr;
   return (p.B <= 1 && p.Ti <= M2TR ? SATT_MEGA_VAR_TABLES_LDS : 0) | (lj ? SATT_MEGA_VAR_LJ : 0) | (p.sproj ? SATT_MEGA_VAR_SPEAKER : 0) |
@@ -1237,12 +1835,42 @@ inline bool opt_drop(const satt_dec_mega_opt_params* o) { return o && o->drop_th
 extern "C" int satt_dec_mega_opt_variant(const satt_dec_mega_params* pp, const satt_dec_mega_opt_params* opt) {
   const int var = satt_dec_mega_variant(pp);
   if (var < 0) return var;
+  if ((var & SATT_MEGA_VAR_SINGLE) && (opt_agent(opt) || opt_drop(opt))) return -1;      // the single form takes no options
   return var | (opt_agent(opt) ? SATT_MEGA_VAR_AGENT : 0) | (opt_drop(opt) ? SATT_MEGA_VAR_DROPOUT : 0);
 }
 
 extern "C" int satt_dec_mega_opt(const satt_dec_mega_params* pp, const satt_dec_mega_opt_params* opt, void* stream) {
   if (!pp || !satt_dec_mega_supported(pp) || pp->nsteps < 1) return SATT_E_UNSUPPORTED;
   const satt_dec_mega_params& p = *pp;
+  if (mega_single(p)) {      // the single-source form: its own pointer set (those of the second memory and of the self-attention block are not read)
+    if (opt_agent(opt) || opt_drop(opt)) return SATT_E_UNSUPPORTED;
+    if (!p.Wp0 || !p.Wp1 || !p.Wa || !p.Wq || !p.W1 || !p.W2 || !p.Wout || !p.bp0 || !p.bp1 || !p.ba || !p.b1l || !p.b2l || !p.bout ||
+        !p.locF || !p.locFb || !p.locU || !p.v1 || !p.b1 || !p.lengths || !p.keys1 || !p.values1 || !p.ca || !p.ha || !p.c1 || !p.h1 ||
+        !p.c2 || !p.h2 || !p.a_state || !p.alpha_state || !p.ctx || !p.yout || !p.align1 || !p.part || !p.ctab || !p.step || !p.err)
+      return SATT_E_BADARG;
+    if (p.sproj && (!p.Wp02 || !p.bp02)) return SATT_E_BADARG;
+    hipStream_t s = (hipStream_t)stream;
+    const int var = satt_dec_mega_variant(pp);
+    const int NB = (var & SATT_MEGA_VAR_TWO_SAMPLES) ? 2 : 1;
+    const size_t smem = mega2s_lds_bytes(NB, p.Ti);
+    static const int spread = [] { const char* e = getenv("SATT_DECODE_ONE_XCD"); return (e && atoi(e) == 0) ? 1 : 8; }();
+#define SATT_MEGA2S_(NBV, TR, SP)                                                                                                         \
+  do {                                                                                                                                    \
+    if (hipFuncSetAttribute((const void*)dec_mega2_single_k<NBV, TR, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) { \
+      (void)hipGetLastError();                                                                                                            \
+      return SATT_E_LAUNCH;                                                                                                               \
+    }                                                                                                                                     \
+    hipLaunchKernelGGL((dec_mega2_single_k<NBV, TR, SP>), dim3(M2G * spread), dim3(M2T), smem, s, p, spread);                              \
+  } while (0)
+#define SATT_MEGA2S(NBV, TR) do { if (var & SATT_MEGA_VAR_SPEAKER) SATT_MEGA2S_(NBV, TR, true); else SATT_MEGA2S_(NBV, TR, false); } while (0)
+    if (var & SATT_MEGA_VAR_TABLES_LDS) SATT_MEGA2S(1, true);
+    else if (NB == 1) SATT_MEGA2S(1, false);
+    else SATT_MEGA2S(2, false);
+#undef SATT_MEGA2S_
+#undef SATT_MEGA2S
+    SATT_LAUNCH_CHECK();
+    return SATT_OK;
+  }
   if (!p.Wp0 || !p.Wp1 || !p.Wa || !p.Wq || !p.W1 || !p.W2 || !p.Wkvq || !p.Wot || !p.Wout || !p.bp0 || !p.bp1 || !p.ba || !p.b1l ||
       !p.b2l || !p.bkvq || !p.bot || !p.bout || !p.locF || !p.locFb || !p.locU || !p.v1 || !p.b1 || !p.v2 || !p.lengths || !p.keys1 ||
       !p.values1 || !p.keys2 || !p.values2 || !p.ca || !p.ha || !p.c1 || !p.h1 || !p.c2 || !p.h2 || !p.a_state || !p.alpha_state ||

@@ -54,14 +54,23 @@ class DecodeSession:
         nm, r = c.num_mels, c.r
         feed, NO = nm * c.n_feed_frame, nm * r + 1
         self._mega_shape = None
-        if (self.MEGA and use_graph and not forced and c.dual and len(c.dec_prenet) == 2 and Ds and c.dec_sa_num_hop == 1 and
+        # The baseline model (one source, no decoder self-attention) is offered as the kernel's SINGLE-SOURCE form: a block with
+        # Ds = heads = U2 = V2 = 0.  With the transition agent or live inference dropout it stays on the launch-per-layer path (the
+        # single form takes no options).
+        dual_form = c.dual and bool(Ds) and c.dec_sa_num_hop == 1
+        single_form = (not c.dual and not Ds and not c.transition_agent and
+                       not (c.apply_dropout_on_inference and c.dec_prenet_drop > 0))
+        self._mega_single = False
+        if (self.MEGA and use_graph and not forced and (dual_form or single_form) and len(c.dec_prenet) == 2 and
                 ops.get_precision() == "bf16" and B <= self.MEGA_MAX_B):
-            shape = dict(B=B, Td=Td, Ti=Ti, A=A, D=D, Ds=Ds, heads=c.dec_sa_heads, U1=U1, V1=V1, U2=U2, V2=V2, kernel=c.att_kernel,
+            sh2 = dict(Ds=Ds, heads=c.dec_sa_heads, U2=U2, V2=V2) if dual_form else dict(Ds=0, heads=0, U2=0, V2=0)
+            shape = dict(B=B, Td=Td, Ti=Ti, A=A, D=D, U1=U1, V1=V1, **sh2, kernel=c.att_kernel,
                          filters=c.att_filters, att1_mode=int(c.attention == "location_sensitive"), cumulative=int(c.cumulative_weights),
                          P0=c.dec_prenet[0], P1=c.dec_prenet[1], feed=feed, NO=NO, ldout=(NO + 7) // 8 * 8, zc=c.zc, zh=c.zh,
                          stop_threshold=float(stop_threshold), min_steps=int(min_steps))
             if ops.dec_mega_supported(ops.dec_mega_params(**shape)):
                 self._mega_shape = shape
+                self._mega_single = not dual_form
                 self.K = max(self.K, self.MEGA_STEPS)
         Tdp = self.Tdp = (Td + self.K - 1) // self.K * self.K          # whole graphs: rows past Td are scratch
         f32 = dict(dtype=torch.float32, device=dev)
@@ -191,14 +200,17 @@ class DecodeSession:
         self.mega = self.mega_opt = None
         self.ctab = self._ctw = None
         if self._mega_shape is not None:
-            from .params import sa_prefix
-            pre = sa_prefix("dec.sa", 0)
+            single = self._mega_single
             self._mega_err = torch.zeros(1, dtype=torch.int32, device=dev)          # sticky error word
-            self._mega_part = Z(max(1, ops.dec_mega_scratch_floats(B, c.dec_sa_heads, Ds // c.dec_sa_heads)))
+            self._mega_part = Z(max(1, ops.dec_mega_scratch_floats(B, 0, 0) if single else
+                                    ops.dec_mega_scratch_floats(B, c.dec_sa_heads, Ds // c.dec_sa_heads)))
             # context tables values W_c (the cells take  sum_r alpha_r (values_r W_c)  instead of ctx W_c):
             # [B * Ti][LSTM 1 x values1 | LSTM 1 x values2 | attention LSTM x values1 | attention LSTM x values2][4 * 256]
-            self.ctab = Z(B * Ti, 4 * 4 * D)
-            self._ctw = [Z(v, 4 * D) for v in (V1, V2, V1, V2)]
+            # (the single-source form: the two values1 tables, [B * Ti][LSTM 1 x values1 | attention LSTM x values1][4 * 256])
+            tabs = (V1, V1) if single else (V1, V2, V1, V2)
+            self.ctab = Z(B * Ti, len(tabs) * 4 * D)
+            self._ctw = [Z(v, 4 * D) for v in tabs]
+            Kf = D if single else Ds          # input width of the mel | stop projection: the fold's K
             # folded feedback (free running): pre-net layer 0 straight from the output transform's result - fed = the last `feed` mel
             # columns of y = vc Wout + bout is linear in vc, so relu(fed Wp0 + bp0) = relu(vc Wf + bf); Wf as bf16 hi + lo (refresh_folded)
             P0w = c.dec_prenet[0]
@@ -207,25 +219,31 @@ class DecodeSession:
             # the plain pre-net - and the layer's second Dense
             spk = {} if self.sproj is None else dict(sproj=self.sproj, Wp02=eng.W("dec.prenet0.W2").n, bp02=P["dec.prenet0.b2"])
             self._fb = None if (teacher or not self.MEGA_FOLD_FEEDBACK) else dict(
-                a=Z(Ds, feed), b=Z(feed, P0w), w=Z(Ds, P0w), t=Z(Ds, P0w), bias=Z(1, P0w),
-                hi=torch.zeros(Ds, P0w, dtype=torch.bfloat16, device=dev), lo=torch.zeros(Ds, P0w, dtype=torch.bfloat16, device=dev))
+                a=Z(Kf, feed), b=Z(feed, P0w), w=Z(Kf, P0w), t=Z(Kf, P0w), bias=Z(1, P0w),
+                hi=torch.zeros(Kf, P0w, dtype=torch.bfloat16, device=dev), lo=torch.zeros(Kf, P0w, dtype=torch.bfloat16, device=dev))
+            if single:          # (the pointers of the second memory and of the self-attention block stay NULL)
+                second = {}
+            else:
+                from .params import sa_prefix
+                pre = sa_prefix("dec.sa", 0)
+                second = dict(Wkvq=eng.W(pre + ".kvq.W").n, Wot=self.Wot_k[0], bkvq=P[pre + ".kvq.b"], bot=self.bot[0], v2=P["dec.att2.v"],
+                              keys2=self.keys2, values2=self.values2, align2=self.al2, kvq=self.kvqs[0])
             self.mega = ops.dec_mega_params(
                 **dict(self._mega_shape, Td=Tdp),
                 Wp0=eng.W("dec.prenet0.W").n, Wp1=eng.W("dec.prenet1.W").n, Wa=self.lstm_w["dec.att_lstm.W"], Wq=wq.n,
-                W1=self.lstm_w["dec.lstm1.W"], W2=self.lstm_w["dec.lstm2.W"], Wkvq=eng.W(pre + ".kvq.W").n, Wot=self.Wot_k[0],
+                W1=self.lstm_w["dec.lstm1.W"], W2=self.lstm_w["dec.lstm2.W"],
                 Wout=self.out_w, bp0=P["dec.prenet0.b"], bp1=P["dec.prenet1.b"], ba=P["dec.att_lstm.b"], b1l=P["dec.lstm1.b"],
-                b2l=P["dec.lstm2.b"], bkvq=P[pre + ".kvq.b"], bot=self.bot[0], bout=P["dec.out.b"],
+                b2l=P["dec.lstm2.b"], bout=P["dec.out.b"],
                 locF=P["dec.att1.F"], locFb=P["dec.att1.bF"], locU=P["dec.att1.U"], v1=P["dec.att1.v"], b1=P["dec.att1.b"],
-                v2=P["dec.att2.v"], lengths=self.lengths, keys1=self.keys1, values1=self.values1, keys2=self.keys2,
-                values2=self.values2, ca=ca, ha=ha, c1=c1, h1=h1, c2=c2, h2=h2, a_state=self.a_state,
-                alpha_state=self.alpha_state, ctx=self.ctx, yout=self.yout, tin=self.tin, align1=self.al1, align2=self.al2,
-                kvq=self.kvqs[0], part=self._mega_part, ctab=self.ctab, step=self.steps2, flag=None if teacher else self.flag,
+                lengths=self.lengths, keys1=self.keys1, values1=self.values1, ca=ca, ha=ha, c1=c1, h1=h1, c2=c2, h2=h2, a_state=self.a_state,
+                alpha_state=self.alpha_state, ctx=self.ctx, yout=self.yout, tin=self.tin, align1=self.al1, **second,
+                part=self._mega_part, ctab=self.ctab, step=self.steps2, flag=None if teacher else self.flag,
                 err=self._mega_err, **spk, **({} if self._fb is None else dict(Wfh=self._fb["hi"], Wfl=self._fb["lo"], bfb=self._fb["bias"])))
             assert ops.dec_mega_supported(self.mega)
             # options of the kernel (a block of their own; None: ops.dec_mega as ever).  Transition agent: the kernel forms no
             # context, so the context part of u's dot product comes from a per-utterance table values1 Wa[:V1]
             # (build_context_tables) and u crosses launches in u_state.  Dropout that stays on: the launch-per-layer masks (pdrop).
-            if c.transition_agent or (c.apply_dropout_on_inference and c.dec_prenet_drop > 0):
+            if not single and (c.transition_agent or (c.apply_dropout_on_inference and c.dec_prenet_drop > 0)):
                 agent = {}
                 if c.transition_agent:
                     self.agent_tab, self.u_state = Z(B * Ti, 1), Z(B)
@@ -383,12 +401,14 @@ class DecodeSession:
         # (speaker_to_decoder: the memories and the cells' context rows are V + mem_speaker wide)
         A, D, V1, V2, P1 = c.att_rnn_units, c.dec_units, c.cbhg_out_units + c.mem_speaker, c.sa_units + c.mem_speaker, c.dec_prenet[1]
         W1, Wa = self.lstm_w["dec.lstm1.W"], self.lstm_w["dec.att_lstm.W"]
-        rows = ((W1, A, V1), (W1, A + V1, V2), (Wa, P1, V1), (Wa, P1 + V1, V2))
-        for q, (W, r0, n) in enumerate(rows):
+        if self._mega_single:      # the two values1 tables: LSTM 1 rows [A, A + V1), attention-LSTM rows [P1, P1 + V1)
+            rows = ((W1, A, V1, self.values1), (Wa, P1, V1, self.values1))
+        else:
+            rows = ((W1, A, V1, self.values1), (W1, A + V1, V2, self.values2), (Wa, P1, V1, self.values1), (Wa, P1 + V1, V2, self.values2))
+        for q, (W, r0, n, x) in enumerate(rows):
             self._ctw[q].copy_(W[r0:r0 + n])
-            x = self.values1 if q % 2 == 0 else self.values2
-            ops.gemm(x.shape[0], 4 * D, n, x, n, self._ctw[q], 4 * D, 1, self.ctab[:, q * 4 * D:], 16 * D, prec=ops.PREC_F32)
-        if c.transition_agent:      # agent_tab[b][r] = values1[b, r] . Wa[:V1] (fp32 parameters, as the launch-per-layer step multiplies)
+            ops.gemm(x.shape[0], 4 * D, n, x, n, self._ctw[q], 4 * D, 1, self.ctab[:, q * 4 * D:], len(rows) * 4 * D, prec=ops.PREC_F32)
+        if c.transition_agent and not self._mega_single:      # agent_tab[b][r] = values1[b, r] . Wa[:V1] (fp32 parameters, as the launch-per-layer step multiplies)
             ops.gemm(self.values1.shape[0], 1, V1, self.values1, V1, self.eng.P["dec.att1.Wa"], 1, 1, self.agent_tab, 1, prec=ops.PREC_F32)
 
     def run_step(self):

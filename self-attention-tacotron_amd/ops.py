@@ -1170,6 +1170,7 @@ def dec_mega(p, nsteps):
 
 
 MEGA_VAR_AGENT, MEGA_VAR_DROPOUT = 16, 32      # include/satt_hip.h: SATT_MEGA_VAR_* of the option block
+MEGA_VAR_SINGLE = 64                           # the single-source form (the baseline model)
 
 
 def dec_mega_opt_params(agentW=None, agentb=None, agent_tab=None, u_state=None, drop=None, drop_T=0, drop_streams=(0, 0)):
