@@ -21,8 +21,17 @@
 // Same buffers and same math as the launch-per-layer path (csrc/decode.hip); selection: satt_dec_mega_supported (A = D = Ds = 256,
 // B <= 2, ...); granule tags are step + 1, the caller zeroes the granule buffer when it resets the step counter.  Single-buffered granules are
 // safe: between the consumption of X(t) and the production of X(t+1) lies at least one exchange every workgroup contributes to.
-// The baseline model (one attention source, no decoder self-attention) runs the SINGLE-SOURCE form, dec_mega2_single_k below: the same
-// helpers, eight exchanges, its own LDS and granule layout, and the granule argument re-derived for its chain.
+// The baseline model (one attention source, no decoder self-attention) runs the SINGLE-SOURCE form, dec_mega2_single_k below: eight
+// exchanges, its own LDS and granule layout, and the granule argument re-derived for its chain.
+// WHAT THE TWO KERNELS SHARE: the leaf helpers (split_mul / split_mul_fb / split_fill, gather_vec, slice_*, pin, lstm_unit,
+// mega_drop) and, on the host, one pointer list, one `spread` static and one launch function (mega_launch) behind both dispatch
+// ladders.  EVERY PHASE THEY HAVE IN COMMON IS WRITTEN OUT IN BOTH KERNELS, and a fix to one copy has to be made in the other: the
+// launch prologue (zeroing of every LDS word, placement handshake, staging, state loads), A1 / A2, the three cell steps, the
+// location features, phase C (requests, poll, softmax, recursion, write of al / e1), the history and hand-over stores, G2
+// (projection, yout, stop rule, step and flag words) and the hand-over contexts.  Each was moved into a __forceinline__ helper and
+// moved back: a helper's body is inlined behind the per-function early passes and meets the kernel in another instruction order,
+// and the registers and spills of these 5 000 - 19 000 instruction kernels, which are kept equal to the figure, did not come out
+// the same (profiles/decode_shared_phases_kernel_regs.txt has the figures per phase).
 #include <cstdlib>
 #include "cluster_xchg.h"
 
@@ -1191,7 +1200,9 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p,
 // V2 == 0 (keys2, values2, v2, align2, Wkvq, bkvq, Wot, bot, kvq are NULL and never read; heads / hd are never touched).  The same
 // machinery as dec_mega2_k - 32 persistent workgroups on one XCD, register-resident weights, sliced cells, split layers, granules
 // tagged step + 1, contexts folded into per-utterance tables - with the phases of the second mechanism and of the self-attention
-// block (E, F, G1) gone.  Eight exchanges per step:
+// block (E, F, G1) gone.  Shared with dec_mega2_k: the leaf helpers; the common phases (prologue, A1 / A2, cell steps, B2's location
+// features, C, history stores, G2, hand-over context) are this kernel's own copy of the dual kernel's statements - see the file
+// header, and keep the two in step.  Eight exchanges per step:
 //       p0 -> p1 -> [attention LSTM] hq -> pq -> [energies] e1 -> [softmax, LSTM 1] h1n -> [LSTM 2] dout -> [projection] y
 // (SPK: p0 -> p02 -> p1 is a ninth).  Folded feedback: the projection's input is dout, so Wf = Wout[:, fed columns] Wp0 has K = D and
 // split_mul_fb works on the gathered dout vector.
@@ -1789,27 +1800,25 @@ namespace {
 // the single-source form is keyed on the block itself; a block that is only half single (Ds == 0 with a second memory, or the
 // reverse) is neither form and is refused by the dual form's conditions
 inline bool mega_single(const satt_dec_mega_params& p) { return p.Ds == 0 && p.heads == 0 && p.U2 == 0 && p.V2 == 0; }
+// the shape conditions both forms share (batch, memory length, cell widths, pre-net, fed frame, projection, location layer)
+inline bool mega_common_shapes(const satt_dec_mega_params& p) {
+  return p.B >= 1 && p.B <= 2 && p.Td >= 1 && p.Ti >= 1 && p.Ti <= M2TI && (p.Ti + M2G - 1) / M2G <= 8 && p.A == M2N && p.D == M2N &&
+         p.U1 % 4 == 0 && p.V1 >= 1 && p.P0 >= 8 && p.P0 <= M2N && p.P0 % 8 == 0 && p.P1 >= 8 && p.P1 <= M2N && p.P1 % 8 == 0 &&
+         p.feed >= 1 && p.feed <= M2N && p.feed + 1 <= p.NO && p.NO <= M2NO && p.ldout % 8 == 0 && p.ldout >= p.NO &&
+         p.kernel >= 1 && p.kernel <= 16 && p.filters >= 1 && p.filters <= 8;
+}
 }  // namespace
 
 // shapes the kernel takes (pointers are checked by satt_dec_mega)
 extern "C" int satt_dec_mega_supported(const satt_dec_mega_params* pp) {
-  if (!pp) return 0;
+  if (!pp || !mega_common_shapes(*pp)) return 0;
   const satt_dec_mega_params& p = *pp;
   if (mega_single(p))      // the single-source form (dec_mega2_single_k): its own widths and its own LDS layout
-    return p.B >= 1 && p.B <= 2 && p.Td >= 1 && p.Ti >= 1 && p.Ti <= M2TI && (p.Ti + M2G - 1) / M2G <= 8 && p.A == M2N && p.D == M2N &&
-           p.U1 % 4 == 0 && p.U1 >= 8 && p.U1 <= M2N && p.V1 >= 1 && p.V1 <= 32 * M2G &&
-           p.P0 >= 8 && p.P0 <= M2N && p.P0 % 8 == 0 && p.P1 >= 8 && p.P1 <= M2N && p.P1 % 8 == 0 &&
-           p.feed >= 1 && p.feed <= M2N && p.feed + 1 <= p.NO && p.NO <= M2NO && p.ldout % 8 == 0 && p.ldout >= p.NO &&
-           p.kernel >= 1 && p.kernel <= 16 && p.filters >= 1 && p.filters <= 8 &&
-           mega2s_lds_bytes(p.B <= 1 ? 1 : 2, p.Ti) <= 160 * 1024;
+    return p.U1 >= 8 && p.U1 <= M2N && p.V1 <= 32 * M2G && mega2s_lds_bytes(p.B <= 1 ? 1 : 2, p.Ti) <= 160 * 1024;
   const int hd = p.heads > 0 ? M2N / p.heads : 0, UQ = p.U1 + p.U2, CT = p.V1 + p.V2;
-  return p.B >= 1 && p.B <= 2 && p.Td >= 1 && p.Ti >= 1 && p.Ti <= M2TI && (p.Ti + M2G - 1) / M2G <= 8 &&
-         p.A == M2N && p.D == M2N && p.Ds == M2N && p.heads >= 2 && M2G % p.heads == 0 && p.heads * hd == M2N &&
+  return p.Ds == M2N && p.heads >= 2 && M2G % p.heads == 0 && p.heads * hd == M2N &&
          hd >= 16 && hd <= M2HD && hd % 16 == 0 && M2T % (hd / 4) == 0 && M2T / (hd / 4) <= 32 && (hd / 16 == 4 || hd / 16 == 8) &&
-         p.U1 >= 1 && p.U1 % 4 == 0 && p.U2 >= 1 && p.U2 <= 64 && UQ <= M2N && UQ % 8 == 0 && p.V1 >= 1 && p.V2 >= 1 && CT <= 32 * M2G &&
-         p.P0 >= 8 && p.P0 <= M2N && p.P0 % 8 == 0 && p.P1 >= 8 && p.P1 <= M2N && p.P1 % 8 == 0 &&
-         p.feed >= 1 && p.feed <= M2N && p.feed + 1 <= p.NO && p.NO <= M2NO && p.ldout % 8 == 0 && p.ldout >= p.NO &&
-         p.kernel >= 1 && p.kernel <= 16 && p.filters >= 1 && p.filters <= 8 &&
+         p.U1 >= 1 && p.U2 >= 1 && p.U2 <= 64 && UQ <= M2N && UQ % 8 == 0 && p.V2 >= 1 && CT <= 32 * M2G &&
          mega2_lds_bytes(p.B <= 1 ? 1 : 2, p.Ti) <= 160 * 1024;
 }
 
@@ -1817,13 +1826,11 @@ extern "C" int satt_dec_mega_supported(const satt_dec_mega_params* pp) {
 extern "C" int satt_dec_mega_variant(const satt_dec_mega_params* pp) {
   if (!pp || !satt_dec_mega_supported(pp)) return -1;
   const satt_dec_mega_params& p = *pp;
-  if (mega_single(p))
-    return SATT_MEGA_VAR_SINGLE | (p.B <= 1 && p.Ti <= M2TR ? SATT_MEGA_VAR_TABLES_LDS : 0) | (p.sproj ? SATT_MEGA_VAR_SPEAKER : 0) |
-           (p.B > 1 ? SATT_MEGA_VAR_TWO_SAMPLES : 0);
+  const int form = (p.B <= 1 && p.Ti <= M2TR ? SATT_MEGA_VAR_TABLES_LDS : 0) | (p.sproj ? SATT_MEGA_VAR_SPEAKER : 0) | (p.B > 1 ? SATT_MEGA_VAR_TWO_SAMPLES : 0);
+  if (mega_single(p)) return SATT_MEGA_VAR_SINGLE | form;
   const bool lj = p.U1 == 224 && p.U2 == 32 && p.V1 == 256 && p.V2 == 32 && p.heads == 2 && p.NO == 161 && p.feed == 80 && p.P0 == 256 &&
                   p.P1 == 128 && p.kernel == 10 && p.filters == 5 && getenv("SATT_DECODE_GENERIC") == nullptr;
-  return (p.B <= 1 && p.Ti <= M2TR ? SATT_MEGA_VAR_TABLES_LDS : 0) | (lj ? SATT_MEGA_VAR_LJ : 0) | (p.sproj ? SATT_MEGA_VAR_SPEAKER : 0) |
-         (p.B > 1 ? SATT_MEGA_VAR_TWO_SAMPLES : 0);
+  return form | (lj ? SATT_MEGA_VAR_LJ : 0);
 }
 
 namespace {
@@ -1839,74 +1846,63 @@ extern "C" int satt_dec_mega_opt_variant(const satt_dec_mega_params* pp, const s
   return var | (opt_agent(opt) ? SATT_MEGA_VAR_AGENT : 0) | (opt_drop(opt) ? SATT_MEGA_VAR_DROPOUT : 0);
 }
 
+namespace {
+// one XCD (grid 8 x 32, every eighth workgroup works: see dec_mega2_k) unless SATT_DECODE_ONE_XCD=0
+inline int mega_spread() {
+  static const int spread = [] { const char* e = getenv("SATT_DECODE_ONE_XCD"); return (e && atoi(e) == 0) ? 1 : 8; }();
+  return spread;
+}
+// one instantiation of either kernel: its dynamic LDS size, then the launch
+template <class... KA, class... A>
+int mega_launch(void (*kernel)(KA...), size_t smem, hipStream_t s, const satt_dec_mega_params& p, const A&... more) {
+  const int spread = mega_spread();
+  if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
+    (void)hipGetLastError();
+    return SATT_E_LAUNCH;
+  }
+  hipLaunchKernelGGL(kernel, dim3(M2G * spread), dim3(M2T), smem, s, p, spread, more...);
+  SATT_LAUNCH_CHECK();
+  return SATT_OK;
+}
+}  // namespace
+
 extern "C" int satt_dec_mega_opt(const satt_dec_mega_params* pp, const satt_dec_mega_opt_params* opt, void* stream) {
   if (!pp || !satt_dec_mega_supported(pp) || pp->nsteps < 1) return SATT_E_UNSUPPORTED;
   const satt_dec_mega_params& p = *pp;
-  if (mega_single(p)) {      // the single-source form: its own pointer set (those of the second memory and of the self-attention block are not read)
-    if (opt_agent(opt) || opt_drop(opt)) return SATT_E_UNSUPPORTED;
-    if (!p.Wp0 || !p.Wp1 || !p.Wa || !p.Wq || !p.W1 || !p.W2 || !p.Wout || !p.bp0 || !p.bp1 || !p.ba || !p.b1l || !p.b2l || !p.bout ||
-        !p.locF || !p.locFb || !p.locU || !p.v1 || !p.b1 || !p.lengths || !p.keys1 || !p.values1 || !p.ca || !p.ha || !p.c1 || !p.h1 ||
-        !p.c2 || !p.h2 || !p.a_state || !p.alpha_state || !p.ctx || !p.yout || !p.align1 || !p.part || !p.ctab || !p.step || !p.err)
-      return SATT_E_BADARG;
-    if (p.sproj && (!p.Wp02 || !p.bp02)) return SATT_E_BADARG;
-    hipStream_t s = (hipStream_t)stream;
-    const int var = satt_dec_mega_variant(pp);
-    const int NB = (var & SATT_MEGA_VAR_TWO_SAMPLES) ? 2 : 1;
-    const size_t smem = mega2s_lds_bytes(NB, p.Ti);
-    static const int spread = [] { const char* e = getenv("SATT_DECODE_ONE_XCD"); return (e && atoi(e) == 0) ? 1 : 8; }();
-#define SATT_MEGA2S_(NBV, TR, SP)                                                                                                         \
-  do {                                                                                                                                    \
-    if (hipFuncSetAttribute((const void*)dec_mega2_single_k<NBV, TR, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) { \
-      (void)hipGetLastError();                                                                                                            \
-      return SATT_E_LAUNCH;                                                                                                               \
-    }                                                                                                                                     \
-    hipLaunchKernelGGL((dec_mega2_single_k<NBV, TR, SP>), dim3(M2G * spread), dim3(M2T), smem, s, p, spread);                              \
-  } while (0)
-#define SATT_MEGA2S(NBV, TR) do { if (var & SATT_MEGA_VAR_SPEAKER) SATT_MEGA2S_(NBV, TR, true); else SATT_MEGA2S_(NBV, TR, false); } while (0)
-    if (var & SATT_MEGA_VAR_TABLES_LDS) SATT_MEGA2S(1, true);
-    else if (NB == 1) SATT_MEGA2S(1, false);
-    else SATT_MEGA2S(2, false);
-#undef SATT_MEGA2S_
-#undef SATT_MEGA2S
-    SATT_LAUNCH_CHECK();
-    return SATT_OK;
-  }
-  if (!p.Wp0 || !p.Wp1 || !p.Wa || !p.Wq || !p.W1 || !p.W2 || !p.Wkvq || !p.Wot || !p.Wout || !p.bp0 || !p.bp1 || !p.ba || !p.b1l ||
-      !p.b2l || !p.bkvq || !p.bot || !p.bout || !p.locF || !p.locFb || !p.locU || !p.v1 || !p.b1 || !p.v2 || !p.lengths || !p.keys1 ||
-      !p.values1 || !p.keys2 || !p.values2 || !p.ca || !p.ha || !p.c1 || !p.h1 || !p.c2 || !p.h2 || !p.a_state || !p.alpha_state ||
-      !p.ctx || !p.yout || !p.align1 || !p.align2 || !p.kvq || !p.part || !p.ctab || !p.step || !p.err) return SATT_E_BADARG;
+  const bool single = mega_single(p);
+  if (single && (opt_agent(opt) || opt_drop(opt))) return SATT_E_UNSUPPORTED;
+  // what both forms read ...
+  if (!p.Wp0 || !p.Wp1 || !p.Wa || !p.Wq || !p.W1 || !p.W2 || !p.Wout || !p.bp0 || !p.bp1 || !p.ba || !p.b1l || !p.b2l || !p.bout ||
+      !p.locF || !p.locFb || !p.locU || !p.v1 || !p.b1 || !p.lengths || !p.keys1 || !p.values1 || !p.ca || !p.ha || !p.c1 || !p.h1 ||
+      !p.c2 || !p.h2 || !p.a_state || !p.alpha_state || !p.ctx || !p.yout || !p.align1 || !p.part || !p.ctab || !p.step || !p.err)
+    return SATT_E_BADARG;
+  // ... and the dual form's second memory and self-attention block (NULL and never read in the single-source form)
+  if (!single && (!p.Wkvq || !p.Wot || !p.bkvq || !p.bot || !p.v2 || !p.keys2 || !p.values2 || !p.align2 || !p.kvq)) return SATT_E_BADARG;
   if (p.sproj && (!p.Wp02 || !p.bp02)) return SATT_E_BADARG;      // multi-speaker pre-net: its second Dense comes with the speaker term
   // options: the agent belongs to the forward recursion and comes with its bias, table and state word; dropout with its seed word
   if (opt_agent(opt) && (!opt->agentb || !opt->agent_tab || !opt->u_state || p.att1_mode != 0)) return SATT_E_BADARG;
   if (opt_drop(opt) && (!opt->drop_seed || opt->drop_T < 1)) return SATT_E_BADARG;
   hipStream_t s = (hipStream_t)stream;
   const int var = satt_dec_mega_opt_variant(pp, opt);
-  const bool lj = var & SATT_MEGA_VAR_LJ, spk = var & SATT_MEGA_VAR_SPEAKER, has_opt = var & (SATT_MEGA_VAR_AGENT | SATT_MEGA_VAR_DROPOUT);
+  const bool tables = var & SATT_MEGA_VAR_TABLES_LDS, lj = var & SATT_MEGA_VAR_LJ, spk = var & SATT_MEGA_VAR_SPEAKER;
+  const bool has_opt = var & (SATT_MEGA_VAR_AGENT | SATT_MEGA_VAR_DROPOUT);
   const int NB = (var & SATT_MEGA_VAR_TWO_SAMPLES) ? 2 : 1;
-  const size_t smem = mega2_lds_bytes(NB, p.Ti, has_opt);
+  const size_t smem = single ? mega2s_lds_bytes(NB, p.Ti) : mega2_lds_bytes(NB, p.Ti, has_opt);
   if (smem > 160 * 1024) return SATT_E_UNSUPPORTED;      // (B = 2 with options: 163 104 bytes - every supported shape fits)
-  // one XCD (grid 8 x 32, every eighth workgroup works: see the kernel) unless SATT_DECODE_ONE_XCD=0
-  static const int spread = [] { const char* e = getenv("SATT_DECODE_ONE_XCD"); return (e && atoi(e) == 0) ? 1 : 8; }();
-#define SATT_MEGA2_(NBV, TR, LJV, SP, OP, OARG)                                                                                           \
-  do {                                                                                                                                    \
-    if (hipFuncSetAttribute((const void*)dec_mega2_k<NBV, TR, LJV, SP, OP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) { \
-      (void)hipGetLastError();                                                                                                            \
-      return SATT_E_LAUNCH;                                                                                                               \
-    }                                                                                                                                     \
-    hipLaunchKernelGGL((dec_mega2_k<NBV, TR, LJV, SP, OP>), dim3(M2G * spread), dim3(M2T), smem, s, p, spread, OARG);                     \
-  } while (0)
-#define SATT_MEGA2O(NBV, TR, LJV, SP) do { if (has_opt) SATT_MEGA2_(NBV, TR, LJV, SP, true, *opt); else SATT_MEGA2_(NBV, TR, LJV, SP, false, MegaNoOpt()); } while (0)
-#define SATT_MEGA2L(NBV, TR, SP) do { if (lj) SATT_MEGA2O(NBV, TR, true, SP); else SATT_MEGA2O(NBV, TR, false, SP); } while (0)
-#define SATT_MEGA2(NBV, TR) do { if (spk) SATT_MEGA2L(NBV, TR, true); else SATT_MEGA2L(NBV, TR, false); } while (0)
-  if (var & SATT_MEGA_VAR_TABLES_LDS) SATT_MEGA2(1, true);
-  else if (NB == 1) SATT_MEGA2(1, false);
-  else SATT_MEGA2(2, false);
-#undef SATT_MEGA2_
+#define SATT_MEGA2S(NBV, TR) (spk ? mega_launch(dec_mega2_single_k<NBV, TR, true>, smem, s, p) : mega_launch(dec_mega2_single_k<NBV, TR, false>, smem, s, p))
+#define SATT_MEGA2O(NBV, TR, LJV, SP) \
+  (has_opt ? mega_launch(dec_mega2_k<NBV, TR, LJV, SP, true>, smem, s, p, *opt) : mega_launch(dec_mega2_k<NBV, TR, LJV, SP, false>, smem, s, p, MegaNoOpt()))
+#define SATT_MEGA2L(NBV, TR, SP) (lj ? SATT_MEGA2O(NBV, TR, true, SP) : SATT_MEGA2O(NBV, TR, false, SP))
+#define SATT_MEGA2D(NBV, TR) (spk ? SATT_MEGA2L(NBV, TR, true) : SATT_MEGA2L(NBV, TR, false))
+  // (the ladders name the 30 instantiations in the order they always had, the single form's first: the device compiler emits them
+  //  in that order, and listings of two revisions compare line by line)
+#define SATT_MEGA2(K) (tables ? K(1, true) : NB == 1 ? K(1, false) : K(2, false))
+  return single ? SATT_MEGA2(SATT_MEGA2S) : SATT_MEGA2(SATT_MEGA2D);
+#undef SATT_MEGA2S
 #undef SATT_MEGA2O
 #undef SATT_MEGA2L
+#undef SATT_MEGA2D
 #undef SATT_MEGA2
-  SATT_LAUNCH_CHECK();
-  return SATT_OK;
 }
 
 extern "C" int satt_dec_mega(const satt_dec_mega_params* pp, void* stream) { return satt_dec_mega_opt(pp, nullptr, stream); }

@@ -255,9 +255,10 @@ class DecodeSession:
         if self.mega is not None:
             # One throw-away launch (zero memories, discarded by the reset() of the first utterance), as the graph path below runs its
             # step once outside the capture: module load and the cold start of the 32 persistent workgroups stay out of the first
-            # utterance.  r5: one run in ~30 fresh processes had the FIRST utterance of the first session off by 7e-3 in mel (bar
-            # 2.2e-3; every other run of it is bit-identical, 24 dedicated fresh-box trials did not reproduce it) - a start-up race we
-            # have not located; later utterances never showed it.
+            # utterance.  It is a matter of time only, not of results: the first-utterance deviation r5 saw (one run in ~30 fresh
+            # processes off by 7e-3 in mel) was located and fixed in r6 - an LDS word read before it was written, the kernel now
+            # zeroes its whole allocation - and this launch never masked it; the cold tests run without it
+            # (tests/test_decode_cold_gpu.py: cold == warm).
             if __import__("os").environ.get("SATT_DECODE_NO_WARMUP") != "1":      # (the switch: tools/decode_stress.py measures the cold case)
                 self.reset()
                 self.lengths.fill_(Ti)

@@ -38,6 +38,8 @@ MODELS = {
     # one fed-back frame per step (examples/ljspeech): the widths the kernel's compile-time specialisation is keyed on
     "agent, one fed frame": dict(transition_agent=True, n_feed_frame=1),
     "dropout, one fed frame": dict(apply_dropout_on_inference=True, n_feed_frame=1),
+    "plain, one fed frame": dict(n_feed_frame=1),
+    "dropout+speakers, one fed frame": dict(SPK, apply_dropout_on_inference=True, n_feed_frame=1),
     "wide": WIDE,
     "wide+resize": dict(WIDE, speaker_proj_dim=24),
 }
@@ -384,3 +386,23 @@ def test_option_kernels_do_not_depend_on_what_the_lds_held_before_the_launch(mod
     assert dirty["steps"] == clean["steps"]
     for k in KEYS:
         assert torch.equal(dirty[k], clean[k]), k
+
+
+# ---- 8: every instantiation of the kernel is launched by a test
+@pytest.mark.parametrize("model,B,Ti,bits,lj", [
+    ("plain, one fed frame", 1, 140, "", True),                                        # dec_mega2_k<1, false, LJ, -, ->
+    ("dropout+speakers", 1, 33, "DROPOUT SPEAKER", False),                             # <1, true, -, SPK, OPT>
+    ("dropout+speakers", 1, 140, "DROPOUT SPEAKER", False),                            # <1, false, -, SPK, OPT>
+    ("dropout+speakers, one fed frame", 1, 33, "DROPOUT SPEAKER", True),               # <1, true, LJ, SPK, OPT>
+    ("dropout+speakers, one fed frame", 1, 140, "DROPOUT SPEAKER", True),              # <1, false, LJ, SPK, OPT>
+    ("dropout+speakers, one fed frame", 2, 57, "DROPOUT SPEAKER", True)])              # <2, false, LJ, SPK, OPT>
+def test_instantiations_no_other_test_launches(model, B, Ti, bits, lj):
+    """the instantiations of dec_mega2_k that neither the tests above nor tests/test_inference_gpu.py, test_decode_golden_gpu.py and
+    test_decode_speaker_gpu.py launch (profiles/decode_shared_phases_kernel_regs.txt lists the test of each of the 30): 9 / 10 / 19
+    steps with 8 steps per launch against the launch-per-layer path, this file's bar"""
+    from satt_amd import ops
+    mask = 0
+    for b in bits.split():
+        mask |= getattr(ops, "MEGA_VAR_" + b)
+    kw = dict(seed=7) if "DROPOUT" in bits else {}
+    against_launch_per_layer(model, B, "free", "tables", mask, Ti=Ti, lj=lj, **kw)

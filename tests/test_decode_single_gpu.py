@@ -143,7 +143,8 @@ def test_single_source_kernel_with_an_attention_width_that_is_no_multiple_of_eig
 
 
 @pytest.mark.parametrize("model,B,Ti", [("speakers", 1, 33), ("speakers", 2, 57), ("speakers, two fed frames", 2, 57),
-                                        ("speakers, one fed frame", 1, 33)])
+                                        ("speakers, one fed frame", 1, 33),
+                                        ("speakers", 1, 140)])          # (tables in global memory with the speaker term)
 def test_single_source_kernel_with_the_multi_speaker_prenet(model, B, Ti):
     eng, cfg = engine(model)
     new = compare(eng, cfg, B, Ti, 12, speaker=True)
