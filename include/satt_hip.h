@@ -835,6 +835,46 @@ typedef struct {
 /* opt == NULL or both options off: satt_dec_mega(p, stream) / satt_dec_mega_variant(p) */
 int satt_dec_mega_opt(const satt_dec_mega_params* p, const satt_dec_mega_opt_params* opt, void* stream);
 int satt_dec_mega_opt_variant(const satt_dec_mega_params* p, const satt_dec_mega_opt_params* opt);
+/* ---- group mode of the persistent decode step: batches of 3 .. 16, one PAIR of samples per XCD.  A launch of satt_dec_mega keeps
+ * one XCD busy (32 workgroups, every eighth of a grid of 8 x 32) and the other seven return at once.  A group launch keeps up to
+ * eight of them busy: group g - the workgroups with blockIdx % 8 == g - decodes samples 2 g and 2 g + 1 with the statements that
+ * decode a B = 2 utterance, from a parameter block of its own.  The groups never exchange anything.
+ *   Each block is a COMPLETE block of a B = 2 problem (p.B == 2): its per-sample pointers are the batch tensors advanced by b0
+ * samples (lengths, keys / values, yout, tin, align1 / align2, kvq, ctab, sproj; o.agent_tab, o.u_state), the double-buffered
+ * state (ca .. h2, a_state, alpha_state, ctx: [2][2][...]), the exchange region `part`
+ * (satt_dec_mega_scratch_floats(2, heads, head_dim) floats) and the two `step` words are the group's OWN, `err` may be one shared
+ * sticky word.  has_opt != 0: `o` holds the group's options (every group the same ones); pre-net dropout draws the mask of batch
+ * row b0 + b, i.e. the masks the launch-per-layer path draws for the whole batch.  p.flag must be NULL: a group cannot evaluate the
+ * stop rule (it fires when ALL samples of the batch exceed the threshold at the same step), so a group launch always runs its
+ * nsteps and the caller runs satt_dec_stop_scan behind it.
+ *   The blocks are read by the kernel from DEVICE memory (device_blocks: ngroups consecutive satt_dec_mega_group, written by the
+ * caller before the launch and constant while it runs); host_blocks is the caller's host copy of the same bytes, which is what
+ * the entry points validate.  With SATT_DECODE_ONE_XCD=0 the grid is 32 x ngroups, group = blockIdx % ngroups, and the exchanges
+ * are write-through.  The placement handshake runs per group.  A group launch needs all 32 CUs of each XCD it uses: a kernel of
+ * another stream or process that occupies one turns into the exchange time-out (the sticky error word). */
+typedef struct {
+  satt_dec_mega_params p;
+  satt_dec_mega_opt_params o;             /* read where has_opt != 0 */
+  int has_opt;
+  int b0;                                 /* batch row of the group's first sample (2 g) */
+} satt_dec_mega_group;
+#define SATT_MEGA_GROUPS_MAX 8
+#define SATT_MEGA_VAR_GROUPS 128     /* group mode (satt_dec_mega_groups) */
+/* 1: ngroups in 1 .. 8, every block passes satt_dec_mega_supported with B == 2 and takes its options (the single-source form takes
+ * none), and all blocks agree in every shape field, in the form (single / dual, speaker pre-net, options, fed inputs, folded
+ * feedback) and in nsteps */
+int satt_dec_mega_groups_supported(const satt_dec_mega_group* host_blocks, int ngroups);
+/* the instantiation of a group launch: the SATT_MEGA_VAR_* bits of a block | SATT_MEGA_VAR_GROUPS; -1 where it is not taken */
+int satt_dec_mega_groups_variant(const satt_dec_mega_group* host_blocks, int ngroups);
+/* ngroups x satt_dec_mega_scratch_floats(2, heads, head_dim): group g's `part` may be slice g of one buffer of this size */
+int64_t satt_dec_mega_groups_scratch_floats(int ngroups, int heads, int head_dim);
+int satt_dec_mega_groups(const satt_dec_mega_group* host_blocks, const void* device_blocks, int ngroups, void* stream);
+/* stop rule of a batch behind a launch that evaluated none: scans the output rows of steps t0 .. t0 + nsteps - 1 (row t + 1 of
+ * yout [B][rows][NO] is step t's; t0 + nsteps < rows) for the first step t > min_steps at which EVERY one of the B samples has
+ * 1 / (1 + exp(-stop logit)) > stop_threshold - the persistent kernel's own expression - and writes *flag = t + 1.  A *flag
+ * that is already non-zero is left as it is. */
+int satt_dec_stop_scan(const float* yout, int B, int rows, int NO, int t0, int nsteps, int min_steps, float stop_threshold,
+                       int* flag, void* stream);
 /* new query row of the causal self-attention over the K|V|Q cache kvq [B,Td,3D] (row *step must hold K|V|Q of the step):
  * out [B,D] = softmax(q K^T * scale over rows 0..*step) V, heads side by side (modules/self_attention.py:45-65) */
 int satt_dec_self_attn(const float* kvq, float* out, const int* step, int B, int Td, int D, int heads, float scale,

@@ -134,6 +134,11 @@ class DecMegaOptParams(C.Structure):
                 [("drop_thresh", C.c_uint32), ("drop_scale", C.c_float), ("drop_T", C.c_int), ("drop_stream", C.c_uint32 * 2)])
 
 
+class DecMegaGroup(C.Structure):
+    """satt_dec_mega_group (include/satt_hip.h): one pair of samples of a group launch of the persistent decode step"""
+    _fields_ = [("p", DecMegaParams), ("o", DecMegaOptParams), ("has_opt", C.c_int), ("b0", C.c_int)]
+
+
 # name -> (restype, argtypes); must list EVERY symbol declared in include/satt_hip.h
 _P = C.c_void_p
 _I = C.c_int
@@ -252,6 +257,11 @@ SIGNATURES = {
     "satt_dec_mega_variant": (_I, [C.POINTER(DecMegaParams)]),
     "satt_dec_mega_opt": (_I, [C.POINTER(DecMegaParams), C.POINTER(DecMegaOptParams), _P]),
     "satt_dec_mega_opt_variant": (_I, [C.POINTER(DecMegaParams), C.POINTER(DecMegaOptParams)]),
+    "satt_dec_mega_groups_supported": (_I, [C.POINTER(DecMegaGroup), _I]),
+    "satt_dec_mega_groups_variant": (_I, [C.POINTER(DecMegaGroup), _I]),
+    "satt_dec_mega_groups_scratch_floats": (c_i64, [_I, _I, _I]),
+    "satt_dec_mega_groups": (_I, [C.POINTER(DecMegaGroup), _P, _I, _P]),
+    "satt_dec_stop_scan": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _P, _P]),
     "satt_dec_self_attn": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "satt_l2_reg": (_I, [_P, _P, _P, _I, _F, _P, _P, _P]),
     "satt_sumsq": (_I, [_P, c_i64, _P, _P]),

@@ -33,6 +33,7 @@
 // and the registers and spills of these 5 000 - 19 000 instruction kernels, which are kept equal to the figure, did not come out
 // the same (profiles/decode_shared_phases_kernel_regs.txt has the figures per phase).
 #include <cstdlib>
+#include <type_traits>
 #include "cluster_xchg.h"
 
 #ifdef SATT_MEGA_PROF      // per-phase wall-clock sums (100 MHz) of workgroup 0: tools/build_variant.sh + tools/decode_mega_prof.py
@@ -352,6 +353,32 @@ __host__ __device__ inline size_t mega2_lds_bytes(int NB, int Ti, bool opt = fal
   return fl * sizeof(float);
 }
 
+// ---- group mode (template flag GRP of both kernels; include/satt_hip.h: satt_dec_mega_group): up to eight independent B = 2
+// problems in one launch, one per XCD.  The kernel reads a device array of complete parameter blocks; group = blockIdx % spread picks
+// the block (workgroups of groups >= ngroups return as the idle ones of a single launch do), the block is copied over the by-value
+// `p` / `o` of the kernel (a wave-uniform constant-address-space source: scalar loads, as the kernarg segment's), and everything
+// behind that point is the statements of the B = 2 kernel.  The kernel arguments of a GRP instantiation are therefore the same
+// block types with the array's address and the group count behind the parameter block (MegaGrpP); the block part of the kernarg
+// segment is never read.  Inside the step loop, where the single launch re-reads its block from the kernarg segment, a group
+// re-reads its block from the array.  A group's exchanges, handshake, step words and state are its own (nothing crosses groups);
+// the only thing that knows about the batch is pre-net dropout, whose mask row is b0 + b (folded into MDrop::step as b0 * drop_T:
+// the same element index).  The instantiations without GRP are instruction-identical to what they were before the flag existed.
+typedef const __attribute__((address_space(4))) satt_dec_mega_group MegaGrpC;
+struct MegaGrpP : satt_dec_mega_params { const satt_dec_mega_group* blocks; int ngroups; };
+// a block of the array -> the kernel's own copy, word by word (wave-uniform constant-address-space loads)
+template <class T> __device__ __forceinline__ void mega_block_copy(T* dst, const __attribute__((address_space(4))) T* src) {
+  typedef uint32_t __attribute__((may_alias)) word;
+  static_assert(sizeof(T) % sizeof(word) == 0, "whole words");
+  const __attribute__((address_space(4))) word* s = (const __attribute__((address_space(4))) word*)src;
+  word* d = (word*)dst;
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(T) / sizeof(word)); ++i) d[i] = s[i];
+}
+template <bool GRP> struct MegaArgT { typedef const satt_dec_mega_params type; };
+template <> struct MegaArgT<true> { typedef MegaGrpP type; };
+template <bool OPT, bool GRP> struct MegaOptArgT { typedef const typename MegaOptT<OPT>::type type; };
+template <> struct MegaOptArgT<true, true> { typedef satt_dec_mega_opt_params type; };
+
 // LJ (r6): the dimensions of examples/ljspeech/self-attention-tacotron.json as compile-time constants (checked by the launcher).  The
 // step body is ~12 000 instructions with ~100 wave-uniform values live across it; with run-time dimensions 1 600 of them were
 // v_readlane / v_writelane traffic of SPILLED scalars (486 spilled SGPRs) in phases that are instruction-issue bound.
@@ -366,16 +393,27 @@ __host__ __device__ inline size_t mega2_lds_bytes(int NB, int Ti, bool opt = fal
 //    softmax redundantly and so every workgroup computes u: no exchange, no granule, no barrier.  agent_tab and the weights are LDS
 //    resident (`agt`, tab's tail | `agx`); u crosses launches through o.u_state.
 //  * dropout: mega_drop in the epilogue of the split pre-net products.
-template <int NB, bool TRES, bool LJ, bool SPK, bool OPT>
-__global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p, const int spread, const typename MegaOptT<OPT>::type o) {
+template <int NB, bool TRES, bool LJ, bool SPK, bool OPT, bool GRP = false>
+__global__ __launch_bounds__(M2T) void dec_mega2_k(typename MegaArgT<GRP>::type p, const int spread, typename MegaOptArgT<OPT, GRP>::type o) {
   // r6: ONE XCD.  Workgroups are dealt to the 8 XCDs round robin in launch order, so with spread = 8 the grid is 8 x 32 and only the
   // workgroups with blockIdx % 8 == 0 stay: all 32 on the same XCD (32 CUs: one each).  Every weight is register resident, so the one
   // L2 only has to carry the exchanges - and granules published with PLAIN stores stay in that L2, where the peers' polling loads find
   // them: 0.55 us per round trip instead of ~0.9 through memory (the training clusters' same-XCD path, cluster_xchg.h).  The
   // placement is VERIFIED per launch (handshake below: every workgroup publishes its XCC id, all must agree); otherwise - and with
   // spread = 1 (SATT_DECODE_ONE_XCD=0) - the exchanges use agent-scope write-through stores as in r5.
-  if (blockIdx.x % spread) return;
-  const int wg = blockIdx.x / spread;
+  [[maybe_unused]] int gm = 1;
+  [[maybe_unused]] MegaGrpC* gb = nullptr;
+  if constexpr (GRP) {      // group mode: the block of the own group becomes `p` / `o`, nothing else differs
+    static_assert(NB == 2 && !TRES, "a group is a B = 2 problem with its context tables in global memory");
+    gm = spread > 1 ? spread : p.ngroups;      // (SATT_DECODE_ONE_XCD=0: groups side by side)
+    const int grp = blockIdx.x % gm;
+    if (grp >= p.ngroups) return;
+    gb = (MegaGrpC*)p.blocks + grp;
+    mega_block_copy(static_cast<satt_dec_mega_params*>(&p), &gb->p);
+    if constexpr (OPT) mega_block_copy(&o, &gb->o);
+  }
+  if (blockIdx.x % (GRP ? 1 : spread)) return;
+  const int wg = blockIdx.x / (GRP ? gm : spread);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* rs = smem;                                  // [8 NB 32] wave partials of the slice / split products
   float* ra = rs + 8 * NB * 32;                      // [8 NB 32] ... of the attention LSTM's context term of the NEXT step
@@ -594,14 +632,18 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p,
   const bool sx = __builtin_amdgcn_readfirstlane((int)(spread > 1 && sx_lds != 0.f)) != 0;      // plain-store exchanges (same XCD, verified)
   for (int s = 0; s < nsteps; ++s, ++t) {
     struct KArgsAll { satt_dec_mega_params p; int spread; typename MegaOptT<OPT>::type o; };      // the kernarg segment
-    typedef const __attribute__((address_space(4))) KArgsAll KArgsM;
-    KArgsM* kq = (KArgsM*)__builtin_amdgcn_kernarg_segment_ptr();
+    // (GRP: the group's block in the array - it has a `p` and an `o` too - re-read like the kernarg segment)
+    typedef const __attribute__((address_space(4))) typename std::conditional<GRP, satt_dec_mega_group, KArgsAll>::type KArgsM;
+    KArgsM* kq = GRP ? (KArgsM*)gb : (KArgsM*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(kq));
     const auto& p = kq->p;
     [[maybe_unused]] const auto& o = kq->o;
+    [[maybe_unused]] uint32_t drow = 0u;              // GRP: the group's first row of the dropout masks' [B][drop_T] index space
+    if constexpr (GRP && OPT) drow = (uint32_t)gb->b0 * (uint32_t)o.drop_T;
     [[maybe_unused]] MDrop dr0 = MDrop(), dr1 = MDrop();
     if constexpr (OPT) {
       dr1.seed = dseed; dr1.stream = o.drop_stream[1]; dr1.thresh = o.drop_thresh; dr1.dT = (uint32_t)o.drop_T; dr1.step = (uint32_t)t;
+      if constexpr (GRP) dr1.step += drow;
       dr1.N = (uint32_t)P1; dr1.scale = o.drop_scale;
       dr0 = dr1; dr0.stream = o.drop_stream[0]; dr0.N = (uint32_t)P0;      // (not used with SPK: MultiSpeakerPreNet has no dropout)
     }
@@ -712,6 +754,10 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p,
             a[0] += wa_ * tanhf_(xa) + wb_ * tanhf_(xb);          // (v1, U and the keys are zero beyond U1; pq there is finite)
           }
         }
+        // (GRP with run-time widths: the compiler contracts the product v2r * tanh into the first add of the wave sum - one rounding
+        //  less than the B = 2 sibling, whose bits a group reproduces, has there; the LJ pair contracts alike.  The product is
+        //  made opaque so that it is rounded as in the sibling: tests/test_decode_groups_gpu.py compares a group with a B = 2 launch bit by bit)
+        if constexpr (GRP && !LJ) asm volatile("" : "+v"(a[1]));
         wave_sum_multi<2>(a);
         if (lane == 0) { zs[(b * 2 + 0) * 8 + rr] = a[0]; zs[(b * 2 + 1) * 8 + rr] = a[1]; }
       }
@@ -1137,6 +1183,7 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(const satt_dec_mega_params p,
     have_p0 = fold && !last;      // (the last step of a launch hands over through yout: the next launch starts unfolded)
     if (have_p0) {
       if constexpr (OPT) dr0.step = (uint32_t)t + 1u;      // (the folded p0 is the NEXT step's)
+      if constexpr (OPT && GRP) dr0.step += drow;
       split_mul_fb<NB, SPK, OPT && !SPK>(wou, wfh, wfl, vc, NO, P0, bt + 32, bt + 168, gr + G.y, gr + G.p0, gbs, tag, wg, rs, tid, sx, spk, dr0);
       MPROF(21);
       // y (waves 0..2: NO <= 192) and the next step's p0 (waves 3..6) in ONE gather phase
@@ -1304,10 +1351,20 @@ __host__ __device__ inline size_t mega2s_lds_bytes(int NB, int Ti) {
   return fl * sizeof(float);
 }
 
-template <int NB, bool TRES, bool SPK>
-__global__ __launch_bounds__(M2T) void dec_mega2_single_k(const satt_dec_mega_params p, const int spread) {
-  if (blockIdx.x % spread) return;       // ONE XCD: see dec_mega2_k
-  const int wg = blockIdx.x / spread;
+template <int NB, bool TRES, bool SPK, bool GRP = false>
+__global__ __launch_bounds__(M2T) void dec_mega2_single_k(typename MegaArgT<GRP>::type p, const int spread) {
+  [[maybe_unused]] int gm = 1;
+  [[maybe_unused]] MegaGrpC* gb = nullptr;
+  if constexpr (GRP) {      // group mode: see dec_mega2_k
+    static_assert(NB == 2 && !TRES, "a group is a B = 2 problem with its context tables in global memory");
+    gm = spread > 1 ? spread : p.ngroups;
+    const int grp = blockIdx.x % gm;
+    if (grp >= p.ngroups) return;
+    gb = (MegaGrpC*)p.blocks + grp;
+    mega_block_copy(static_cast<satt_dec_mega_params*>(&p), &gb->p);
+  }
+  if (blockIdx.x % (GRP ? 1 : spread)) return;       // ONE XCD: see dec_mega2_k
+  const int wg = blockIdx.x / (GRP ? gm : spread);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* rs = smem;                                  // [8 NB 32] wave partials of the slice / split products
   float* ra = rs + 8 * NB * 32;                      // [8 NB 32] ... of the attention LSTM's context term of the NEXT step
@@ -1465,8 +1522,8 @@ __global__ __launch_bounds__(M2T) void dec_mega2_single_k(const satt_dec_mega_pa
   const bool sx = __builtin_amdgcn_readfirstlane((int)(spread > 1 && sx_lds != 0.f)) != 0;
   for (int s = 0; s < nsteps; ++s, ++t) {
     struct KArgsAll { satt_dec_mega_params p; int spread; };      // the kernarg segment
-    typedef const __attribute__((address_space(4))) KArgsAll KArgsM;
-    KArgsM* kq = (KArgsM*)__builtin_amdgcn_kernarg_segment_ptr();
+    typedef const __attribute__((address_space(4))) typename std::conditional<GRP, satt_dec_mega_group, KArgsAll>::type KArgsM;      // (dec_mega2_k)
+    KArgsM* kq = GRP ? (KArgsM*)gb : (KArgsM*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(kq));
     const auto& p = kq->p;
     int oz = 0;
@@ -1776,6 +1833,27 @@ __global__ __launch_bounds__(M2T) void dec_mega2_single_k(const satt_dec_mega_pa
   }
 }
 
+// ---- stop rule of a batch decoded in groups (no group can decide it alone: it fires when ALL samples exceed the threshold at the
+// same step).  One workgroup behind a group launch: thread s looks at step t0 + s, row t0 + s + 1 of every sample; the first step
+// that qualifies wins.  The comparison is the step loop's own expression (G2 above), so the decision has the same bits.
+__global__ __launch_bounds__(256) void dec_stop_scan_k(const float* __restrict__ yout, int B, int rows, int NO, int t0, int nsteps, int min_steps,
+                                                       float stop_threshold, int* flag) {
+  __shared__ int first;
+  if (threadIdx.x == 0) first = 0x7fffffff;
+  __syncthreads();
+  if (*flag != 0) return;                            // (fired behind an earlier launch: every thread reads the same word)
+  for (int s = threadIdx.x; s < nsteps; s += blockDim.x) {
+    const int t = t0 + s;
+    if (t > min_steps) {
+      bool fire = true;
+      for (int b = 0; b < B; ++b) fire = fire && (1.f / (1.f + __expf(-yout[((int64_t)b * rows + t + 1) * NO + NO - 1])) > stop_threshold);
+      if (fire) atomicMin(&first, t);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && first != 0x7fffffff) *flag = first + 1;
+}
+
 }  // namespace
 
 #ifdef SATT_MEGA_PROF
@@ -1852,23 +1930,27 @@ inline int mega_spread() {
   static const int spread = [] { const char* e = getenv("SATT_DECODE_ONE_XCD"); return (e && atoi(e) == 0) ? 1 : 8; }();
   return spread;
 }
+// workgroups of a launch: 32 on one XCD of 8; group mode: 32 per group, the groups side by side on the XCDs
+inline int mega_grid(const satt_dec_mega_params&, int spread) { return M2G * spread; }
+inline int mega_grid(const MegaGrpP& a, int spread) { return M2G * (spread > 1 ? spread : a.ngroups); }
 // one instantiation of either kernel: its dynamic LDS size, then the launch
-template <class... KA, class... A>
-int mega_launch(void (*kernel)(KA...), size_t smem, hipStream_t s, const satt_dec_mega_params& p, const A&... more) {
+template <class... KA, class P, class... A>
+int mega_launch(void (*kernel)(KA...), size_t smem, hipStream_t s, const P& p, const A&... more) {
   const int spread = mega_spread();
   if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
     (void)hipGetLastError();
     return SATT_E_LAUNCH;
   }
-  hipLaunchKernelGGL(kernel, dim3(M2G * spread), dim3(M2T), smem, s, p, spread, more...);
+  hipLaunchKernelGGL(kernel, dim3(mega_grid(p, spread)), dim3(M2T), smem, s, p, spread, more...);
   SATT_LAUNCH_CHECK();
   return SATT_OK;
 }
 }  // namespace
 
-extern "C" int satt_dec_mega_opt(const satt_dec_mega_params* pp, const satt_dec_mega_opt_params* opt, void* stream) {
-  if (!pp || !satt_dec_mega_supported(pp) || pp->nsteps < 1) return SATT_E_UNSUPPORTED;
-  const satt_dec_mega_params& p = *pp;
+namespace {
+// a supported block (and its options) before a launch: the pointers the kernel of its form dereferences
+int mega_check_block(const satt_dec_mega_params& p, const satt_dec_mega_opt_params* opt) {
+  if (p.nsteps < 1) return SATT_E_UNSUPPORTED;
   const bool single = mega_single(p);
   if (single && (opt_agent(opt) || opt_drop(opt))) return SATT_E_UNSUPPORTED;
   // what both forms read ...
@@ -1882,6 +1964,15 @@ extern "C" int satt_dec_mega_opt(const satt_dec_mega_params* pp, const satt_dec_
   // options: the agent belongs to the forward recursion and comes with its bias, table and state word; dropout with its seed word
   if (opt_agent(opt) && (!opt->agentb || !opt->agent_tab || !opt->u_state || p.att1_mode != 0)) return SATT_E_BADARG;
   if (opt_drop(opt) && (!opt->drop_seed || opt->drop_T < 1)) return SATT_E_BADARG;
+  return SATT_OK;
+}
+}  // namespace
+
+extern "C" int satt_dec_mega_opt(const satt_dec_mega_params* pp, const satt_dec_mega_opt_params* opt, void* stream) {
+  if (!pp || !satt_dec_mega_supported(pp)) return SATT_E_UNSUPPORTED;
+  const satt_dec_mega_params& p = *pp;
+  const bool single = mega_single(p);
+  if (const int rc = mega_check_block(p, opt)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int var = satt_dec_mega_opt_variant(pp, opt);
   const bool tables = var & SATT_MEGA_VAR_TABLES_LDS, lj = var & SATT_MEGA_VAR_LJ, spk = var & SATT_MEGA_VAR_SPEAKER;
@@ -1906,3 +1997,72 @@ extern "C" int satt_dec_mega_opt(const satt_dec_mega_params* pp, const satt_dec_
 }
 
 extern "C" int satt_dec_mega(const satt_dec_mega_params* pp, void* stream) { return satt_dec_mega_opt(pp, nullptr, stream); }
+
+// ---- group mode (include/satt_hip.h: satt_dec_mega_group)
+extern "C" int64_t satt_dec_mega_groups_scratch_floats(int ngroups, int heads, int hd) {
+  if (ngroups < 1 || ngroups > SATT_MEGA_GROUPS_MAX) return 0;
+  return ngroups * satt_dec_mega_scratch_floats(2, heads, hd);
+}
+
+namespace {
+inline const satt_dec_mega_opt_params* group_opt(const satt_dec_mega_group& g) { return g.has_opt ? &g.o : nullptr; }
+// every shape field, the form and nsteps
+bool groups_agree(const satt_dec_mega_group& a, const satt_dec_mega_group& b) {
+  const satt_dec_mega_params &p = a.p, &q = b.p;
+  const satt_dec_mega_opt_params *o = group_opt(a), *r = group_opt(b);
+  return p.B == q.B && p.Td == q.Td && p.Ti == q.Ti && p.A == q.A && p.D == q.D && p.Ds == q.Ds && p.heads == q.heads && p.U1 == q.U1 &&
+         p.V1 == q.V1 && p.U2 == q.U2 && p.V2 == q.V2 && p.kernel == q.kernel && p.filters == q.filters && p.att1_mode == q.att1_mode &&
+         p.cumulative == q.cumulative && p.P0 == q.P0 && p.P1 == q.P1 && p.feed == q.feed && p.NO == q.NO && p.ldout == q.ldout &&
+         p.zc == q.zc && p.zh == q.zh && p.stop_threshold == q.stop_threshold && p.min_steps == q.min_steps && p.nsteps == q.nsteps &&
+         !p.sproj == !q.sproj && !p.tin == !q.tin && !p.Wfh == !q.Wfh && !p.Wfl == !q.Wfl && !p.bfb == !q.bfb &&
+         !a.has_opt == !b.has_opt && opt_agent(o) == opt_agent(r) && opt_drop(o) == opt_drop(r) &&
+         (!opt_drop(o) || (o->drop_thresh == r->drop_thresh && o->drop_scale == r->drop_scale && o->drop_T == r->drop_T &&
+                           o->drop_stream[0] == r->drop_stream[0] && o->drop_stream[1] == r->drop_stream[1]));
+}
+}  // namespace
+
+extern "C" int satt_dec_mega_groups_variant(const satt_dec_mega_group* hb, int ngroups) {
+  if (!hb || ngroups < 1 || ngroups > SATT_MEGA_GROUPS_MAX) return -1;
+  for (int g = 0; g < ngroups; ++g)
+    if (hb[g].p.B != 2 || hb[g].b0 < 0 || satt_dec_mega_opt_variant(&hb[g].p, group_opt(hb[g])) < 0 || !groups_agree(hb[0], hb[g])) return -1;
+  return satt_dec_mega_opt_variant(&hb[0].p, group_opt(hb[0])) | SATT_MEGA_VAR_GROUPS;
+}
+
+extern "C" int satt_dec_mega_groups_supported(const satt_dec_mega_group* hb, int ngroups) { return satt_dec_mega_groups_variant(hb, ngroups) >= 0; }
+
+extern "C" int satt_dec_mega_groups(const satt_dec_mega_group* hb, const void* device_blocks, int ngroups, void* stream) {
+  const int var = satt_dec_mega_groups_variant(hb, ngroups);
+  if (var < 0) return SATT_E_UNSUPPORTED;
+  if (!device_blocks) return SATT_E_BADARG;
+  for (int g = 0; g < ngroups; ++g) {
+    if (const int rc = mega_check_block(hb[g].p, group_opt(hb[g]))) return rc;
+    if (hb[g].p.flag) return SATT_E_BADARG;          // no stop rule inside a group launch: satt_dec_stop_scan behind it
+    for (int h = 0; h < g; ++h)                      // exchanges, step words and state belong to ONE group
+      if (hb[h].p.part == hb[g].p.part || hb[h].p.step == hb[g].p.step || hb[h].p.ha == hb[g].p.ha) return SATT_E_BADARG;
+  }
+  const satt_dec_mega_params& p = hb[0].p;
+  const bool single = var & SATT_MEGA_VAR_SINGLE, lj = var & SATT_MEGA_VAR_LJ, spk = var & SATT_MEGA_VAR_SPEAKER;
+  const bool has_opt = var & (SATT_MEGA_VAR_AGENT | SATT_MEGA_VAR_DROPOUT);
+  const size_t smem = single ? mega2s_lds_bytes(2, p.Ti) : mega2_lds_bytes(2, p.Ti, has_opt);
+  if (smem > 160 * 1024) return SATT_E_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  MegaGrpP ga;                                       // (the block part is a place holder: every group reads its own from the array)
+  static_cast<satt_dec_mega_params&>(ga) = p;
+  ga.blocks = (const satt_dec_mega_group*)device_blocks; ga.ngroups = ngroups;
+#define SATT_MEGA2GO(LJV, SP) \
+  (has_opt ? mega_launch(dec_mega2_k<2, false, LJV, SP, true, true>, smem, s, ga, hb[0].o) : mega_launch(dec_mega2_k<2, false, LJV, SP, false, true>, smem, s, ga, MegaNoOpt()))
+#define SATT_MEGA2GL(SP) (lj ? SATT_MEGA2GO(true, SP) : SATT_MEGA2GO(false, SP))
+  if (single) return spk ? mega_launch(dec_mega2_single_k<2, false, true, true>, smem, s, ga) : mega_launch(dec_mega2_single_k<2, false, false, true>, smem, s, ga);
+  return spk ? SATT_MEGA2GL(true) : SATT_MEGA2GL(false);
+#undef SATT_MEGA2GO
+#undef SATT_MEGA2GL
+}
+
+extern "C" int satt_dec_stop_scan(const float* yout, int B, int rows, int NO, int t0, int nsteps, int min_steps, float stop_threshold,
+                                  int* flag, void* stream) {
+  if (!yout || !flag) return SATT_E_BADARG;
+  if (B < 1 || NO < 1 || t0 < 0 || nsteps < 1 || (int64_t)t0 + nsteps >= rows) return SATT_E_BADARG;
+  hipLaunchKernelGGL(dec_stop_scan_k, dim3(1), dim3(256), 0, (hipStream_t)stream, yout, B, rows, NO, t0, nsteps, min_steps, stop_threshold, flag);
+  SATT_LAUNCH_CHECK();
+  return SATT_OK;
+}

@@ -72,9 +72,27 @@ class DecodeSession:
                 self._mega_shape = shape
                 self._mega_single = not dual_form
                 self.K = max(self.K, self.MEGA_STEPS)
+        # Batches of 3 .. MEGA_GROUPS_MAX_B: the same kernel in GROUP mode - one pair of samples per XCD, ceil(B / 2) independent
+        # B = 2 problems in one launch (csrc/decode_mega2.hip, include/satt_hip.h: satt_dec_mega_group).  Decided by the library on
+        # the B = 2 block of the model.  An odd batch is padded with a copy of its last sample (`Ba` rows are allocated, B returned).
+        self._groups = 0
+        if (self.MEGA and self.MEGA_GROUPS and use_graph and not forced and (dual_form or single_form) and len(c.dec_prenet) == 2 and
+                ops.get_precision() == "bf16" and 2 < B <= min(self.MEGA_GROUPS_MAX_B, 2 * ops.MEGA_GROUPS_MAX)):
+            sh2 = dict(Ds=Ds, heads=c.dec_sa_heads, U2=U2, V2=V2) if dual_form else dict(Ds=0, heads=0, U2=0, V2=0)
+            shape = dict(B=2, Td=Td, Ti=Ti, A=A, D=D, U1=U1, V1=V1, **sh2, kernel=c.att_kernel,
+                         filters=c.att_filters, att1_mode=int(c.attention == "location_sensitive"), cumulative=int(c.cumulative_weights),
+                         P0=c.dec_prenet[0], P1=c.dec_prenet[1], feed=feed, NO=NO, ldout=(NO + 7) // 8 * 8, zc=c.zc, zh=c.zh,
+                         stop_threshold=float(stop_threshold), min_steps=int(min_steps))
+            if ops.dec_mega_supported(ops.dec_mega_params(**shape)):
+                self._mega_shape = shape
+                self._mega_single = not dual_form
+                self._groups = (B + 1) // 2
+                self.K = max(self.K, self.MEGA_GROUPS_STEPS)
+        Ba = self.Ba = 2 * self._groups if self._groups else B
         Tdp = self.Tdp = (Td + self.K - 1) // self.K * self.K          # whole graphs: rows past Td are scratch
         f32 = dict(dtype=torch.float32, device=dev)
         Z = lambda *s: torch.zeros(*s, **f32)
+        ZB = lambda n, *s: Z(Ba * n, *s)[:B * n]          # per-sample rows: the first B of Ba allocated (group mode pads an odd batch)
         CT, UQ = V1 + V2, U1 + U2
         # Two copies of the step counter: sB is read by the pre-net launches (the first of a step) and written by the
         # output projection (the last); the last pre-net launch copies it into sA, which every other launch reads.  Each
@@ -82,17 +100,17 @@ class DecodeSession:
         self.steps2 = torch.zeros(2, dtype=torch.int32, device=dev)
         self.step, sB = self.steps2[0:1], self.steps2[1:2]
         self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.lengths = torch.zeros(B, dtype=torch.int64, device=dev)
-        self.values1, self.keys1 = Z(B * Ti, V1), Z(B * Ti, U1)
-        self.values2 = Z(B * Ti, V2) if c.dual else None
-        self.keys2 = Z(B * Ti, U2) if c.dual else None
-        self.yout = Z(B, Tdp + 1, NO)                     # row 0 = go frame (zeros); step t writes row t + 1
-        self.tin = Z(B, Tdp, feed) if teacher else None   # teacher-fed inputs: go frame | shifted targets
-        self.sproj = Z(B, c.dec_prenet[0]) if c.num_speakers > 0 else None
+        self.lengths = torch.zeros(Ba, dtype=torch.int64, device=dev)[:B]
+        self.values1, self.keys1 = ZB(Ti, V1), ZB(Ti, U1)
+        self.values2 = ZB(Ti, V2) if c.dual else None
+        self.keys2 = ZB(Ti, U2) if c.dual else None
+        self.yout = ZB(1, Tdp + 1, NO)                    # row 0 = go frame (zeros); step t writes row t + 1
+        self.tin = ZB(1, Tdp, feed) if teacher else None  # teacher-fed inputs: go frame | shifted targets
+        self.sproj = ZB(1, c.dec_prenet[0]) if c.num_speakers > 0 else None
         self.ctx = Z(2, B, CT)                            # contexts of step t in buffer t & 1 (csrc/decode.hip)
         self.a_state, self.alpha_state = Z(2, B, Ti), Z(2, B, Ti)      # double-buffered by step parity
         self.e1, self.e2 = Z(B, Ti), Z(B, Ti)
-        self.al1, self.al2 = Z(B, Tdp, Ti), (Z(B, Tdp, Ti) if c.dual else None)
+        self.al1, self.al2 = ZB(1, Tdp, Ti), (ZB(1, Tdp, Ti) if c.dual else None)
         self.teach1 = Z(B, Tdp, Ti) if forced else None
         self.teach2 = Z(B, Tdp, Ti) if (forced and c.dual) else None
         # c, h of the three cells, double-buffered by step parity (csrc/decode.hip: read [t & 1], write [(t & 1) ^ 1])
@@ -100,7 +118,7 @@ class DecodeSession:
         ca, ha, c1, h1, c2, h2 = self.states
         hq, pq, h1n, dout = Z(B, A), Z(2, B, UQ), Z(B, D), Z(B, D)     # pq: processed query of step t in buffer t & 1
         NH = c.dec_sa_num_hop if Ds else 0                # stacked causal blocks (modules/module.py:707-715): one K|V|Q cache per hop
-        self.kvqs = [Z(B, Tdp, 3 * Ds) for _ in range(NH)]
+        self.kvqs = [ZB(1, Tdp, 3 * Ds) for _ in range(NH)]
         self.kvq = self.kvqs[0] if NH else None
         o_t, tr_t = (Z(B, Ds), Z(B, Ds)) if Ds else (None, None)
         st = self.step
@@ -197,18 +215,18 @@ class DecodeSession:
         self.graph = None
         # ---- persistent form (csrc/decode_mega2.hip): the same step, ONE launch per K steps on 32 persistent workgroups that exchange
         # {tag, value} granules instead of nine dependent launches - for the configurations satt_dec_mega_supported took above
-        self.mega = self.mega_opt = None
+        self.mega = self.mega_opt = self.mega_groups = None
         self.ctab = self._ctw = None
         if self._mega_shape is not None:
             single = self._mega_single
             self._mega_err = torch.zeros(1, dtype=torch.int32, device=dev)          # sticky error word
-            self._mega_part = Z(max(1, ops.dec_mega_scratch_floats(B, 0, 0) if single else
-                                    ops.dec_mega_scratch_floats(B, c.dec_sa_heads, Ds // c.dec_sa_heads)))
+            self._mega_part = Z(max(1, ops.dec_mega_scratch_floats(Ba, 0, 0) if single else
+                                    ops.dec_mega_scratch_floats(Ba, c.dec_sa_heads, Ds // c.dec_sa_heads)))
             # context tables values W_c (the cells take  sum_r alpha_r (values_r W_c)  instead of ctx W_c):
             # [B * Ti][LSTM 1 x values1 | LSTM 1 x values2 | attention LSTM x values1 | attention LSTM x values2][4 * 256]
             # (the single-source form: the two values1 tables, [B * Ti][LSTM 1 x values1 | attention LSTM x values1][4 * 256])
             tabs = (V1, V1) if single else (V1, V2, V1, V2)
-            self.ctab = Z(B * Ti, len(tabs) * 4 * D)
+            self.ctab = Z(Ba * Ti, len(tabs) * 4 * D)
             self._ctw = [Z(v, 4 * D) for v in tabs]
             Kf = D if single else Ds          # input width of the mel | stop projection: the fold's K
             # folded feedback (free running): pre-net layer 0 straight from the output transform's result - fed = the last `feed` mel
@@ -228,7 +246,7 @@ class DecodeSession:
                 pre = sa_prefix("dec.sa", 0)
                 second = dict(Wkvq=eng.W(pre + ".kvq.W").n, Wot=self.Wot_k[0], bkvq=P[pre + ".kvq.b"], bot=self.bot[0], v2=P["dec.att2.v"],
                               keys2=self.keys2, values2=self.values2, align2=self.al2, kvq=self.kvqs[0])
-            self.mega = ops.dec_mega_params(
+            mega = ops.dec_mega_params(
                 **dict(self._mega_shape, Td=Tdp),
                 Wp0=eng.W("dec.prenet0.W").n, Wp1=eng.W("dec.prenet1.W").n, Wa=self.lstm_w["dec.att_lstm.W"], Wq=wq.n,
                 W1=self.lstm_w["dec.lstm1.W"], W2=self.lstm_w["dec.lstm2.W"],
@@ -237,22 +255,27 @@ class DecodeSession:
                 locF=P["dec.att1.F"], locFb=P["dec.att1.bF"], locU=P["dec.att1.U"], v1=P["dec.att1.v"], b1=P["dec.att1.b"],
                 lengths=self.lengths, keys1=self.keys1, values1=self.values1, ca=ca, ha=ha, c1=c1, h1=h1, c2=c2, h2=h2, a_state=self.a_state,
                 alpha_state=self.alpha_state, ctx=self.ctx, yout=self.yout, tin=self.tin, align1=self.al1, **second,
-                part=self._mega_part, ctab=self.ctab, step=self.steps2, flag=None if teacher else self.flag,
+                part=self._mega_part, ctab=self.ctab, step=self.steps2, flag=None if (teacher or self._groups) else self.flag,
                 err=self._mega_err, **spk, **({} if self._fb is None else dict(Wfh=self._fb["hi"], Wfl=self._fb["lo"], bfb=self._fb["bias"])))
-            assert ops.dec_mega_supported(self.mega)
+            assert ops.dec_mega_supported(mega)
             # options of the kernel (a block of their own; None: ops.dec_mega as ever).  Transition agent: the kernel forms no
             # context, so the context part of u's dot product comes from a per-utterance table values1 Wa[:V1]
             # (build_context_tables) and u crosses launches in u_state.  Dropout that stays on: the launch-per-layer masks (pdrop).
             if not single and (c.transition_agent or (c.apply_dropout_on_inference and c.dec_prenet_drop > 0)):
                 agent = {}
                 if c.transition_agent:
-                    self.agent_tab, self.u_state = Z(B * Ti, 1), Z(B)
+                    self.agent_tab, self.u_state = Z(Ba * Ti, 1), Z(Ba)
                     agent = dict(agentW=P["dec.att1.Wa"], agentb=P["dec.att1.ba"], agent_tab=self.agent_tab, u_state=self.u_state)
                 drop = ops.Drop(c.dec_prenet_drop, 0, self.drop_seed) if c.apply_dropout_on_inference else None
                 self.mega_opt = ops.dec_mega_opt_params(drop=drop, drop_T=Td, drop_streams=(S_DEC_PRENET0, S_DEC_PRENET1), **agent)
+            if self._groups:
+                self._group_blocks_init(mega, self.mega_opt)
+                self.mega_opt = None
+            else:
+                self.mega = mega
             self.kernel_launches = 1          # per K steps
         self.refresh_folded()
-        if self.mega is not None:
+        if self.mega is not None or self.mega_groups is not None:
             # One throw-away launch (zero memories, discarded by the reset() of the first utterance), as the graph path below runs its
             # step once outside the capture: module load and the cold start of the 32 persistent workgroups stay out of the first
             # utterance.  It is a matter of time only, not of results: the first-utterance deviation r5 saw (one run in ~30 fresh
@@ -276,6 +299,55 @@ class DecodeSession:
                 for _ in range(self.K):
                     self.run_step()
             self.graph = g
+
+    def _group_blocks_init(self, mega, opt):
+        """group mode: `mega` / `opt` are the blocks of the whole (padded) batch; group g's block is a copy whose per-sample pointers
+        are advanced by 2 g samples and whose recurrent state, exchange region and step words are the group's own - the state buffers
+        are double-buffered with a parity stride of B samples, which inside a group is 2"""
+        c, G, Ba, Ti, dev = self.eng.cfg, self._groups, self.Ba, self.Ti, self.eng.dev
+        f32 = dict(dtype=torch.float32, device=dev)
+        A, D = c.att_rnn_units, c.dec_units
+        CT = mega.V1 + mega.V2
+        self._gstates = [torch.zeros(G, 2, 2, n, **f32) for n in (A, A, D, D, D, D)]
+        self._ga_state, self._galpha_state, self._gctx = (torch.zeros(G, 2, 2, n, **f32) for n in (Ti, Ti, CT))
+        self._gsteps = torch.zeros(G, 2, dtype=torch.int32, device=dev)
+        part = self._mega_part.view(G, -1)
+        # bytes per sample of what is indexed by the batch row
+        per = dict(lengths=8, keys1=4 * Ti * mega.U1, values1=4 * Ti * mega.V1, keys2=4 * Ti * mega.U2, values2=4 * Ti * mega.V2,
+                   yout=4 * (self.Tdp + 1) * mega.NO, tin=4 * self.Tdp * mega.feed, align1=4 * self.Tdp * Ti, align2=4 * self.Tdp * Ti,
+                   kvq=4 * self.Tdp * 3 * mega.Ds, ctab=4 * self.ctab.shape[1] * Ti, sproj=4 * mega.P0)
+        oper = dict(agent_tab=4 * Ti, u_state=4)
+        blocks = []
+        for g in range(G):
+            p = type(mega).from_buffer_copy(mega)
+            for k, nb in per.items():
+                if getattr(p, k):
+                    setattr(p, k, getattr(p, k) + 2 * g * nb)
+            for k, t in zip(("ca", "ha", "c1", "h1", "c2", "h2"), self._gstates):
+                setattr(p, k, t[g].data_ptr())
+            p.a_state, p.alpha_state, p.ctx = self._ga_state[g].data_ptr(), self._galpha_state[g].data_ptr(), self._gctx[g].data_ptr()
+            p.part, p.step, p.flag = part[g].data_ptr(), self._gsteps[g].data_ptr(), None
+            o = None
+            if opt is not None:
+                o = type(opt).from_buffer_copy(opt)
+                for k, nb in oper.items():
+                    if getattr(o, k):
+                        setattr(o, k, getattr(o, k) + 2 * g * nb)
+            blocks.append((p, o, 2 * g))
+        self._gproto, self._gblocks = blocks, {}
+        self.mega_groups = self._group_blocks(self.K)[0]
+        assert ops.dec_mega_groups_supported(self.mega_groups)
+        self._t0 = 0
+
+    def _group_blocks(self, nsteps):
+        """(host array, device copy) of the group blocks for launches of `nsteps` steps (the blocks carry nsteps: a ragged last
+        launch has an array of its own)"""
+        if nsteps not in self._gblocks:
+            for p, _, _ in self._gproto:
+                p.nsteps = int(nsteps)
+            arr = ops.dec_mega_groups_blocks(self._gproto)
+            self._gblocks[nsteps] = (arr, ops.dec_mega_groups_device(arr, self.eng.dev))
+        return self._gblocks[nsteps]
 
     @staticmethod
     def _fuse_chains(L):
@@ -350,6 +422,14 @@ class DecodeSession:
     # itself, so a long launch costs nothing past the token; the launch prologue (weights into registers, tables into LDS, placement
     # handshake: ~10 us) is what the length amortises - r6, B = 1, 200 steps: 32 -> 14.2 us per step, 64 -> 13.8, 128 -> 13.5, 224 -> 13.4
     MEGA_STEPS = 128
+    # group mode of the persistent kernel (2 < B <= MEGA_GROUPS_MAX_B: one pair of samples per XCD, all groups in one launch).  It
+    # needs every CU of the XCDs it uses - a kernel running beside it in another stream or process turns into the exchange time-out
+    # (SattError from check()); False / SATT_DECODE_MEGA_GROUPS=0 is the way out (the hipGraph path).  MEGA = False switches it off too.
+    MEGA_GROUPS = __import__("os").environ.get("SATT_DECODE_MEGA_GROUPS", "1") != "0"
+    MEGA_GROUPS_MAX_B = 16
+    # steps per group launch: no group can evaluate the stop rule, so a launch runs all its steps, the stop scan runs behind it and the
+    # host reads the flag once per launch - the overshoot past the stop token is bounded by the launch length
+    MEGA_GROUPS_STEPS = 32
     MEGA_FOLD_FEEDBACK = __import__("os").environ.get("SATT_DECODE_FOLD_FEEDBACK", "1") != "0"     # projection -> pre-net 0 folded (csrc/decode_mega2.hip)
     FUSE = True         # chain short Dense launches into their consumers (csrc/decode.hip dec_chain_k); tests switch it off
     MAX_CHAIN = 1       # layers chained in front of a consumer (the kernel takes up to 2)
@@ -396,21 +476,28 @@ class DecodeSession:
 
     def build_context_tables(self):
         """per utterance, after the memories are in place: values W_c in fp32 (the bf16-rounded, regrouped weights of the step)"""
-        if self.mega is None or self.ctab is None:
+        if (self.mega is None and self.mega_groups is None) or self.ctab is None:
             return
         c = self.eng.cfg
+        full = lambda t: t if t._base is None else t._base      # all Ba allocated samples (group mode; otherwise the tensor itself)
+        if self.mega_groups is not None and self.B % 2:      # the padding sample of an odd batch: a copy of the last one's inputs
+            for t in (self.lengths, self.values1, self.keys1, self.values2, self.keys2, self.sproj, self.tin):
+                if t is not None:
+                    rows = full(t).view(self.Ba, -1)
+                    rows[self.B].copy_(rows[self.B - 1])
+        values1, values2 = full(self.values1), (None if self.values2 is None else full(self.values2))
         # (speaker_to_decoder: the memories and the cells' context rows are V + mem_speaker wide)
         A, D, V1, V2, P1 = c.att_rnn_units, c.dec_units, c.cbhg_out_units + c.mem_speaker, c.sa_units + c.mem_speaker, c.dec_prenet[1]
         W1, Wa = self.lstm_w["dec.lstm1.W"], self.lstm_w["dec.att_lstm.W"]
         if self._mega_single:      # the two values1 tables: LSTM 1 rows [A, A + V1), attention-LSTM rows [P1, P1 + V1)
-            rows = ((W1, A, V1, self.values1), (Wa, P1, V1, self.values1))
+            rows = ((W1, A, V1, values1), (Wa, P1, V1, values1))
         else:
-            rows = ((W1, A, V1, self.values1), (W1, A + V1, V2, self.values2), (Wa, P1, V1, self.values1), (Wa, P1 + V1, V2, self.values2))
+            rows = ((W1, A, V1, values1), (W1, A + V1, V2, values2), (Wa, P1, V1, values1), (Wa, P1 + V1, V2, values2))
         for q, (W, r0, n, x) in enumerate(rows):
             self._ctw[q].copy_(W[r0:r0 + n])
             ops.gemm(x.shape[0], 4 * D, n, x, n, self._ctw[q], 4 * D, 1, self.ctab[:, q * 4 * D:], len(rows) * 4 * D, prec=ops.PREC_F32)
         if c.transition_agent and not self._mega_single:      # agent_tab[b][r] = values1[b, r] . Wa[:V1] (fp32 parameters, as the launch-per-layer step multiplies)
-            ops.gemm(self.values1.shape[0], 1, V1, self.values1, V1, self.eng.P["dec.att1.Wa"], 1, 1, self.agent_tab, 1, prec=ops.PREC_F32)
+            ops.gemm(values1.shape[0], 1, V1, values1, V1, self.eng.P["dec.att1.Wa"], 1, 1, self.agent_tab, 1, prec=ops.PREC_F32)
 
     def run_step(self):
         for fn, prm in self.launches:
@@ -419,7 +506,15 @@ class DecodeSession:
     def replay(self, nsteps=None):
         """K decoder steps (the persistent kernel: `nsteps` <= K of them - a ragged last launch): one launch of the persistent
         kernel, or one replay of the captured graph"""
-        if self.mega is not None:
+        if self.mega_groups is not None:
+            # every group runs its n steps (no stop rule inside); the batch's stop rule is scanned over the n new rows behind them
+            n = self.K if nsteps is None else max(1, min(self.K, int(nsteps)))
+            ops.dec_mega_groups(*self._group_blocks(n))
+            if self.tin is None:
+                ops.dec_stop_scan(self.yout, self.B, self.Tdp + 1, self.yout.shape[-1], self._t0, n, self._mega_shape["min_steps"],
+                                  self._mega_shape["stop_threshold"], self.flag)
+            self._t0 += n
+        elif self.mega is not None:
             n = self.K if nsteps is None else max(1, min(self.K, int(nsteps)))
             if self.mega_opt is not None:
                 ops.dec_mega_opt(self.mega, self.mega_opt, n)
@@ -430,14 +525,21 @@ class DecodeSession:
 
     def check(self):
         """host-synchronous: raise if an exchange of the persistent kernel timed out (sticky word)"""
-        if self.mega is not None and int(self._mega_err.item()):
+        if (self.mega is not None or self.mega_groups is not None) and int(self._mega_err.item()):
             raise SattError("decode: an exchange of the persistent step kernel timed out")
 
     def reset(self):
         """recurrent state of a new utterance (zeros; alpha_0 = onehot(0): modules/forward_attention.py:128-136)"""
         self.steps2.zero_(); self.flag.zero_()
-        if self.mega is not None:
+        if self.mega is not None or self.mega_groups is not None:
             self._mega_part.zero_()        # exchange granules carry step + 1 as their tag: a new utterance starts from untagged ones
+        if self.mega_groups is not None:      # the groups' own step words and state ([G][parity][2][...])
+            self._gsteps.zero_(); self._t0 = 0
+            for t in self._gstates + [self._ga_state, self._gctx, self._galpha_state]:
+                t.zero_()
+            self._galpha_state[:, 0, :, 0] = 1.0
+            full = self.yout._base
+            full[:, 0].zero_()
         for t in self.states:
             t.zero_()
         self.ctx.zero_(); self.a_state.zero_(); self.alpha_state.zero_()
@@ -507,7 +609,8 @@ def infer(eng, source, source_length, max_steps=None, teacher=None, speaker_id=N
         lstm_out, sa_out = eng._encode(batch, False, ctx)
     key = (B, Ti, Td, teacher is not None, forced, int(min_steps), float(stop_threshold), int(check_every), bool(use_graph),
            ops.get_precision(), DecodeSession.FUSE, DecodeSession.MAX_CHAIN, DecodeSession.MEGA, DecodeSession.MEGA_MAX_B,
-           DecodeSession.MEGA_STEPS, DecodeSession.MEGA_FOLD_FEEDBACK)
+           DecodeSession.MEGA_STEPS, DecodeSession.MEGA_FOLD_FEEDBACK, DecodeSession.MEGA_GROUPS, DecodeSession.MEGA_GROUPS_MAX_B,
+           DecodeSession.MEGA_GROUPS_STEPS)
     cache = eng.__dict__.setdefault("_decode_sessions", {})
     ses = cache.get(key)
     if ses is None:         # (the kernels read the parameters in place: an optimiser step does not invalidate a session)
@@ -573,7 +676,7 @@ def infer(eng, source, source_length, max_steps=None, teacher=None, speaker_id=N
     steps = Td
     ev_a, ev_b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     ev_a.record()
-    if ses.graph is None and ses.mega is None:
+    if ses.graph is None and ses.mega is None and ses.mega_groups is None:
         for t in range(Td):
             ses.run_step()
             if teacher is None and t > min_steps and (t % K == 0 or t == Td - 1):

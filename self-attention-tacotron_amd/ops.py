@@ -1197,6 +1197,51 @@ def dec_mega_opt(p, opt, nsteps):
     _lib.check(_lib.lib().satt_dec_mega_opt(C.byref(p), None if opt is None else C.byref(opt), _s()), "dec_mega_opt")
 
 
+MEGA_VAR_GROUPS = 128                          # group mode: one pair of samples per XCD (satt_dec_mega_groups)
+MEGA_GROUPS_MAX = 8
+
+
+def dec_mega_groups_blocks(blocks):
+    """host array of satt_dec_mega_group from (params, option block or None, b0) triples - copies: the array is self-contained"""
+    arr = (_lib.DecMegaGroup * len(blocks))()
+    for g, (p, o, b0) in zip(arr, blocks):
+        C.memmove(C.byref(g.p), C.byref(p), C.sizeof(p))
+        if o is not None:
+            C.memmove(C.byref(g.o), C.byref(o), C.sizeof(o))
+        g.has_opt, g.b0 = int(o is not None), int(b0)
+    return arr
+
+
+def dec_mega_groups_supported(arr):
+    return bool(_lib.lib().satt_dec_mega_groups_supported(arr, len(arr)))
+
+
+def dec_mega_groups_variant(arr):
+    """the instantiation a group launch of `arr` takes: the blocks' MEGA_VAR_* bits | MEGA_VAR_GROUPS, -1 where it is not taken"""
+    return int(_lib.lib().satt_dec_mega_groups_variant(arr, len(arr)))
+
+
+def dec_mega_groups_scratch_floats(ngroups, heads, hd):
+    return int(_lib.lib().satt_dec_mega_groups_scratch_floats(ngroups, heads, hd))
+
+
+def dec_mega_groups_device(arr, device):
+    """the device copy of a host array of group blocks (the kernel reads its blocks from device memory)"""
+    raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
+    return raw.to(device)
+
+
+def dec_mega_groups(arr, dev_blocks):
+    """the blocks' nsteps decoder steps of up to eight pairs of samples in ONE launch (csrc/decode_mega2.hip, group mode)"""
+    _lib.check(_lib.lib().satt_dec_mega_groups(arr, _p(dev_blocks), len(arr), _s()), "dec_mega_groups")
+
+
+def dec_stop_scan(yout, B, rows, NO, t0, nsteps, min_steps, stop_threshold, flag):
+    """stop rule of the batch over the steps t0 .. t0 + nsteps - 1 of yout [B][rows][NO] (row t + 1 = step t): *flag = t + 1"""
+    _lib.check(_lib.lib().satt_dec_stop_scan(_p(yout), int(B), int(rows), int(NO), int(t0), int(nsteps), int(min_steps),
+                                             float(stop_threshold), _p(flag), _s()), "dec_stop_scan")
+
+
 def dec_self_attn(kvq, out, step, B, Td, D, heads, scale):
     _lib.check(_lib.lib().satt_dec_self_attn(_p(kvq), _p(out), _p(step), B, Td, D, heads, float(scale), _s()), "dec_self_attn")
 

@@ -3,7 +3,9 @@
 --hparams-json: another model, e.g. examples/vctk/self-attention-tacotron.json (speaker ids: the first B of the table).
 --hparams "k=v,...": overrides on top of it (on the LJSpeech example's file when no --hparams-json is given), e.g.
 use_forward_attention_transition_agent=True or apply_dropout_on_inference=True.
-usage: python tools/bench_infer.py [--steps 200] [--batch 1] [--hparams-json FILE] [--hparams "k=v,..."] [--repeat N]"""
+--batch 3 .. 16 takes the persistent kernel in group mode (one pair of samples per XCD); --no-groups: the hipGraph of launch-per-layer
+steps such batches ran on before.
+usage: python tools/bench_infer.py [--steps 200] [--batch 1] [--no-groups] [--hparams-json FILE] [--hparams "k=v,..."] [--repeat N]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -21,6 +23,7 @@ ap.add_argument("--precision", default="bf16")
 ap.add_argument("--steps-per-graph", type=int, default=8)
 ap.add_argument("--no-graph", action="store_true")
 ap.add_argument("--mega-max-b", type=int, default=None, help="largest batch that takes the persistent step kernel (default: the session's)")
+ap.add_argument("--no-groups", action="store_true", help="DecodeSession.MEGA_GROUPS = False: batches of 3 .. 16 on the launch-per-layer path")
 ap.add_argument("--hparams-json", default=None, help="hparams file of the model (default: the LJSpeech dimensions)")
 ap.add_argument("--hparams", default=None, help='comma-separated name=value overrides of the model\'s hparams')
 ap.add_argument("--repeat", type=int, default=1, help="timed utterances (one JSON line each)")
@@ -29,6 +32,11 @@ ops.set_precision(a.precision)
 if a.mega_max_b is not None:
     from satt_amd.inference import DecodeSession
     DecodeSession.MEGA_MAX_B = a.mega_max_b
+if a.batch < 1 or a.batch > 16:
+    ap.error("--batch: 1 .. 16")
+if a.no_groups:
+    from satt_amd.inference import DecodeSession
+    DecodeSession.MEGA_GROUPS = False
 if a.hparams_json or a.hparams:
     from satt_amd.hparams import hparams
     hp = hparams.copy()
@@ -56,7 +64,8 @@ for _ in range(a.repeat):
     dt = out["decode_ms"] * 1e-3            # the decoder steps alone (HIP events around the replay loop)
     al = out["alignment1"]
     ses = eng._decode_sessions[next(reversed(eng._decode_sessions))]
-    path = "persistent" if getattr(ses, "mega", None) is not None else "launch-per-layer"
+    path = "persistent" if getattr(ses, "mega", None) is not None else \
+        ("persistent, groups" if getattr(ses, "mega_groups", None) is not None else "launch-per-layer")
     frames = a.steps * cfg.r * B
     print(json.dumps({"metric": "free-running decode (config 5)", "model": (a.hparams_json or "ljspeech") + (" + " + a.hparams if a.hparams else ""), "path": path, "batch": B, "Ti": Ti, "decoder_steps": out["steps"],
                       "ms_per_step": 1e3 * dt / a.steps, "utterance_ms_incl_encoder": 1e3 * dt_all,
