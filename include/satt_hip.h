@@ -732,8 +732,8 @@ int satt_dec_attention(const satt_dec_attention_params* p, void* stream);
  * Same math and the same buffers as the launch-per-layer path above (the caller may switch between the two from one LAUNCH to the
  * next: recurrent state, contexts, location input and forward variable are handed over at the last step of a launch).  Supported
  * (otherwise satt_dec_mega_supported() == 0 and the caller uses satt_dec_linear / satt_dec_attention / satt_dec_self_attn): the
- * dual-source model with a two-layer pre-net - plain, or with MultiSpeakerPreNet as its first layer (sproj below) -, no forced
- * alignments, bf16 weight shadows, B <= 2 (transition agent and pre-net dropout: satt_dec_mega_opt below),
+ * dual-source model with a two-layer pre-net - plain, or with MultiSpeakerPreNet as its first layer (sproj below) -, free-running
+ * alignments (forced ones: satt_dec_mega_forced below), bf16 weight shadows, B <= 2 (transition agent and pre-net dropout: satt_dec_mega_opt below),
  * Ti <= 256, A = D = Ds = 256, one causal self-attention hop of 2 or 4 heads.  Replaces, per step: reference
  * modules/module.py:762-778, modules/rnn_wrappers.py:47-124,188-214, modules/forward_attention.py:88-136,
  * modules/helpers.py:58-166 (mirrors).
@@ -835,6 +835,31 @@ typedef struct {
 /* opt == NULL or both options off: satt_dec_mega(p, stream) / satt_dec_mega_variant(p) */
 int satt_dec_mega_opt(const satt_dec_mega_params* p, const satt_dec_mega_opt_params* opt, void* stream);
 int satt_dec_mega_opt_variant(const satt_dec_mega_params* p, const satt_dec_mega_opt_params* opt);
+/* ---- forced alignments on the persistent decode step (use_forced_alignment_mode; reference
+ * modules/teacher_forcing_attention.py:29-35), in a third block: satt_dec_mega_params and satt_dec_mega_opt_params keep their
+ * layout.  The attention mechanisms are bypassed - no query layer, no location features, no energies, no softmax, no forward
+ * recursion, no transition agent - and row t of teach1 / teach2 ([B][Td][Ti] fp32, Td of the main block; rows as the caller
+ * wants them, normalised or not) IS the alignment of step t.  Semantics of the launch-per-layer path (satt_dec_attention with
+ * teach1 set): the histories align1 / align2 receive the rows as given; the contexts weight memory row r with
+ * r < length ? a[r] : 0; at the last step of a launch a_state and alpha_state of the other parity both receive the given row of
+ * mechanism 1, and the contexts are handed over as ever - so a forced utterance too may change between this entry point and the
+ * launch-per-layer ones from one launch to the next.  Everything else of the step (pre-nets with the folded feedback, the three
+ * cells, K|V|Q, cached self-attention, output transform, projection, stop rule, tin, multi-speaker pre-net, pre-net dropout) is
+ * the step of satt_dec_mega_opt.  Two exchanges per step fewer than the free-running step (pq, e): nine in the dual form, six
+ * in the single-source form.  The forced instantiations are siblings of the GENERIC-width ones: a block with the dimensions
+ * SATT_MEGA_VAR_LJ is keyed on runs forced on its generic sibling.
+ *  - f == NULL or f->teach1 == NULL: the call IS satt_dec_mega_opt / satt_dec_mega_opt_variant.
+ *  - otherwise the variant is that of the same block without f, without SATT_MEGA_VAR_LJ, | SATT_MEGA_VAR_FORCED;
+ *  - the dual form needs teach2 (NULL: SATT_E_BADARG, variant -1); the single-source form never reads it;
+ *  - the transition agent switched on in `opt` together with f: SATT_E_UNSUPPORTED, variant -1 (the agent never runs under
+ *    forced alignments: the caller leaves its fields NULL); the single-source form takes no options, as ever;
+ *  - there is no forced group launch. */
+typedef struct { const float *teach1, *teach2; } satt_dec_mega_forced_params;   /* [B][Td][Ti]; teach2 NULL in the single form */
+#define SATT_MEGA_VAR_FORCED 256     /* forced alignments (satt_dec_mega_forced with f->teach1 != NULL) */
+int satt_dec_mega_forced(const satt_dec_mega_params* p, const satt_dec_mega_opt_params* opt_or_null,
+                         const satt_dec_mega_forced_params* f, void* stream);
+int satt_dec_mega_forced_variant(const satt_dec_mega_params* p, const satt_dec_mega_opt_params* opt_or_null,
+                                 const satt_dec_mega_forced_params* f);
 /* ---- group mode of the persistent decode step: batches of 3 .. 16, one PAIR of samples per XCD.  A launch of satt_dec_mega keeps
  * one XCD busy (32 workgroups, every eighth of a grid of 8 x 32) and the other seven return at once.  A group launch keeps up to
  * eight of them busy: group g - the workgroups with blockIdx % 8 == g - decodes samples 2 g and 2 g + 1 with the statements that

@@ -134,6 +134,11 @@ class DecMegaOptParams(C.Structure):
                 [("drop_thresh", C.c_uint32), ("drop_scale", C.c_float), ("drop_T", C.c_int), ("drop_stream", C.c_uint32 * 2)])
 
 
+class DecMegaForcedParams(C.Structure):
+    """satt_dec_mega_forced_params (include/satt_hip.h): the teacher alignments of a forced launch of the persistent decode step"""
+    _fields_ = [("teach1", C.c_void_p), ("teach2", C.c_void_p)]
+
+
 class DecMegaGroup(C.Structure):
     """satt_dec_mega_group (include/satt_hip.h): one pair of samples of a group launch of the persistent decode step"""
     _fields_ = [("p", DecMegaParams), ("o", DecMegaOptParams), ("has_opt", C.c_int), ("b0", C.c_int)]
@@ -257,6 +262,8 @@ SIGNATURES = {
     "satt_dec_mega_variant": (_I, [C.POINTER(DecMegaParams)]),
     "satt_dec_mega_opt": (_I, [C.POINTER(DecMegaParams), C.POINTER(DecMegaOptParams), _P]),
     "satt_dec_mega_opt_variant": (_I, [C.POINTER(DecMegaParams), C.POINTER(DecMegaOptParams)]),
+    "satt_dec_mega_forced": (_I, [C.POINTER(DecMegaParams), C.POINTER(DecMegaOptParams), C.POINTER(DecMegaForcedParams), _P]),
+    "satt_dec_mega_forced_variant": (_I, [C.POINTER(DecMegaParams), C.POINTER(DecMegaOptParams), C.POINTER(DecMegaForcedParams)]),
     "satt_dec_mega_groups_supported": (_I, [C.POINTER(DecMegaGroup), _I]),
     "satt_dec_mega_groups_variant": (_I, [C.POINTER(DecMegaGroup), _I]),
     "satt_dec_mega_groups_scratch_floats": (c_i64, [_I, _I, _I]),

@@ -23,6 +23,30 @@
 // safe: between the consumption of X(t) and the production of X(t+1) lies at least one exchange every workgroup contributes to.
 // The baseline model (one attention source, no decoder self-attention) runs the SINGLE-SOURCE form, dec_mega2_single_k below: eight
 // exchanges, its own LDS and granule layout, and the granule argument re-derived for its chain.
+// FORCED ALIGNMENTS (template flag FRC of BOTH kernels; satt_dec_mega_forced): the mechanisms are bypassed - row t of the teacher
+// histories is the alignment of step t (reference modules/teacher_forcing_attention.py:29-35; csrc/decode.hip dec_attn_context_k).
+// Compiled out: the query layer's split product (B1) with its register slice, the whole of B2 (location features, energies), the pq
+// and e exchanges, and in phase C the poll, the softmax, the recursion and the agent; in the launch prologue everything only those
+// phases read (kls, Us, Fs, tab).  Phase C is: wave (sample, mechanism) writes the row it holds in registers to LDS TWICE - as given
+// (`alpha`: mechanism 1, `aprev`: mechanism 2; histories, and a_state = alpha_state = the given row of mechanism 1 at the hand-over)
+// and masked by the length (e1 / e2: table products, handed-over contexts) - and requests row t + 1; the launch's first row is
+// requested in the prologue.  The request is a step ahead because its address depends on nothing computed: a cold row never sits on
+// the chain in front of LSTM 1 (the waves that hold rows poll next for h1n, behind the LSTM 1 products).  Nine exchanges (dual)
+// and six (single) per step.  SINGLE-BUFFERED GRANULES, re-derived for the shorter chains.  FULL exchanges (every workgroup publishes
+// a part, every workgroup gathers all of it; a workgroup publishes X only behind its own gathers of everything in front of X in
+// program order, each ended by a workgroup barrier) are hq, h1n, dout and, in the dual form, tr.  Claim as before: when any
+// workgroup P overwrites X(t) with X(t + 1), every workgroup has finished reading X(t) - because between P's gather of X(t) and
+// its publication of X(t + 1) P gathered a full exchange F that lies behind X(t), F's gather returned only when EVERY workgroup had
+// published its part of F, and each did that behind its own gather of X(t).
+//   dual    p0 p1 [hq] [h1n] [dout] kvq part [tr] y | p0 ...   (SPK: p02 between p0 and p1)
+//           X in {p0, p02, p1}: F = hq(t);  hq: h1n(t);  h1n: dout(t);  dout: tr(t);  kvq, part: tr(t);  tr: hq(t + 1);  y: hq(t + 1)
+//   single  p0 p1 [hq] [h1n] [dout] y | p0 ...
+//           X in {p0, p02, p1}: F = hq(t);  hq: h1n(t);  h1n: dout(t);  dout: hq(t + 1);  y: hq(t + 1)
+// pq and e were never full (UQ columns; the workgroups whose rows lie below Ti), so no F above was one of them: the free-running
+// argument loses nothing, the two full exchanges hq and h1n merely become neighbours.  The fold publishes p0(t + 1) next to y(t),
+// behind P's gather of tr(t) (dual) / dout(t) (single): full, and behind every workgroup's gather of p0(t).  The teacher rows are
+// read-only global memory: no granule, no tag, nothing to overwrite.  tools/decode_stress.py's forced case under the jitter build
+// is the timing-independence evidence (profiles/decode_forced_bench_and_kernel_times.txt).
 // WHAT THE TWO KERNELS SHARE: the leaf helpers (split_mul / split_mul_fb / split_fill, gather_vec, slice_*, pin, lstm_unit,
 // mega_drop) and, on the host, one pointer list, one `spread` static and one launch function (mega_launch) behind both dispatch
 // ladders.  EVERY PHASE THEY HAVE IN COMMON IS WRITTEN OUT IN BOTH KERNELS, and a fix to one copy has to be made in the other: the
@@ -378,6 +402,11 @@ template <bool GRP> struct MegaArgT { typedef const satt_dec_mega_params type; }
 template <> struct MegaArgT<true> { typedef MegaGrpP type; };
 template <bool OPT, bool GRP> struct MegaOptArgT { typedef const typename MegaOptT<OPT>::type type; };
 template <> struct MegaOptArgT<true, true> { typedef satt_dec_mega_opt_params type; };
+// FRC (forced alignments, satt_dec_mega_forced_params): the two teacher pointers are one more kernel argument that only the FRC
+// instantiations have - the others take an empty type, as the ones without OPT do for the option block
+struct MegaNoFrc {};
+template <bool FRC> struct MegaFrcT { typedef MegaNoFrc type; };
+template <> struct MegaFrcT<true> { typedef satt_dec_mega_forced_params type; };
 
 // LJ (r6): the dimensions of examples/ljspeech/self-attention-tacotron.json as compile-time constants (checked by the launcher).  The
 // step body is ~12 000 instructions with ~100 wave-uniform values live across it; with run-time dimensions 1 600 of them were
@@ -393,8 +422,10 @@ template <> struct MegaOptArgT<true, true> { typedef satt_dec_mega_opt_params ty
 //    softmax redundantly and so every workgroup computes u: no exchange, no granule, no barrier.  agent_tab and the weights are LDS
 //    resident (`agt`, tab's tail | `agx`); u crosses launches through o.u_state.
 //  * dropout: mega_drop in the epilogue of the split pre-net products.
-template <int NB, bool TRES, bool LJ, bool SPK, bool OPT, bool GRP = false>
-__global__ __launch_bounds__(M2T) void dec_mega2_k(typename MegaArgT<GRP>::type p, const int spread, typename MegaOptArgT<OPT, GRP>::type o) {
+template <int NB, bool TRES, bool LJ, bool SPK, bool OPT, bool GRP = false, bool FRC = false>
+__global__ __launch_bounds__(M2T) void dec_mega2_k(typename MegaArgT<GRP>::type p, const int spread, typename MegaOptArgT<OPT, GRP>::type o,
+                                                   const typename MegaFrcT<FRC>::type f) {
+  static_assert(!(FRC && (GRP || LJ)), "forced alignments: the generic-width instantiations of a single launch");
   // r6: ONE XCD.  Workgroups are dealt to the 8 XCDs round robin in launch order, so with spread = 8 the grid is 8 x 32 and only the
   // workgroups with blockIdx % 8 == 0 stay: all 32 on the same XCD (32 CUs: one each).  Every weight is register resident, so the one
   // L2 only has to carry the exchanges - and granules published with PLAIN stores stay in that L2, where the peers' polling loads find
@@ -489,31 +520,35 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(typename MegaArgT<GRP>::type 
       sx_lds = rs[M2G];
       __syncthreads();                               // (rs is reused below)
     }
-    for (int i = tid; i < 8 * M2N; i += M2T) { const int f = i / M2N, u = i - f * M2N; Us[i] = (f < F && u < U1) ? p.locU[f * U1 + u] : 0.f; }
-    for (int i = tid; i < 3 * M2N; i += M2T) {
-      const int w = i / M2N, u = i - w * M2N;
-      float v = w == 0 ? (u < U1 ? p.v1[u] : 0.f) : (w == 1 ? (u < U1 ? p.b1[u] : 0.f) : (u < U2 ? p.v2[u] : 0.f));
-      if (w == 1 && u < U1)
-        for (int f = 0; f < F; ++f) v += p.locFb[f] * p.locU[f * U1 + u];           // (bias of the location convolution, through U)
-      if constexpr (OPT) {      // (v2 ends at U2 <= 64: the row's tail carries the agent's query weights [0, AGT))
-        if (w == 2 && u >= 64 && u - 64 < U1 && o.agentW) v = o.agentW[V1 + u - 64];
+    if constexpr (!FRC) {      // (forced alignments: nothing reads the location layer, v / b or the agent's weights)
+      for (int i = tid; i < 8 * M2N; i += M2T) { const int f = i / M2N, u = i - f * M2N; Us[i] = (f < F && u < U1) ? p.locU[f * U1 + u] : 0.f; }
+      for (int i = tid; i < 3 * M2N; i += M2T) {
+        const int w = i / M2N, u = i - w * M2N;
+        float v = w == 0 ? (u < U1 ? p.v1[u] : 0.f) : (w == 1 ? (u < U1 ? p.b1[u] : 0.f) : (u < U2 ? p.v2[u] : 0.f));
+        if (w == 1 && u < U1)
+          for (int f = 0; f < F; ++f) v += p.locFb[f] * p.locU[f * U1 + u];           // (bias of the location convolution, through U)
+        if constexpr (OPT) {      // (v2 ends at U2 <= 64: the row's tail carries the agent's query weights [0, AGT))
+          if (w == 2 && u >= 64 && u - 64 < U1 && o.agentW) v = o.agentW[V1 + u - 64];
+        }
+        tab[i] = v;
       }
-      tab[i] = v;
-    }
-    if constexpr (OPT) {
-      if (o.agentW) {
-        if (tid < 64 && AGT + tid < U1) agx[tid] = o.agentW[V1 + AGT + tid];
-        for (int i = tid; i < NB * Ti; i += M2T) { const int b = i / Ti, r = i - b * Ti; agt[b * M2TI + r] = o.agent_tab[i]; }
+      if constexpr (OPT) {
+        if (o.agentW) {
+          if (tid < 64 && AGT + tid < U1) agx[tid] = o.agentW[V1 + AGT + tid];
+          for (int i = tid; i < NB * Ti; i += M2T) { const int b = i / Ti, r = i - b * Ti; agt[b * M2TI + r] = o.agent_tab[i]; }
+        }
       }
     }
     if (tid < 4) lens[tid] = tid < B ? (int)p.lengths[tid] : 0;
-    for (int i = tid; i < NB * 8 * KLS; i += M2T) {
-      const int row = i / KLS, u = i - row * KLS, b = row / 8, rr = row - b * 8, tt = r0 + rr;
-      float v = 0.f;
-      if (b < B && rr < R && tt < Ti) v = u < M2N ? (u < U1 ? p.keys1[((int64_t)b * Ti + tt) * U1 + u] : 0.f) : (u - M2N < U2 ? p.keys2[((int64_t)b * Ti + tt) * U2 + u - M2N] : 0.f);
-      kls[i] = v;
+    if constexpr (!FRC) {      // (... nor the key table or the location filters)
+      for (int i = tid; i < NB * 8 * KLS; i += M2T) {
+        const int row = i / KLS, u = i - row * KLS, b = row / 8, rr = row - b * 8, tt = r0 + rr;
+        float v = 0.f;
+        if (b < B && rr < R && tt < Ti) v = u < M2N ? (u < U1 ? p.keys1[((int64_t)b * Ti + tt) * U1 + u] : 0.f) : (u - M2N < U2 ? p.keys2[((int64_t)b * Ti + tt) * U2 + u - M2N] : 0.f);
+        kls[i] = v;
+      }
+      for (int i = tid; i < 16 * 8; i += M2T) { const int j = i >> 3, f = i & 7; Fs[i] = (f < F && j < KW) ? p.locF[j * F + f] : 0.f; }
     }
-    for (int i = tid; i < 16 * 8; i += M2T) { const int j = i >> 3, f = i & 7; Fs[i] = (f < F && j < KW) ? p.locF[j * F + f] : 0.f; }
     if (tid < 40) {
       const int l = tid >> 3, n = 8 * wg + (tid & 7);
       const float* bp = l == 0 ? p.bp0 : (l == 1 ? p.bp1 : (l == 2 ? nullptr : (l == 3 ? p.bot : p.bout)));
@@ -534,6 +569,12 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(typename MegaArgT<GRP>::type 
     // state of step t: location-conv input, forward variable, recurrent vectors, the previous step's alignments, the fed frame
     for (int i = tid; i < NB * Ti; i += M2T) {
       const int b = i / Ti, r = i - b * Ti;
+      if constexpr (FRC) {      // (no recursion state; the history rows are AS GIVEN, the table products take them masked by the length)
+        if (b < B && t > 0) {
+          e1[b * M2TI + r] = r < lens[b] ? p.align1[((int64_t)b * p.Td + t - 1) * Ti + r] : 0.f;
+          e2[b * M2TI + r] = r < lens[b] ? p.align2[((int64_t)b * p.Td + t - 1) * Ti + r] : 0.f;
+        }
+      } else
       if (b < B) {
         aprev[b * (M2TI + 16) + PL + r] = p.a_state[((int64_t)par * B + b) * Ti + r];
         alpha[b * M2TI + r] = p.alpha_state[((int64_t)par * B + b) * Ti + r];
@@ -585,11 +626,25 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(typename MegaArgT<GRP>::type 
   [[maybe_unused]] float u_cur = 0.5f, agb = 0.f;
   [[maybe_unused]] uint32_t dseed = 0u;
   if constexpr (OPT) {
-    if (o.agentW) {
-      agb = o.agentb[0];
-      if (t > 0) u_cur = o.u_state[min((int)(threadIdx.x >> 7), B - 1)];
+    if constexpr (!FRC) {      // (the agent never runs under forced alignments: the launcher refuses the pair)
+      if (o.agentW) {
+        agb = o.agentb[0];
+        if (t > 0) u_cur = o.u_state[min((int)(threadIdx.x >> 7), B - 1)];
+      }
     }
     if (o.drop_thresh) dseed = *o.drop_seed;
+  }
+  // forced alignments: wave (b, mechanism) holds row t of its teacher history in registers, requested HERE for the launch's first step
+  // and, for every later step, a step ahead (phase C of the step before): the addresses depend on nothing that is computed, and a
+  // cold row must not sit on the step's dependency chain in front of LSTM 1
+  [[maybe_unused]] float trow[4] = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (FRC) {
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    if (w < 2 * B) {
+      const float* row = ((w & 1) ? f.teach2 : f.teach1) + ((int64_t)(w >> 1) * p.Td + min(t, p.Td - 1)) * Ti;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) trow[q] = row[min(l + 64 * q, Ti - 1)];
+    }
   }
   // ---- resident weights (registers for the whole launch)
   SliceR<4> sa, s1, s2; SliceR<2> sk;
@@ -598,7 +653,7 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(typename MegaArgT<GRP>::type 
   slice_fill(s2, p.W2, 4 * M2N, 32 * wg, 2 * M2N, 2 * M2N, 0, (int)threadIdx.x);
   slice_fill(sk, p.Wkvq, 3 * M2N, min(32 * wg, 3 * M2N - 32), M2N, M2N, 0, (int)threadIdx.x);
   uint4 wp0 = split_fill(p.Wp0, P0, FEED, wg, (int)threadIdx.x), wp1 = split_fill(p.Wp1, P1, P0, wg, (int)threadIdx.x);
-  uint4 wqr = split_fill(p.Wq, UQ, M2N, wg, (int)threadIdx.x), wot = split_fill(p.Wot, M2N, M2N, wg, (int)threadIdx.x);
+  uint4 wqr = FRC ? make_uint4(0u, 0u, 0u, 0u) : split_fill(p.Wq, UQ, M2N, wg, (int)threadIdx.x), wot = split_fill(p.Wot, M2N, M2N, wg, (int)threadIdx.x);
   uint4 wou = split_fill(p.Wout, p.ldout, M2N, wg, (int)threadIdx.x);
   const bool fold = p.Wfh && p.Wfl && p.bfb && !p.tin;      // folded feedback (free running only)
   uint4 wfh = fold ? split_fill(p.Wfh, P0, M2N, wg, (int)threadIdx.x) : make_uint4(0u, 0u, 0u, 0u);
@@ -631,7 +686,7 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(typename MegaArgT<GRP>::type 
   const int nsteps = p.nsteps;
   const bool sx = __builtin_amdgcn_readfirstlane((int)(spread > 1 && sx_lds != 0.f)) != 0;      // plain-store exchanges (same XCD, verified)
   for (int s = 0; s < nsteps; ++s, ++t) {
-    struct KArgsAll { satt_dec_mega_params p; int spread; typename MegaOptT<OPT>::type o; };      // the kernarg segment
+    struct KArgsAll { satt_dec_mega_params p; int spread; typename MegaOptT<OPT>::type o; typename MegaFrcT<FRC>::type f; };      // the kernarg segment
     // (GRP: the group's block in the array - it has a `p` and an `o` too - re-read like the kernarg segment)
     typedef const __attribute__((address_space(4))) typename std::conditional<GRP, satt_dec_mega_group, KArgsAll>::type KArgsM;
     KArgsM* kq = GRP ? (KArgsM*)gb : (KArgsM*)__builtin_amdgcn_kernarg_segment_ptr();
@@ -649,7 +704,7 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(typename MegaArgT<GRP>::type 
     }
     int oz = 0;
     asm volatile("" : "+v"(oz));
-    pin(sa); pin(s1); pin(s2); pin(sk); pin(wp0); pin(wp1); pin(wqr); pin(wot); pin(wou); pin(wfh); pin(wfl);
+    pin(sa); pin(s1); pin(s2); pin(sk); pin(wp0); pin(wp1); if constexpr (!FRC) pin(wqr); pin(wot); pin(wou); pin(wfh); pin(wfl);
     if constexpr (SPK) pin(wp02);
     const int tid = (int)threadIdx.x + oz, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     __builtin_assume(tid >= 0 && tid < M2T && wave >= 0 && wave < XW);
@@ -714,154 +769,179 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(typename MegaArgT<GRP>::type 
       *hs = (1.f - zh) * v + zh * *hs;
     });
     MPROF(6);
-    // ================= B1: query layer (split)
-    split_mul<NB>(wqr, X1, 512, UQ, bt + 16, SATT_ACT_NONE, nullptr, 0, gr + G.pq, gbs, tag, wg, B, rs, tid, sx);
-    MPROF(7);
-    gather_vec<NB>(gr + G.pq, gbs, UQ, tag, B, tid, err, dead, [&](int b, int i, float v) { va[b * M2N + i] = v; });
-    MPROF(8);
-    // ================= B2: energies of the own rows: row pr on wave 7 - pr (the polling waves stay free when there are <= 4 rows)
+    if constexpr (!FRC) {      // (forced alignments: no query layer, no energies - the pq and e exchanges do not exist)
+      // ================= B1: query layer (split)
+      split_mul<NB>(wqr, X1, 512, UQ, bt + 16, SATT_ACT_NONE, nullptr, 0, gr + G.pq, gbs, tag, wg, B, rs, tid, sx);
+      MPROF(7);
+      gather_vec<NB>(gr + G.pq, gbs, UQ, tag, B, tid, err, dead, [&](int b, int i, float v) { va[b * M2N + i] = v; });
+      MPROF(8);
+      // ================= B2: energies of the own rows: row pr on wave 7 - pr (the polling waves stay free when there are <= 4 rows)
 #ifdef SATT_MEGA_PROF
-    const unsigned long long en0 = wall_clock64();
+      const unsigned long long en0 = wall_clock64();
 #endif
-    for (int pr = 7 - wave; pr < B * R; pr += XW) {
-      const int b = pr / R, rr = pr - b * R, tt = r0 + rr;
-      if (tt < Ti) {
-        const float* kr = kls + (b * 8 + rr) * KLS;
-        const float* pq = va + b * M2N;
-        // location features: lane = (filter l & 7, tap group l >> 3): taps jj = group, group + 8; xor-reduced over the groups
-        const int f = lane & 7, jg = lane >> 3;
-        const float* ap = aprev + b * (M2TI + 16) + tt;
-        const float t0 = ap[jg], t1 = ap[jg + 8], f0 = Fs[jg * 8 + f], f1 = Fs[(jg + 8) * 8 + f];      // (Fs rows >= kernel are zero)
-        const float k2 = kr[M2N + lane], q2 = pq[min(U1 + lane, M2N - 1)], v2r = tab[2 * M2N + lane];
-        float part = t0 * f0 + t1 * f1;
-        part += swz_xor(part, 8); part += swz_xor(part, 16);
-        part += lane_xor32(part, lane);
-        float fl[8];
+      for (int pr = 7 - wave; pr < B * R; pr += XW) {
+        const int b = pr / R, rr = pr - b * R, tt = r0 + rr;
+        if (tt < Ti) {
+          const float* kr = kls + (b * 8 + rr) * KLS;
+          const float* pq = va + b * M2N;
+          // location features: lane = (filter l & 7, tap group l >> 3): taps jj = group, group + 8; xor-reduced over the groups
+          const int f = lane & 7, jg = lane >> 3;
+          const float* ap = aprev + b * (M2TI + 16) + tt;
+          const float t0 = ap[jg], t1 = ap[jg + 8], f0 = Fs[jg * 8 + f], f1 = Fs[(jg + 8) * 8 + f];      // (Fs rows >= kernel are zero)
+          const float k2 = kr[M2N + lane], q2 = pq[min(U1 + lane, M2N - 1)], v2r = tab[2 * M2N + lane];
+          float part = t0 * f0 + t1 * f1;
+          part += swz_xor(part, 8); part += swz_xor(part, 16);
+          part += lane_xor32(part, lane);
+          float fl[8];
 #pragma unroll
-        for (int ff = 0; ff < 8; ++ff) fl[ff] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(part), ff));
-        float a[2] = {0.f, v2r * tanhf_(k2 + q2)};          // (v2 is zero beyond U2, every operand finite)
+          for (int ff = 0; ff < 8; ++ff) fl[ff] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(part), ff));
+          float a[2] = {0.f, v2r * tanhf_(k2 + q2)};          // (v2 is zero beyond U2, every operand finite)
 #pragma unroll
-        for (int q0 = 0; q0 < 4; q0 += 2) {
-          if (64 * q0 < U1) {
-            const int d0 = lane + 64 * q0, d1 = d0 + 64;
-            const float ka = kr[d0], kb = kr[d1], ba_ = tab[M2N + d0], bb_ = tab[M2N + d1], pa = pq[d0], pb = pq[d1], wa_ = tab[d0], wb_ = tab[d1];
-            float ua[8], ub[8];
+          for (int q0 = 0; q0 < 4; q0 += 2) {
+            if (64 * q0 < U1) {
+              const int d0 = lane + 64 * q0, d1 = d0 + 64;
+              const float ka = kr[d0], kb = kr[d1], ba_ = tab[M2N + d0], bb_ = tab[M2N + d1], pa = pq[d0], pb = pq[d1], wa_ = tab[d0], wb_ = tab[d1];
+              float ua[8], ub[8];
 #pragma unroll
-            for (int ff = 0; ff < 8; ++ff) { ua[ff] = Us[ff * M2N + d0]; ub[ff] = Us[ff * M2N + d1]; }
-            float xa = ka + ba_ + pa, xb = kb + bb_ + pb;
+              for (int ff = 0; ff < 8; ++ff) { ua[ff] = Us[ff * M2N + d0]; ub[ff] = Us[ff * M2N + d1]; }
+              float xa = ka + ba_ + pa, xb = kb + bb_ + pb;
 #pragma unroll
-            for (int ff = 0; ff < 8; ++ff) { xa += fl[ff] * ua[ff]; xb += fl[ff] * ub[ff]; }
-            a[0] += wa_ * tanhf_(xa) + wb_ * tanhf_(xb);          // (v1, U and the keys are zero beyond U1; pq there is finite)
+              for (int ff = 0; ff < 8; ++ff) { xa += fl[ff] * ua[ff]; xb += fl[ff] * ub[ff]; }
+              a[0] += wa_ * tanhf_(xa) + wb_ * tanhf_(xb);          // (v1, U and the keys are zero beyond U1; pq there is finite)
+            }
           }
+          // (GRP with run-time widths: the compiler contracts the product v2r * tanh into the first add of the wave sum - one rounding
+          //  less than the B = 2 sibling, whose bits a group reproduces, has there; the LJ pair contracts alike.  The product is
+          //  made opaque so that it is rounded as in the sibling: tests/test_decode_groups_gpu.py compares a group with a B = 2 launch bit by bit)
+          if constexpr (GRP && !LJ) asm volatile("" : "+v"(a[1]));
+          wave_sum_multi<2>(a);
+          if (lane == 0) { zs[(b * 2 + 0) * 8 + rr] = a[0]; zs[(b * 2 + 1) * 8 + rr] = a[1]; }
         }
-        // (GRP with run-time widths: the compiler contracts the product v2r * tanh into the first add of the wave sum - one rounding
-        //  less than the B = 2 sibling, whose bits a group reproduces, has there; the LJ pair contracts alike.  The product is
-        //  made opaque so that it is rounded as in the sibling: tests/test_decode_groups_gpu.py compares a group with a B = 2 launch bit by bit)
-        if constexpr (GRP && !LJ) asm volatile("" : "+v"(a[1]));
-        wave_sum_multi<2>(a);
-        if (lane == 0) { zs[(b * 2 + 0) * 8 + rr] = a[0]; zs[(b * 2 + 1) * 8 + rr] = a[1]; }
       }
-    }
-    lds_barrier();
-    // The workgroup's 2 R energies of a sample are ONE contiguous run of granules [wg][mechanism][row], published by one store
-    // instruction: 200 separate 8-byte write-throughs into the same 26 lines (one per row and mechanism, as the first version did)
-    // serialise at the memory side - that exchange took 2.1 us where the others take 0.8.
-    // (rows beyond the sample's length are published too: their consumers mask them - every granule of [0, Ti) gets its tag)
-    if (wave == PUTW && lane < 2 * R * NB) {
-      const int b = lane / (2 * R), l = lane - b * 2 * R, mech = l / R, rr = l - mech * R;
-      if (b < B && r0 + rr < Ti) gput(gr + b * gbs + G.e + wg * 2 * R + l, tag, zs[(b * 2 + mech) * 8 + rr], sx);
-    }
+      lds_barrier();
+      // The workgroup's 2 R energies of a sample are ONE contiguous run of granules [wg][mechanism][row], published by one store
+      // instruction: 200 separate 8-byte write-throughs into the same 26 lines (one per row and mechanism, as the first version did)
+      // serialise at the memory side - that exchange took 2.1 us where the others take 0.8.
+      // (rows beyond the sample's length are published too: their consumers mask them - every granule of [0, Ti) gets its tag)
+      if (wave == PUTW && lane < 2 * R * NB) {
+        const int b = lane / (2 * R), l = lane - b * 2 * R, mech = l / R, rr = l - mech * R;
+        if (b < B && r0 + rr < Ti) gput(gr + b * gbs + G.e + wg * 2 * R + l, tag, zs[(b * 2 + mech) * 8 + rr], sx);
+      }
 #ifdef SATT_MEGA_PROF
-    if (wg == satt_mega2_prof_wg && threadIdx.x == 64 * PUTW) satt_mega2_prof[31] += wall_clock64() - en0;
+      if (wg == satt_mega2_prof_wg && threadIdx.x == 64 * PUTW) satt_mega2_prof[31] += wall_clock64() - en0;
 #endif
-    MPROF(9);
+      MPROF(9);
+    }
     // the context tables of sample 0 do not depend on the alignments: requested before the energy exchange
     TabR tb;
     if constexpr (!tres) tab_load(tb, p.ctab, 0, Ti, wg, tid);
-    // ================= C: softmax + forward recursion, one wave per (sample, mechanism): polls its energies into registers
-    if (wave < 2 * B) {
-      const int b = wave >> 1, mech = wave & 1, len = lens[b];
-      float* al = alpha + b * M2TI;
-      float* ap = aprev + b * (M2TI + 16) + PL;
-      float alv[4], alm[4], apv[4], ev[4];
+    if constexpr (!FRC) {
+      // ================= C: softmax + forward recursion, one wave per (sample, mechanism): polls its energies into registers
+      if (wave < 2 * B) {
+        const int b = wave >> 1, mech = wave & 1, len = lens[b];
+        float* al = alpha + b * M2TI;
+        float* ap = aprev + b * (M2TI + 16) + PL;
+        float alv[4], alm[4], apv[4], ev[4];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {      // (what the recursion needs of the previous step: requested before the poll)
-        const int i = lane + 64 * q;
-        alv[q] = al[i]; alm[q] = al[max(i - 1, 0)]; apv[q] = ap[i]; ev[q] = 0.f;
-      }
-      // transition agent: the query part of the next step's u and the agent table's entries, read before the poll too
-      [[maybe_unused]] float agq = 0.f, agv[4] = {0.f, 0.f, 0.f, 0.f};
-      [[maybe_unused]] bool agent = false;
-      if constexpr (OPT) {
-        agent = o.agentW != nullptr && mech == 0;
-        if (agent) {
+        for (int q = 0; q < 4; ++q) {      // (what the recursion needs of the previous step: requested before the poll)
+          const int i = lane + 64 * q;
+          alv[q] = al[i]; alm[q] = al[max(i - 1, 0)]; apv[q] = ap[i]; ev[q] = 0.f;
+        }
+        // transition agent: the query part of the next step's u and the agent table's entries, read before the poll too
+        [[maybe_unused]] float agq = 0.f, agv[4] = {0.f, 0.f, 0.f, 0.f};
+        [[maybe_unused]] bool agent = false;
+        if constexpr (OPT) {
+          agent = o.agentW != nullptr && mech == 0;
+          if (agent) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const int i = lane + 64 * q;
+              const float w = 64 * q < AGT ? tab[2 * M2N + 64 + i] : agx[i - AGT], x = va[b * M2N + i];
+              agq += i < U1 ? x * w : 0.f;
+              agv[q] = agt[b * M2TI + i];
+            }
+          }
+        }
+        {
+          const gu64* g[4];
+          u64 x[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int i = min(lane + 64 * q, Ti - 1), w = i / R;
+            g[q] = (const gu64*)(gr + b * gbs + G.e + w * 2 * R + mech * R + (i - w * R));
+            x[q] = 0;
+          }
+          if (!*dead && !poll_until<4>(g, tag, x)) {
+            if (lane == 0) __hip_atomic_store((gu32*)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            *dead = 1;
+          }
+#pragma unroll
+          for (int q = 0; q < 4; ++q) ev[q] = __uint_as_float((uint32_t)x[q]);
+        }
+        MPROF(24);
+        float m = -INFINITY;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) m = fmaxf(m, lane + 64 * q < len ? ev[q] : -INFINITY);
+        m = wave_max(m);
+        float x[4], sacc = 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { x[q] = lane + 64 * q < len ? __expf(ev[q] - m) : 0.f; sacc += x[q]; }
+        const float rsum = 1.f / wave_sum(sacc);
+        if (mech == 1) {
+          float* e = e2 + b * M2TI;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) e[lane + 64 * q] = x[q] * rsum;
+        } else {
+          float* e = e1 + b * M2TI;
+          float keep[4], s2_ = 0.f;
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const int i = lane + 64 * q;
-            const float w = 64 * q < AGT ? tab[2 * M2N + 64 + i] : agx[i - AGT], x = va[b * M2N + i];
-            agq += i < U1 ? x * w : 0.f;
-            agv[q] = agt[b * M2TI + i];
+            const float a = x[q] * rsum;
+            if (i < Ti) ap[i] = p.cumulative ? a + apv[q] : a;
+            keep[q] = a;
+            if constexpr (OPT) {      // (u_cur = 0.5 without the agent: the same bits as the constants)
+              if (p.att1_mode == 0) { keep[q] = i < Ti ? ((1.f - u_cur) * alv[q] + u_cur * (i > 0 ? alm[q] : 0.f) + 1e-7f) * a : 0.f; s2_ += keep[q]; }
+            } else {
+              if (p.att1_mode == 0) { keep[q] = i < Ti ? (0.5f * alv[q] + 0.5f * (i > 0 ? alm[q] : 0.f) + 1e-7f) * a : 0.f; s2_ += keep[q]; }
+            }
           }
+          if (p.att1_mode == 0) {
+            const float r2 = 1.f / wave_sum(s2_);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) keep[q] *= r2;
+          }
+          if constexpr (OPT) {
+            if (agent) {      // u of step t + 1 from this step's alignment (agent table: zero beyond Ti) and processed query
+              const float z = wave_sum(agq + ((keep[0] * agv[0] + keep[1] * agv[1]) + (keep[2] * agv[2] + keep[3] * agv[3])));
+              u_cur = 1.f / (1.f + __expf(-(z + agb)));
+              if (last && wg == 2 % M2G && lane == 0) o.u_state[b] = u_cur;      // (next to the forward variable's hand-over)
+            }
+          }
+#pragma unroll
+          for (int q = 0; q < 4; ++q) { al[lane + 64 * q] = keep[q]; e[lane + 64 * q] = keep[q]; }
         }
       }
-      {
-        const gu64* g[4];
-        u64 x[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int i = min(lane + 64 * q, Ti - 1), w = i / R;
-          g[q] = (const gu64*)(gr + b * gbs + G.e + w * 2 * R + mech * R + (i - w * R));
-          x[q] = 0;
-        }
-        if (!*dead && !poll_until<4>(g, tag, x)) {
-          if (lane == 0) __hip_atomic_store((gu32*)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          *dead = 1;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) ev[q] = __uint_as_float((uint32_t)x[q]);
-      }
-      MPROF(24);
-      float m = -INFINITY;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) m = fmaxf(m, lane + 64 * q < len ? ev[q] : -INFINITY);
-      m = wave_max(m);
-      float x[4], sacc = 0.f;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) { x[q] = lane + 64 * q < len ? __expf(ev[q] - m) : 0.f; sacc += x[q]; }
-      const float rsum = 1.f / wave_sum(sacc);
-      if (mech == 1) {
-        float* e = e2 + b * M2TI;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) e[lane + 64 * q] = x[q] * rsum;
-      } else {
-        float* e = e1 + b * M2TI;
-        float keep[4], s2_ = 0.f;
+    }
+    if constexpr (FRC) {
+      // ================= C (forced alignments): the step's alignments are row t of the teacher histories, in the registers of wave
+      // (sample, mechanism) since the step before.  TWO copies: as given (`alpha`: mechanism 1, `aprev`: mechanism 2 - the recursion
+      // state they hold otherwise does not exist here) for the histories and the hand-over, and masked by the length (e1 / e2) for the
+      // table products and the hand-over contexts (csrc/decode.hip dec_attn_context_k: r < len ? a[r] : 0)
+      if (wave < 2 * B) {
+        const int b = wave >> 1, mech = wave & 1, len = lens[b];
+        float* em = (mech ? e2 : e1) + b * M2TI;
+        float* eg = mech ? aprev + b * (M2TI + 16) : alpha + b * M2TI;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int i = lane + 64 * q;
-          const float a = x[q] * rsum;
-          if (i < Ti) ap[i] = p.cumulative ? a + apv[q] : a;
-          keep[q] = a;
-          if constexpr (OPT) {      // (u_cur = 0.5 without the agent: the same bits as the constants)
-            if (p.att1_mode == 0) { keep[q] = i < Ti ? ((1.f - u_cur) * alv[q] + u_cur * (i > 0 ? alm[q] : 0.f) + 1e-7f) * a : 0.f; s2_ += keep[q]; }
-          } else {
-            if (p.att1_mode == 0) { keep[q] = i < Ti ? (0.5f * alv[q] + 0.5f * (i > 0 ? alm[q] : 0.f) + 1e-7f) * a : 0.f; s2_ += keep[q]; }
-          }
+          const float v = i < Ti ? trow[q] : 0.f;
+          eg[i] = v; em[i] = i < len ? v : 0.f;
         }
-        if (p.att1_mode == 0) {
-          const float r2 = 1.f / wave_sum(s2_);
+        // row t + 1, a step ahead (the last row again behind the last step: in bounds, not used)
+        const float* row = (mech ? kq->f.teach2 : kq->f.teach1) + ((int64_t)b * p.Td + min(t + 1, p.Td - 1)) * Ti;
 #pragma unroll
-          for (int q = 0; q < 4; ++q) keep[q] *= r2;
-        }
-        if constexpr (OPT) {
-          if (agent) {      // u of step t + 1 from this step's alignment (agent table: zero beyond Ti) and processed query
-            const float z = wave_sum(agq + ((keep[0] * agv[0] + keep[1] * agv[1]) + (keep[2] * agv[2] + keep[3] * agv[3])));
-            u_cur = 1.f / (1.f + __expf(-(z + agb)));
-            if (last && wg == 2 % M2G && lane == 0) o.u_state[b] = u_cur;      // (next to the forward variable's hand-over)
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { al[lane + 64 * q] = keep[q]; e[lane + 64 * q] = keep[q]; }
+        for (int q = 0; q < 4; ++q) trow[q] = row[min(lane + 64 * q, Ti - 1)];
       }
     }
     MPROF(25);
@@ -872,8 +952,9 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(typename MegaArgT<GRP>::type 
       for (int i = tid; i < NB * Ti; i += M2T) {
         const int b = i / Ti, r = i - b * Ti;
         if (b < B) {
-          p.align1[((int64_t)b * p.Td + t) * Ti + r] = e1[b * M2TI + r];
-          p.align2[((int64_t)b * p.Td + t) * Ti + r] = e2[b * M2TI + r];
+          // (forced alignments: the rows as given - `alpha` / `aprev` of phase C -, not the masked copies the products read)
+          p.align1[((int64_t)b * p.Td + t) * Ti + r] = FRC ? alpha[b * M2TI + r] : e1[b * M2TI + r];
+          p.align2[((int64_t)b * p.Td + t) * Ti + r] = FRC ? aprev[b * (M2TI + 16) + r] : e2[b * M2TI + r];
         }
       }
     }
@@ -881,8 +962,9 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(typename MegaArgT<GRP>::type 
       for (int i = tid; i < NB * Ti; i += M2T) {
         const int b = i / Ti, r = i - b * Ti;
         if (b < B) {
-          p.a_state[((int64_t)(par ^ 1) * B + b) * Ti + r] = aprev[b * (M2TI + 16) + PL + r];
-          p.alpha_state[((int64_t)(par ^ 1) * B + b) * Ti + r] = e1[b * M2TI + r];
+          // (forced alignments, csrc/decode.hip dec_attn_context_k: both receive the given row of mechanism 1)
+          p.a_state[((int64_t)(par ^ 1) * B + b) * Ti + r] = FRC ? alpha[b * M2TI + r] : aprev[b * (M2TI + 16) + PL + r];
+          p.alpha_state[((int64_t)(par ^ 1) * B + b) * Ti + r] = FRC ? alpha[b * M2TI + r] : e1[b * M2TI + r];
         }
       }
     }
@@ -1351,8 +1433,9 @@ __host__ __device__ inline size_t mega2s_lds_bytes(int NB, int Ti) {
   return fl * sizeof(float);
 }
 
-template <int NB, bool TRES, bool SPK, bool GRP = false>
-__global__ __launch_bounds__(M2T) void dec_mega2_single_k(typename MegaArgT<GRP>::type p, const int spread) {
+template <int NB, bool TRES, bool SPK, bool GRP = false, bool FRC = false>
+__global__ __launch_bounds__(M2T) void dec_mega2_single_k(typename MegaArgT<GRP>::type p, const int spread, const typename MegaFrcT<FRC>::type f) {
+  static_assert(!(FRC && GRP), "forced alignments: a single launch");
   [[maybe_unused]] int gm = 1;
   [[maybe_unused]] MegaGrpC* gb = nullptr;
   if constexpr (GRP) {      // group mode: see dec_mega2_k
@@ -1422,20 +1505,24 @@ __global__ __launch_bounds__(M2T) void dec_mega2_single_k(typename MegaArgT<GRP>
       sx_lds = rs[M2G];
       __syncthreads();
     }
-    for (int i = tid; i < 8 * M2N; i += M2T) { const int f = i / M2N, u = i - f * M2N; Us[i] = (f < F && u < U1) ? p.locU[f * U1 + u] : 0.f; }
-    for (int i = tid; i < 2 * M2N; i += M2T) {
-      const int w = i / M2N, u = i - w * M2N;
-      float v = u < U1 ? (w == 0 ? p.v1[u] : p.b1[u]) : 0.f;
-      if (w == 1 && u < U1)
-        for (int f = 0; f < F; ++f) v += p.locFb[f] * p.locU[f * U1 + u];
-      tab[i] = v;
+    if constexpr (!FRC) {      // (forced alignments: nothing reads the location layer, v / b or the agent's weights)
+      for (int i = tid; i < 8 * M2N; i += M2T) { const int f = i / M2N, u = i - f * M2N; Us[i] = (f < F && u < U1) ? p.locU[f * U1 + u] : 0.f; }
+      for (int i = tid; i < 2 * M2N; i += M2T) {
+        const int w = i / M2N, u = i - w * M2N;
+        float v = u < U1 ? (w == 0 ? p.v1[u] : p.b1[u]) : 0.f;
+        if (w == 1 && u < U1)
+          for (int f = 0; f < F; ++f) v += p.locFb[f] * p.locU[f * U1 + u];
+        tab[i] = v;
+      }
     }
     if (tid < 4) lens[tid] = tid < B ? (int)p.lengths[tid] : 0;
-    for (int i = tid; i < NB * 8 * M2N; i += M2T) {
-      const int row = i / M2N, u = i - row * M2N, b = row / 8, rr = row - b * 8, tt = r0 + rr;
-      kls[i] = (b < B && rr < R && tt < Ti && u < U1) ? p.keys1[((int64_t)b * Ti + tt) * U1 + u] : 0.f;
+    if constexpr (!FRC) {      // (... nor the key table or the location filters)
+      for (int i = tid; i < NB * 8 * M2N; i += M2T) {
+        const int row = i / M2N, u = i - row * M2N, b = row / 8, rr = row - b * 8, tt = r0 + rr;
+        kls[i] = (b < B && rr < R && tt < Ti && u < U1) ? p.keys1[((int64_t)b * Ti + tt) * U1 + u] : 0.f;
+      }
+      for (int i = tid; i < 16 * 8; i += M2T) { const int j = i >> 3, f = i & 7; Fs[i] = (f < F && j < KW) ? p.locF[j * F + f] : 0.f; }
     }
-    for (int i = tid; i < 16 * 8; i += M2T) { const int j = i >> 3, f = i & 7; Fs[i] = (f < F && j < KW) ? p.locF[j * F + f] : 0.f; }
     if (tid < 40) {
       const int l = tid >> 3, n = 8 * wg + (tid & 7);
       const float* bp = l == 0 ? p.bp0 : (l == 1 ? p.bp1 : (l == 4 ? p.bout : nullptr));
@@ -1453,6 +1540,9 @@ __global__ __launch_bounds__(M2T) void dec_mega2_single_k(typename MegaArgT<GRP>
     // state of step t: location-conv input, forward variable, recurrent vectors, the previous step's alignment, the fed frame
     for (int i = tid; i < NB * Ti; i += M2T) {
       const int b = i / Ti, r = i - b * Ti;
+      if constexpr (FRC) {      // (dec_mega2_k: the history row is as given, the table products take it masked by the length)
+        if (b < B && t > 0) e1[b * M2TI + r] = r < lens[b] ? p.align1[((int64_t)b * p.Td + t - 1) * Ti + r] : 0.f;
+      } else
       if (b < B) {
         aprev[b * (M2TI + 16) + PL + r] = p.a_state[((int64_t)par * B + b) * Ti + r];
         alpha[b * M2TI + r] = p.alpha_state[((int64_t)par * B + b) * Ti + r];
@@ -1484,13 +1574,23 @@ __global__ __launch_bounds__(M2T) void dec_mega2_single_k(typename MegaArgT<GRP>
     const int l = threadIdx.x & 63, w = threadIdx.x >> 6, n = 8 * wg + (l & 7);
     if ((w == PUTW || w == AUXW) && l < 8 * NB && n < P0) { spk = p.sproj[(l >> 3) * P0 + n]; bp02 = p.bp02[n]; }
   }
+  // forced alignments: wave b holds row t of its sample's teacher history in registers (dec_mega2_k: requested a step ahead)
+  [[maybe_unused]] float trow[4] = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (FRC) {
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    if (w < B) {
+      const float* row = f.teach1 + ((int64_t)w * p.Td + min(t, p.Td - 1)) * Ti;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) trow[q] = row[min(l + 64 * q, Ti - 1)];
+    }
+  }
   // ---- resident weights (registers for the whole launch)
   SliceR<4> sa, s1, s2;
   slice_fill(sa, p.Wa, 4 * M2N, 32 * wg, P1 + M2N, P1, V1, (int)threadIdx.x);
   slice_fill(s1, p.W1, 4 * M2N, 32 * wg, 2 * M2N, M2N, V1, (int)threadIdx.x);
   slice_fill(s2, p.W2, 4 * M2N, 32 * wg, 2 * M2N, 2 * M2N, 0, (int)threadIdx.x);
   uint4 wp0 = split_fill(p.Wp0, P0, FEED, wg, (int)threadIdx.x), wp1 = split_fill(p.Wp1, P1, P0, wg, (int)threadIdx.x);
-  uint4 wqr = split_fill_any(p.Wq, U1, M2N, wg, (int)threadIdx.x);
+  uint4 wqr = FRC ? make_uint4(0u, 0u, 0u, 0u) : split_fill_any(p.Wq, U1, M2N, wg, (int)threadIdx.x);
   uint4 wou = split_fill(p.Wout, p.ldout, M2N, wg, (int)threadIdx.x);
   const bool fold = p.Wfh && p.Wfl && p.bfb && !p.tin;      // folded feedback (free running only)
   uint4 wfh = fold ? split_fill(p.Wfh, P0, M2N, wg, (int)threadIdx.x) : make_uint4(0u, 0u, 0u, 0u);
@@ -1521,14 +1621,14 @@ __global__ __launch_bounds__(M2T) void dec_mega2_single_k(typename MegaArgT<GRP>
   const int nsteps = p.nsteps;
   const bool sx = __builtin_amdgcn_readfirstlane((int)(spread > 1 && sx_lds != 0.f)) != 0;
   for (int s = 0; s < nsteps; ++s, ++t) {
-    struct KArgsAll { satt_dec_mega_params p; int spread; };      // the kernarg segment
+    struct KArgsAll { satt_dec_mega_params p; int spread; typename MegaFrcT<FRC>::type f; };      // the kernarg segment
     typedef const __attribute__((address_space(4))) typename std::conditional<GRP, satt_dec_mega_group, KArgsAll>::type KArgsM;      // (dec_mega2_k)
     KArgsM* kq = GRP ? (KArgsM*)gb : (KArgsM*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(kq));
     const auto& p = kq->p;
     int oz = 0;
     asm volatile("" : "+v"(oz));
-    pin(sa); pin(s1); pin(s2); pin(wp0); pin(wp1); pin(wqr); pin(wou); pin(wfh); pin(wfl);
+    pin(sa); pin(s1); pin(s2); pin(wp0); pin(wp1); if constexpr (!FRC) pin(wqr); pin(wou); pin(wfh); pin(wfl);
     if constexpr (SPK) pin(wp02);
     const int tid = (int)threadIdx.x + oz, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     __builtin_assume(tid >= 0 && tid < M2T && wave >= 0 && wave < XW);
@@ -1591,107 +1691,129 @@ __global__ __launch_bounds__(M2T) void dec_mega2_single_k(typename MegaArgT<GRP>
       *hs = (1.f - zh) * v + zh * *hs;
     });
     MPROF(6);
-    // ================= B1: query layer (split)
-    split_mul<NB>(wqr, X1, 512, U1, bt + 16, SATT_ACT_NONE, nullptr, 0, gr + G.pq, gbs, tag, wg, B, rs, tid, sx);
-    MPROF(7);
-    gather_vec<NB>(gr + G.pq, gbs, U1, tag, B, tid, err, dead, [&](int b, int i, float v) { va[b * M2N + i] = v; });
-    MPROF(8);
-    // ================= B2: energies of the own rows: row pr on wave 7 - pr
-    for (int pr = 7 - wave; pr < B * R; pr += XW) {
-      const int b = pr / R, rr = pr - b * R, tt = r0 + rr;
-      if (tt < Ti) {
-        const float* kr = kls + (b * 8 + rr) * M2N;
-        const float* pq = va + b * M2N;
-        const int f = lane & 7, jg = lane >> 3;
-        const float* ap = aprev + b * (M2TI + 16) + tt;
-        const float t0 = ap[jg], t1 = ap[jg + 8], f0 = Fs[jg * 8 + f], f1 = Fs[(jg + 8) * 8 + f];      // (Fs rows >= kernel are zero)
-        float part = t0 * f0 + t1 * f1;
-        part += swz_xor(part, 8); part += swz_xor(part, 16);
-        part += lane_xor32(part, lane);
-        float fl[8];
+    if constexpr (!FRC) {      // (forced alignments: no query layer, no energies - the pq and e exchanges do not exist)
+      // ================= B1: query layer (split)
+      split_mul<NB>(wqr, X1, 512, U1, bt + 16, SATT_ACT_NONE, nullptr, 0, gr + G.pq, gbs, tag, wg, B, rs, tid, sx);
+      MPROF(7);
+      gather_vec<NB>(gr + G.pq, gbs, U1, tag, B, tid, err, dead, [&](int b, int i, float v) { va[b * M2N + i] = v; });
+      MPROF(8);
+      // ================= B2: energies of the own rows: row pr on wave 7 - pr
+      for (int pr = 7 - wave; pr < B * R; pr += XW) {
+        const int b = pr / R, rr = pr - b * R, tt = r0 + rr;
+        if (tt < Ti) {
+          const float* kr = kls + (b * 8 + rr) * M2N;
+          const float* pq = va + b * M2N;
+          const int f = lane & 7, jg = lane >> 3;
+          const float* ap = aprev + b * (M2TI + 16) + tt;
+          const float t0 = ap[jg], t1 = ap[jg + 8], f0 = Fs[jg * 8 + f], f1 = Fs[(jg + 8) * 8 + f];      // (Fs rows >= kernel are zero)
+          float part = t0 * f0 + t1 * f1;
+          part += swz_xor(part, 8); part += swz_xor(part, 16);
+          part += lane_xor32(part, lane);
+          float fl[8];
 #pragma unroll
-        for (int ff = 0; ff < 8; ++ff) fl[ff] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(part), ff));
-        float a = 0.f;
+          for (int ff = 0; ff < 8; ++ff) fl[ff] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(part), ff));
+          float a = 0.f;
 #pragma unroll
-        for (int q0 = 0; q0 < 4; q0 += 2) {
-          if (64 * q0 < U1) {
-            const int d0 = lane + 64 * q0, d1 = d0 + 64;
-            const float ka = kr[d0], kb = kr[d1], ba_ = tab[M2N + d0], bb_ = tab[M2N + d1], pa = pq[d0], pb = pq[d1], wa_ = tab[d0], wb_ = tab[d1];
-            float ua[8], ub[8];
+          for (int q0 = 0; q0 < 4; q0 += 2) {
+            if (64 * q0 < U1) {
+              const int d0 = lane + 64 * q0, d1 = d0 + 64;
+              const float ka = kr[d0], kb = kr[d1], ba_ = tab[M2N + d0], bb_ = tab[M2N + d1], pa = pq[d0], pb = pq[d1], wa_ = tab[d0], wb_ = tab[d1];
+              float ua[8], ub[8];
 #pragma unroll
-            for (int ff = 0; ff < 8; ++ff) { ua[ff] = Us[ff * M2N + d0]; ub[ff] = Us[ff * M2N + d1]; }
-            float xa = ka + ba_ + pa, xb = kb + bb_ + pb;
+              for (int ff = 0; ff < 8; ++ff) { ua[ff] = Us[ff * M2N + d0]; ub[ff] = Us[ff * M2N + d1]; }
+              float xa = ka + ba_ + pa, xb = kb + bb_ + pb;
 #pragma unroll
-            for (int ff = 0; ff < 8; ++ff) { xa += fl[ff] * ua[ff]; xb += fl[ff] * ub[ff]; }
-            a += wa_ * tanhf_(xa) + wb_ * tanhf_(xb);          // (v1, U and the keys are zero beyond U1; pq there is finite)
+              for (int ff = 0; ff < 8; ++ff) { xa += fl[ff] * ua[ff]; xb += fl[ff] * ub[ff]; }
+              a += wa_ * tanhf_(xa) + wb_ * tanhf_(xb);          // (v1, U and the keys are zero beyond U1; pq there is finite)
+            }
           }
+          a = wave_sum(a);
+          if (lane == 0) zs[b * 8 + rr] = a;
         }
-        a = wave_sum(a);
-        if (lane == 0) zs[b * 8 + rr] = a;
       }
+      lds_barrier();
+      // the workgroup's R energies of a sample: ONE contiguous run of granules (row index = granule index), one store instruction
+      if (wave == PUTW && lane < R * NB) {
+        const int b = lane / R, rr = lane - b * R;
+        if (b < B && r0 + rr < Ti) gput(gr + b * gbs + G.e + r0 + rr, tag, zs[b * 8 + rr], sx);
+      }
+      MPROF(9);
     }
-    lds_barrier();
-    // the workgroup's R energies of a sample: ONE contiguous run of granules (row index = granule index), one store instruction
-    if (wave == PUTW && lane < R * NB) {
-      const int b = lane / R, rr = lane - b * R;
-      if (b < B && r0 + rr < Ti) gput(gr + b * gbs + G.e + r0 + rr, tag, zs[b * 8 + rr], sx);
-    }
-    MPROF(9);
     // the context tables of sample 0 do not depend on the alignment: requested before the energy exchange
     TabR1 tb;
     if constexpr (!tres) tab1_load(tb, p.ctab, 0, Ti, wg, tid);
-    // ================= C: softmax + forward recursion, one wave per sample: polls its energies into registers
-    if (wave < B) {
-      const int b = wave, len = lens[b];
-      float* al = alpha + b * M2TI;
-      float* ap = aprev + b * (M2TI + 16) + PL;
-      float alv[4], alm[4], apv[4], ev[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int i = lane + 64 * q;
-        alv[q] = al[i]; alm[q] = al[max(i - 1, 0)]; apv[q] = ap[i]; ev[q] = 0.f;
-      }
-      {
-        const gu64* g[4];
-        u64 x[4];
+    if constexpr (!FRC) {
+      // ================= C: softmax + forward recursion, one wave per sample: polls its energies into registers
+      if (wave < B) {
+        const int b = wave, len = lens[b];
+        float* al = alpha + b * M2TI;
+        float* ap = aprev + b * (M2TI + 16) + PL;
+        float alv[4], alm[4], apv[4], ev[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          g[q] = (const gu64*)(gr + b * gbs + G.e + min(lane + 64 * q, Ti - 1));
-          x[q] = 0;
+          const int i = lane + 64 * q;
+          alv[q] = al[i]; alm[q] = al[max(i - 1, 0)]; apv[q] = ap[i]; ev[q] = 0.f;
         }
-        if (!*dead && !poll_until<4>(g, tag, x)) {
-          if (lane == 0) __hip_atomic_store((gu32*)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          *dead = 1;
+        {
+          const gu64* g[4];
+          u64 x[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            g[q] = (const gu64*)(gr + b * gbs + G.e + min(lane + 64 * q, Ti - 1));
+            x[q] = 0;
+          }
+          if (!*dead && !poll_until<4>(g, tag, x)) {
+            if (lane == 0) __hip_atomic_store((gu32*)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            *dead = 1;
+          }
+#pragma unroll
+          for (int q = 0; q < 4; ++q) ev[q] = __uint_as_float((uint32_t)x[q]);
+        }
+        MPROF(24);
+        float m = -INFINITY;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) m = fmaxf(m, lane + 64 * q < len ? ev[q] : -INFINITY);
+        m = wave_max(m);
+        float x[4], sacc = 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { x[q] = lane + 64 * q < len ? __expf(ev[q] - m) : 0.f; sacc += x[q]; }
+        const float rsum = 1.f / wave_sum(sacc);
+        float* e = e1 + b * M2TI;
+        float keep[4], s2_ = 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int i = lane + 64 * q;
+          const float a = x[q] * rsum;
+          if (i < Ti) ap[i] = p.cumulative ? a + apv[q] : a;
+          keep[q] = a;
+          if (p.att1_mode == 0) { keep[q] = i < Ti ? (0.5f * alv[q] + 0.5f * (i > 0 ? alm[q] : 0.f) + 1e-7f) * a : 0.f; s2_ += keep[q]; }
+        }
+        if (p.att1_mode == 0) {
+          const float r2 = 1.f / wave_sum(s2_);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) keep[q] *= r2;
         }
 #pragma unroll
-        for (int q = 0; q < 4; ++q) ev[q] = __uint_as_float((uint32_t)x[q]);
+        for (int q = 0; q < 4; ++q) { al[lane + 64 * q] = keep[q]; e[lane + 64 * q] = keep[q]; }
       }
-      MPROF(24);
-      float m = -INFINITY;
+    }
+    if constexpr (FRC) {
+      // ================= C (forced alignments; dec_mega2_k): row t of the teacher history from wave b's registers - as given into
+      // `alpha` (history, hand-over), masked by the length into e1 (table products, hand-over context) - and the request for row t + 1
+      if (wave < B) {
+        const int b = wave, len = lens[b];
+        float* em = e1 + b * M2TI;
+        float* eg = alpha + b * M2TI;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) m = fmaxf(m, lane + 64 * q < len ? ev[q] : -INFINITY);
-      m = wave_max(m);
-      float x[4], sacc = 0.f;
+        for (int q = 0; q < 4; ++q) {
+          const int i = lane + 64 * q;
+          const float v = i < Ti ? trow[q] : 0.f;
+          eg[i] = v; em[i] = i < len ? v : 0.f;
+        }
+        const float* row = kq->f.teach1 + ((int64_t)b * p.Td + min(t + 1, p.Td - 1)) * Ti;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) { x[q] = lane + 64 * q < len ? __expf(ev[q] - m) : 0.f; sacc += x[q]; }
-      const float rsum = 1.f / wave_sum(sacc);
-      float* e = e1 + b * M2TI;
-      float keep[4], s2_ = 0.f;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int i = lane + 64 * q;
-        const float a = x[q] * rsum;
-        if (i < Ti) ap[i] = p.cumulative ? a + apv[q] : a;
-        keep[q] = a;
-        if (p.att1_mode == 0) { keep[q] = i < Ti ? (0.5f * alv[q] + 0.5f * (i > 0 ? alm[q] : 0.f) + 1e-7f) * a : 0.f; s2_ += keep[q]; }
+        for (int q = 0; q < 4; ++q) trow[q] = row[min(lane + 64 * q, Ti - 1)];
       }
-      if (p.att1_mode == 0) {
-        const float r2 = 1.f / wave_sum(s2_);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) keep[q] *= r2;
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) { al[lane + 64 * q] = keep[q]; e[lane + 64 * q] = keep[q]; }
     }
     MPROF(25);
     lds_barrier();
@@ -1700,15 +1822,16 @@ __global__ __launch_bounds__(M2T) void dec_mega2_single_k(typename MegaArgT<GRP>
     if (wg == 1 % M2G) {
       for (int i = tid; i < NB * Ti; i += M2T) {
         const int b = i / Ti, r = i - b * Ti;
-        if (b < B) p.align1[((int64_t)b * p.Td + t) * Ti + r] = e1[b * M2TI + r];
+        if (b < B) p.align1[((int64_t)b * p.Td + t) * Ti + r] = FRC ? alpha[b * M2TI + r] : e1[b * M2TI + r];      // (forced: as given)
       }
     }
     if (last && wg == 2 % M2G) {
       for (int i = tid; i < NB * Ti; i += M2T) {
         const int b = i / Ti, r = i - b * Ti;
         if (b < B) {
-          p.a_state[((int64_t)(par ^ 1) * B + b) * Ti + r] = aprev[b * (M2TI + 16) + PL + r];
-          p.alpha_state[((int64_t)(par ^ 1) * B + b) * Ti + r] = e1[b * M2TI + r];
+          // (forced alignments, csrc/decode.hip dec_attn_context_k: both receive the given row of mechanism 1)
+          p.a_state[((int64_t)(par ^ 1) * B + b) * Ti + r] = FRC ? alpha[b * M2TI + r] : aprev[b * (M2TI + 16) + PL + r];
+          p.alpha_state[((int64_t)(par ^ 1) * B + b) * Ti + r] = FRC ? alpha[b * M2TI + r] : e1[b * M2TI + r];
         }
       }
     }
@@ -1980,9 +2103,11 @@ extern "C" int satt_dec_mega_opt(const satt_dec_mega_params* pp, const satt_dec_
   const int NB = (var & SATT_MEGA_VAR_TWO_SAMPLES) ? 2 : 1;
   const size_t smem = single ? mega2s_lds_bytes(NB, p.Ti) : mega2_lds_bytes(NB, p.Ti, has_opt);
   if (smem > 160 * 1024) return SATT_E_UNSUPPORTED;      // (B = 2 with options: 163 104 bytes - every supported shape fits)
-#define SATT_MEGA2S(NBV, TR) (spk ? mega_launch(dec_mega2_single_k<NBV, TR, true>, smem, s, p) : mega_launch(dec_mega2_single_k<NBV, TR, false>, smem, s, p))
+#define SATT_MEGA2S(NBV, TR) \
+  (spk ? mega_launch(dec_mega2_single_k<NBV, TR, true>, smem, s, p, MegaNoFrc()) : mega_launch(dec_mega2_single_k<NBV, TR, false>, smem, s, p, MegaNoFrc()))
 #define SATT_MEGA2O(NBV, TR, LJV, SP) \
-  (has_opt ? mega_launch(dec_mega2_k<NBV, TR, LJV, SP, true>, smem, s, p, *opt) : mega_launch(dec_mega2_k<NBV, TR, LJV, SP, false>, smem, s, p, MegaNoOpt()))
+  (has_opt ? mega_launch(dec_mega2_k<NBV, TR, LJV, SP, true>, smem, s, p, *opt, MegaNoFrc()) : \
+             mega_launch(dec_mega2_k<NBV, TR, LJV, SP, false>, smem, s, p, MegaNoOpt(), MegaNoFrc()))
 #define SATT_MEGA2L(NBV, TR, SP) (lj ? SATT_MEGA2O(NBV, TR, true, SP) : SATT_MEGA2O(NBV, TR, false, SP))
 #define SATT_MEGA2D(NBV, TR) (spk ? SATT_MEGA2L(NBV, TR, true) : SATT_MEGA2L(NBV, TR, false))
   // (the ladders name the 30 instantiations in the order they always had, the single form's first: the device compiler emits them
@@ -1997,6 +2122,51 @@ extern "C" int satt_dec_mega_opt(const satt_dec_mega_params* pp, const satt_dec_
 }
 
 extern "C" int satt_dec_mega(const satt_dec_mega_params* pp, void* stream) { return satt_dec_mega_opt(pp, nullptr, stream); }
+
+// ---- forced alignments (include/satt_hip.h: satt_dec_mega_forced_params; template flag FRC of both kernels).  Without teacher rows
+// the entry points ARE the ones above.  The forced instantiations are siblings of the generic-width ones only (18: 12 dual, 6 single).
+namespace {
+inline bool frc_on(const satt_dec_mega_forced_params* f) { return f && f->teach1; }
+}  // namespace
+
+extern "C" int satt_dec_mega_forced_variant(const satt_dec_mega_params* pp, const satt_dec_mega_opt_params* opt, const satt_dec_mega_forced_params* f) {
+  if (!frc_on(f)) return satt_dec_mega_opt_variant(pp, opt);
+  if (opt_agent(opt)) return -1;                     // the agent never runs under forced alignments
+  const int var = satt_dec_mega_opt_variant(pp, opt);
+  if (var < 0) return var;
+  if (!(var & SATT_MEGA_VAR_SINGLE) && !f->teach2) return -1;
+  return (var & ~SATT_MEGA_VAR_LJ) | SATT_MEGA_VAR_FORCED;
+}
+
+extern "C" int satt_dec_mega_forced(const satt_dec_mega_params* pp, const satt_dec_mega_opt_params* opt, const satt_dec_mega_forced_params* f,
+                                    void* stream) {
+  if (!frc_on(f)) return satt_dec_mega_opt(pp, opt, stream);
+  if (!pp || !satt_dec_mega_supported(pp)) return SATT_E_UNSUPPORTED;
+  const satt_dec_mega_params& p = *pp;
+  if (opt_agent(opt)) return SATT_E_UNSUPPORTED;
+  if (const int rc = mega_check_block(p, opt)) return rc;
+  const bool single = mega_single(p);
+  if (!single && !f->teach2) return SATT_E_BADARG;
+  hipStream_t s = (hipStream_t)stream;
+  const int var = satt_dec_mega_forced_variant(pp, opt, f);
+  if (var < 0) return SATT_E_UNSUPPORTED;
+  const bool tables = var & SATT_MEGA_VAR_TABLES_LDS, spk = var & SATT_MEGA_VAR_SPEAKER, has_opt = var & SATT_MEGA_VAR_DROPOUT;
+  const int NB = (var & SATT_MEGA_VAR_TWO_SAMPLES) ? 2 : 1;
+  const size_t smem = single ? mega2s_lds_bytes(NB, p.Ti) : mega2_lds_bytes(NB, p.Ti, has_opt);
+  if (smem > 160 * 1024) return SATT_E_UNSUPPORTED;
+#define SATT_MEGA2FS(NBV, TR) \
+  (spk ? mega_launch(dec_mega2_single_k<NBV, TR, true, false, true>, smem, s, p, *f) : mega_launch(dec_mega2_single_k<NBV, TR, false, false, true>, smem, s, p, *f))
+#define SATT_MEGA2FO(NBV, TR, SP) \
+  (has_opt ? mega_launch(dec_mega2_k<NBV, TR, false, SP, true, false, true>, smem, s, p, *opt, *f) : \
+             mega_launch(dec_mega2_k<NBV, TR, false, SP, false, false, true>, smem, s, p, MegaNoOpt(), *f))
+#define SATT_MEGA2FD(NBV, TR) (spk ? SATT_MEGA2FO(NBV, TR, true) : SATT_MEGA2FO(NBV, TR, false))
+#define SATT_MEGA2F(K) (tables ? K(1, true) : NB == 1 ? K(1, false) : K(2, false))
+  return single ? SATT_MEGA2F(SATT_MEGA2FS) : SATT_MEGA2F(SATT_MEGA2FD);
+#undef SATT_MEGA2FS
+#undef SATT_MEGA2FO
+#undef SATT_MEGA2FD
+#undef SATT_MEGA2F
+}
 
 // ---- group mode (include/satt_hip.h: satt_dec_mega_group)
 extern "C" int64_t satt_dec_mega_groups_scratch_floats(int ngroups, int heads, int hd) {
@@ -2050,9 +2220,11 @@ extern "C" int satt_dec_mega_groups(const satt_dec_mega_group* hb, const void* d
   static_cast<satt_dec_mega_params&>(ga) = p;
   ga.blocks = (const satt_dec_mega_group*)device_blocks; ga.ngroups = ngroups;
 #define SATT_MEGA2GO(LJV, SP) \
-  (has_opt ? mega_launch(dec_mega2_k<2, false, LJV, SP, true, true>, smem, s, ga, hb[0].o) : mega_launch(dec_mega2_k<2, false, LJV, SP, false, true>, smem, s, ga, MegaNoOpt()))
+  (has_opt ? mega_launch(dec_mega2_k<2, false, LJV, SP, true, true>, smem, s, ga, hb[0].o, MegaNoFrc()) : \
+             mega_launch(dec_mega2_k<2, false, LJV, SP, false, true>, smem, s, ga, MegaNoOpt(), MegaNoFrc()))
 #define SATT_MEGA2GL(SP) (lj ? SATT_MEGA2GO(true, SP) : SATT_MEGA2GO(false, SP))
-  if (single) return spk ? mega_launch(dec_mega2_single_k<2, false, true, true>, smem, s, ga) : mega_launch(dec_mega2_single_k<2, false, false, true>, smem, s, ga);
+  if (single)
+    return spk ? mega_launch(dec_mega2_single_k<2, false, true, true>, smem, s, ga, MegaNoFrc()) : mega_launch(dec_mega2_single_k<2, false, false, true>, smem, s, ga, MegaNoFrc());
   return spk ? SATT_MEGA2GL(true) : SATT_MEGA2GL(false);
 #undef SATT_MEGA2GO
 #undef SATT_MEGA2GL

@@ -57,11 +57,15 @@ class DecodeSession:
         # The baseline model (one source, no decoder self-attention) is offered as the kernel's SINGLE-SOURCE form: a block with
         # Ds = heads = U2 = V2 = 0.  With the transition agent or live inference dropout it stays on the launch-per-layer path (the
         # single form takes no options).
+        # Forced alignments (teacher_alignments=) take the kernel's FORCED instantiations (satt_dec_mega_forced: the mechanisms are
+        # bypassed, the teacher rows are the alignments) for every model the free-running session takes - and for the transition-agent
+        # models, dual AND baseline, without any option block: the agent is dead under forced alignments.
+        mega_forced = forced and self.MEGA_FORCED
+        live_drop = c.apply_dropout_on_inference and c.dec_prenet_drop > 0
         dual_form = c.dual and bool(Ds) and c.dec_sa_num_hop == 1
-        single_form = (not c.dual and not Ds and not c.transition_agent and
-                       not (c.apply_dropout_on_inference and c.dec_prenet_drop > 0))
+        single_form = not c.dual and not Ds and (not c.transition_agent or mega_forced) and not live_drop
         self._mega_single = False
-        if (self.MEGA and use_graph and not forced and (dual_form or single_form) and len(c.dec_prenet) == 2 and
+        if (self.MEGA and use_graph and (not forced or mega_forced) and (dual_form or single_form) and len(c.dec_prenet) == 2 and
                 ops.get_precision() == "bf16" and B <= self.MEGA_MAX_B):
             sh2 = dict(Ds=Ds, heads=c.dec_sa_heads, U2=U2, V2=V2) if dual_form else dict(Ds=0, heads=0, U2=0, V2=0)
             shape = dict(B=B, Td=Td, Ti=Ti, A=A, D=D, U1=U1, V1=V1, **sh2, kernel=c.att_kernel,
@@ -215,7 +219,8 @@ class DecodeSession:
         self.graph = None
         # ---- persistent form (csrc/decode_mega2.hip): the same step, ONE launch per K steps on 32 persistent workgroups that exchange
         # {tag, value} granules instead of nine dependent launches - for the configurations satt_dec_mega_supported took above
-        self.mega = self.mega_opt = self.mega_groups = None
+        self.mega = self.mega_opt = self.mega_groups = self.mega_forced = None
+        self.agent_tab = self.u_state = None
         self.ctab = self._ctw = None
         if self._mega_shape is not None:
             single = self._mega_single
@@ -261,9 +266,11 @@ class DecodeSession:
             # options of the kernel (a block of their own; None: ops.dec_mega as ever).  Transition agent: the kernel forms no
             # context, so the context part of u's dot product comes from a per-utterance table values1 Wa[:V1]
             # (build_context_tables) and u crosses launches in u_state.  Dropout that stays on: the launch-per-layer masks (pdrop).
-            if not single and (c.transition_agent or (c.apply_dropout_on_inference and c.dec_prenet_drop > 0)):
+            # Forced alignments: no agent fields, no agent_tab / u_state (an agent model without dropout runs without an option block).
+            use_agent = c.transition_agent and not forced
+            if not single and (use_agent or live_drop):
                 agent = {}
-                if c.transition_agent:
+                if use_agent:
                     self.agent_tab, self.u_state = Z(Ba * Ti, 1), Z(Ba)
                     agent = dict(agentW=P["dec.att1.Wa"], agentb=P["dec.att1.ba"], agent_tab=self.agent_tab, u_state=self.u_state)
                 drop = ops.Drop(c.dec_prenet_drop, 0, self.drop_seed) if c.apply_dropout_on_inference else None
@@ -273,6 +280,9 @@ class DecodeSession:
                 self.mega_opt = None
             else:
                 self.mega = mega
+                if forced:      # the teacher rows of the utterance (infer() rewrites them in place; zeros for the warm-up launch below)
+                    self.mega_forced = ops.dec_mega_forced_params(self.teach1, self.teach2)
+                    assert ops.dec_mega_forced_variant(mega, self.mega_opt, self.mega_forced) & ops.MEGA_VAR_FORCED
             self.kernel_launches = 1          # per K steps
         self.refresh_folded()
         if self.mega is not None or self.mega_groups is not None:
@@ -430,6 +440,8 @@ class DecodeSession:
     # steps per group launch: no group can evaluate the stop rule, so a launch runs all its steps, the stop scan runs behind it and the
     # host reads the flag once per launch - the overshoot past the stop token is bounded by the launch length
     MEGA_GROUPS_STEPS = 32
+    # forced-alignment sessions (B <= MEGA_MAX_B) on the kernel's forced instantiations; False / SATT_DECODE_MEGA_FORCED=0: the hipGraph path
+    MEGA_FORCED = __import__("os").environ.get("SATT_DECODE_MEGA_FORCED", "1") != "0"
     MEGA_FOLD_FEEDBACK = __import__("os").environ.get("SATT_DECODE_FOLD_FEEDBACK", "1") != "0"     # projection -> pre-net 0 folded (csrc/decode_mega2.hip)
     FUSE = True         # chain short Dense launches into their consumers (csrc/decode.hip dec_chain_k); tests switch it off
     MAX_CHAIN = 1       # layers chained in front of a consumer (the kernel takes up to 2)
@@ -496,7 +508,7 @@ class DecodeSession:
         for q, (W, r0, n, x) in enumerate(rows):
             self._ctw[q].copy_(W[r0:r0 + n])
             ops.gemm(x.shape[0], 4 * D, n, x, n, self._ctw[q], 4 * D, 1, self.ctab[:, q * 4 * D:], len(rows) * 4 * D, prec=ops.PREC_F32)
-        if c.transition_agent and not self._mega_single:      # agent_tab[b][r] = values1[b, r] . Wa[:V1] (fp32 parameters, as the launch-per-layer step multiplies)
+        if self.agent_tab is not None:      # agent_tab[b][r] = values1[b, r] . Wa[:V1] (fp32 parameters, as the launch-per-layer step multiplies)
             ops.gemm(values1.shape[0], 1, V1, values1, V1, self.eng.P["dec.att1.Wa"], 1, 1, self.agent_tab, 1, prec=ops.PREC_F32)
 
     def run_step(self):
@@ -516,7 +528,9 @@ class DecodeSession:
             self._t0 += n
         elif self.mega is not None:
             n = self.K if nsteps is None else max(1, min(self.K, int(nsteps)))
-            if self.mega_opt is not None:
+            if self.mega_forced is not None:
+                ops.dec_mega_forced(self.mega, self.mega_opt, self.mega_forced, n)
+            elif self.mega_opt is not None:
                 ops.dec_mega_opt(self.mega, self.mega_opt, n)
             else:
                 ops.dec_mega(self.mega, n)
@@ -610,7 +624,7 @@ def infer(eng, source, source_length, max_steps=None, teacher=None, speaker_id=N
     key = (B, Ti, Td, teacher is not None, forced, int(min_steps), float(stop_threshold), int(check_every), bool(use_graph),
            ops.get_precision(), DecodeSession.FUSE, DecodeSession.MAX_CHAIN, DecodeSession.MEGA, DecodeSession.MEGA_MAX_B,
            DecodeSession.MEGA_STEPS, DecodeSession.MEGA_FOLD_FEEDBACK, DecodeSession.MEGA_GROUPS, DecodeSession.MEGA_GROUPS_MAX_B,
-           DecodeSession.MEGA_GROUPS_STEPS)
+           DecodeSession.MEGA_GROUPS_STEPS, DecodeSession.MEGA_FORCED)
     cache = eng.__dict__.setdefault("_decode_sessions", {})
     ses = cache.get(key)
     if ses is None:         # (the kernels read the parameters in place: an optimiser step does not invalidate a session)

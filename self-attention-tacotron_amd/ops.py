@@ -1197,6 +1197,30 @@ def dec_mega_opt(p, opt, nsteps):
     _lib.check(_lib.lib().satt_dec_mega_opt(C.byref(p), None if opt is None else C.byref(opt), _s()), "dec_mega_opt")
 
 
+MEGA_VAR_FORCED = 256                          # forced alignments (satt_dec_mega_forced): the generic-width instantiations only
+
+
+def dec_mega_forced_params(teach1, teach2=None):
+    """teacher alignments of a forced launch (satt_dec_mega_forced_params): [B][Td][Ti] fp32 with the Td of the main block; teach2
+    None in the single-source form"""
+    f = _lib.DecMegaForcedParams()
+    ptr = lambda v: v.data_ptr() if isinstance(v, torch.Tensor) else v
+    f.teach1, f.teach2 = ptr(teach1), ptr(teach2)
+    return f
+
+
+def dec_mega_forced_variant(p, opt, f):
+    """dec_mega_opt_variant of a launch with the teacher alignments `f` (None: without): plus MEGA_VAR_FORCED, without MEGA_VAR_LJ"""
+    return int(_lib.lib().satt_dec_mega_forced_variant(C.byref(p), None if opt is None else C.byref(opt), None if f is None else C.byref(f)))
+
+
+def dec_mega_forced(p, opt, f, nsteps):
+    """dec_mega_opt with forced alignments: the mechanisms are bypassed, row t of `f` is the alignment of step t"""
+    p.nsteps = int(nsteps)
+    _lib.check(_lib.lib().satt_dec_mega_forced(C.byref(p), None if opt is None else C.byref(opt), None if f is None else C.byref(f), _s()),
+               "dec_mega_forced")
+
+
 MEGA_VAR_GROUPS = 128                          # group mode: one pair of samples per XCD (satt_dec_mega_groups)
 MEGA_GROUPS_MAX = 8
 

@@ -5,7 +5,9 @@
 use_forward_attention_transition_agent=True or apply_dropout_on_inference=True.
 --batch 3 .. 16 takes the persistent kernel in group mode (one pair of samples per XCD); --no-groups: the hipGraph of launch-per-layer
 steps such batches ran on before.
-usage: python tools/bench_infer.py [--steps 200] [--batch 1] [--no-groups] [--hparams-json FILE] [--hparams "k=v,..."] [--repeat N]"""
+--forced: forced-alignment synthesis (infer(..., teacher_alignments=...), the second pass of predict_mel.py's
+use_forced_alignment_mode): one free-running utterance produces the alignments, the timed utterances replay them.
+usage: python tools/bench_infer.py [--steps 200] [--batch 1] [--no-groups] [--forced] [--hparams-json FILE] [--hparams "k=v,..."] [--repeat N]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -24,6 +26,7 @@ ap.add_argument("--steps-per-graph", type=int, default=8)
 ap.add_argument("--no-graph", action="store_true")
 ap.add_argument("--mega-max-b", type=int, default=None, help="largest batch that takes the persistent step kernel (default: the session's)")
 ap.add_argument("--no-groups", action="store_true", help="DecodeSession.MEGA_GROUPS = False: batches of 3 .. 16 on the launch-per-layer path")
+ap.add_argument("--forced", action="store_true", help="time forced-alignment utterances fed the alignments of one free-running utterance")
 ap.add_argument("--hparams-json", default=None, help="hparams file of the model (default: the LJSpeech dimensions)")
 ap.add_argument("--hparams", default=None, help='comma-separated name=value overrides of the model\'s hparams')
 ap.add_argument("--repeat", type=int, default=1, help="timed utterances (one JSON line each)")
@@ -54,6 +57,9 @@ sl = np.full((B,), Ti, dtype=np.int64)
 ap_kw = dict(max_steps=a.steps, min_steps=10 ** 6, check_every=a.steps_per_graph, use_graph=not a.no_graph)
 if cfg.num_speakers > 0:
     ap_kw["speaker_id"] = (np.arange(B) % cfg.num_speakers + cfg.speaker_offset).astype(np.int64)
+if a.forced:                            # the alignments of one free-running utterance; the forced session is built by the warm-up below
+    free = infer(eng, src, sl, **ap_kw)
+    ap_kw["teacher_alignments"] = (free["alignment1"], free["alignment2"])
 infer(eng, src, sl, **ap_kw)            # warm-up: builds the session of this shape (buffers + captured hipGraph)
 torch.cuda.synchronize()
 for _ in range(a.repeat):
@@ -64,10 +70,10 @@ for _ in range(a.repeat):
     dt = out["decode_ms"] * 1e-3            # the decoder steps alone (HIP events around the replay loop)
     al = out["alignment1"]
     ses = eng._decode_sessions[next(reversed(eng._decode_sessions))]
-    path = "persistent" if getattr(ses, "mega", None) is not None else \
+    path = "persistent, forced" if getattr(ses, "mega_forced", None) is not None else "persistent" if getattr(ses, "mega", None) is not None else \
         ("persistent, groups" if getattr(ses, "mega_groups", None) is not None else "launch-per-layer")
     frames = a.steps * cfg.r * B
-    print(json.dumps({"metric": "free-running decode (config 5)", "model": (a.hparams_json or "ljspeech") + (" + " + a.hparams if a.hparams else ""), "path": path, "batch": B, "Ti": Ti, "decoder_steps": out["steps"],
+    print(json.dumps({"metric": "forced-alignment decode" if a.forced else "free-running decode (config 5)", "model": (a.hparams_json or "ljspeech") + (" + " + a.hparams if a.hparams else ""), "path": path, "batch": B, "Ti": Ti, "decoder_steps": out["steps"],
                       "ms_per_step": 1e3 * dt / a.steps, "utterance_ms_incl_encoder": 1e3 * dt_all,
                       "steps_per_graph": a.steps_per_graph, "graph": not a.no_graph,
                       "mel_frames_per_sec": frames / dt,

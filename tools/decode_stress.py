@@ -1,6 +1,9 @@
 #!/usr/bin/env python
 """Repeat the free-running decode of the frozen b1 / b2 fixtures N times in one process and count runs whose mel differs from the
-first run (the persistent step kernel is deterministic: every run must be bit-identical).  python tools/decode_stress.py [N] [case]"""
+first run (the persistent step kernel is deterministic: every run must be bit-identical).  python tools/decode_stress.py [N] [case]
+A fourth argument `forced` (after `fresh` or `-`): one free-running utterance first, then every run is a forced-alignment utterance
+fed that utterance's alignments (the forced instantiations of the kernel), compared with the first forced run; the session's sticky
+error word and the distance from the free-running utterance are printed.  Meant for the jitter build (tools/build_variant.sh jitter decode_mega2.hip -DSATT_MEGA_JITTER)."""
 import os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -14,6 +17,7 @@ from satt_amd.inference import infer
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 case = sys.argv[2] if len(sys.argv) > 2 else "b1"
 fresh = len(sys.argv) > 3 and sys.argv[3] == "fresh"       # a new engine + session per run (every utterance is a session's first)
+forced = len(sys.argv) > 4 and sys.argv[4] == "forced"
 z = np.load(os.path.join(ROOT, "tests", "golden", "decode_ljspeech_%s.npz" % case))
 cfg = ModelConfig(); P = dict(init_params(cfg, int(z["param_seed"])))
 ops.set_precision("bf16")
@@ -29,12 +33,16 @@ def make():
 eng = make()
 steps = int(z["steps"])
 ref, bad, worst = None, 0, 0.0
+kw = {}
+if forced:
+    free = infer(eng, z["source"], z["source_length"], max_steps=steps, min_steps=10 ** 6, use_graph=True)
+    kw["teacher_alignments"] = (free["alignment1"], free["alignment2"])
 import time
 _t0, _ms = time.time(), []
 for i in range(N):
     if fresh and i:
         eng = make()
-    out = infer(eng, z["source"], z["source_length"], max_steps=steps, min_steps=10 ** 6, use_graph=True)
+    out = infer(eng, z["source"], z["source_length"], max_steps=steps, min_steps=10 ** 6, use_graph=True, **kw)
     mel = out["mel"].float().cpu().numpy()
     _ms.append(out["decode_ms"])
     if ref is None:
@@ -46,4 +54,8 @@ for i in range(N):
             bad += 1; worst = max(worst, d)
             t = np.abs(mel - ref).reshape(steps, -1).max(-1)
             print("run %d differs: max %.3e, first differing step %d" % (i, d, int(np.argmax(t > 0))))
+if forced:
+    ses = eng._decode_sessions[next(reversed(eng._decode_sessions))]
+    assert ses.mega_forced is not None, "the forced session did not take the persistent kernel"
+    print("forced: error word %d, |mel - free run| max %.3e" % (int(ses._mega_err.item()), float(np.abs(ref - free["mel"].float().cpu().numpy()).max())))
 print("%s: %d runs, %d differ from run 0 (worst %.3e)%s; decode %.1f ms per utterance (median), %.0f s in all" % (case, N, bad, worst, " [fresh session per run]" if fresh else "", sorted(_ms)[len(_ms) // 2], time.time() - _t0))
