@@ -853,7 +853,7 @@ int satt_dec_mega_opt_variant(const satt_dec_mega_params* p, const satt_dec_mega
  *  - the dual form needs teach2 (NULL: SATT_E_BADARG, variant -1); the single-source form never reads it;
  *  - the transition agent switched on in `opt` together with f: SATT_E_UNSUPPORTED, variant -1 (the agent never runs under
  *    forced alignments: the caller leaves its fields NULL); the single-source form takes no options, as ever;
- *  - there is no forced group launch. */
+ *  - batches of 3 .. 16 under forced alignments: satt_dec_mega_groups_forced below (group mode with ONE forced block). */
 typedef struct { const float *teach1, *teach2; } satt_dec_mega_forced_params;   /* [B][Td][Ti]; teach2 NULL in the single form */
 #define SATT_MEGA_VAR_FORCED 256     /* forced alignments (satt_dec_mega_forced with f->teach1 != NULL) */
 int satt_dec_mega_forced(const satt_dec_mega_params* p, const satt_dec_mega_opt_params* opt_or_null,
@@ -894,6 +894,19 @@ int satt_dec_mega_groups_variant(const satt_dec_mega_group* host_blocks, int ngr
 /* ngroups x satt_dec_mega_scratch_floats(2, heads, head_dim): group g's `part` may be slice g of one buffer of this size */
 int64_t satt_dec_mega_groups_scratch_floats(int ngroups, int heads, int head_dim);
 int satt_dec_mega_groups(const satt_dec_mega_group* host_blocks, const void* device_blocks, int ngroups, void* stream);
+/* ---- forced alignments in group mode: SATT_MEGA_VAR_FORCED | SATT_MEGA_VAR_GROUPS.  The blocks are those of satt_dec_mega_groups
+ * and ONE forced block serves the whole launch: teach1 / teach2 are the BATCH's histories [2 ngroups][Td][Ti] (the padding sample
+ * of an odd batch has rows of its own), and group g reads batch rows b0 and b0 + 1 of them.  Each group runs the statements of
+ * the B = 2 launch of satt_dec_mega_forced on its pair; nothing crosses groups and no group evaluates the stop rule.
+ *  - f == NULL or f->teach1 == NULL: the call IS satt_dec_mega_groups / satt_dec_mega_groups_variant;
+ *  - otherwise the variant is (that of satt_dec_mega_groups_variant & ~SATT_MEGA_VAR_LJ) | SATT_MEGA_VAR_FORCED;
+ *  - the transition agent switched on in the blocks: SATT_E_UNSUPPORTED, variant -1;
+ *  - the dual form without teach2: SATT_E_BADARG, variant -1; the single-source form never reads it;
+ *  - everything satt_dec_mega_groups checks is checked (p.flag == NULL, part / step / state of their own per group, blocks that
+ *    agree), and every refusal returns before anything is launched. */
+int satt_dec_mega_groups_forced_variant(const satt_dec_mega_group* host_blocks, int ngroups, const satt_dec_mega_forced_params* f);
+int satt_dec_mega_groups_forced(const satt_dec_mega_group* host_blocks, const void* device_blocks, int ngroups,
+                                const satt_dec_mega_forced_params* f, void* stream);
 /* stop rule of a batch behind a launch that evaluated none: scans the output rows of steps t0 .. t0 + nsteps - 1 (row t + 1 of
  * yout [B][rows][NO] is step t's; t0 + nsteps < rows) for the first step t > min_steps at which EVERY one of the B samples has
  * 1 / (1 + exp(-stop logit)) > stop_threshold - the persistent kernel's own expression - and writes *flag = t + 1.  A *flag

@@ -3,14 +3,15 @@
 
 Usage: predict_mel.py --source-data-root=<dir> --target-data-root=<dir> --checkpoint-dir=<dir> --output-dir=<dir>
                       --selected-list-dir=<dir> [--checkpoint=<file>] [--selected-list-filename=<name>]
-                      [--hparams=<a=b>] [--hparam-json-file=<path>]
+                      [--hparams=<a=b>] [--hparam-json-file=<path>] [--batch-size=<N>]
 
 For every key of the list: free-running decode (batch size 1) from `model-<step>.pt`, output `<key>.mfbsp` (raw
 little-endian float32 [T, num_mels]; the PostNetV2 output when `use_postnet_v2`, models/models.py:440-462), `<key>.alignment.npz` + `<key>.png` (the
 two alignment histories laid out [T_memory, T_query] as in the reference's predictions) and `<key>.tfrecord` (the
 reference's prediction record, utils/tfrecord.py:135-152).  `use_forced_alignment_mode=True` (models/models.py:387-428):
 pass 1 is the validation decode fed with the GROUND-TRUTH mel (needs --target-data-root), pass 2 feeds its own outputs
-back while both attention mechanisms return pass 1's alignments.
+back while both attention mechanisms return pass 1's alignments.  `--batch-size N` (forced-alignment mode only) decodes N
+utterances per pass.
 Usage: see --help"""
 import argparse
 import glob
@@ -31,7 +32,14 @@ def main(argv=None):
     ap.add_argument("--selected-list-filename", default="test.csv")
     ap.add_argument("--hparams", default="")
     ap.add_argument("--hparam-json-file", default=None)
+    ap.add_argument("--batch-size", type=int, default=1, metavar="N",
+                    help="utterances per decode, 1 .. 16 (default 1, the reference's).  N > 1 needs use_forced_alignment_mode=True: both "
+                         "passes then decode N utterances at once and every prediction is cut to its own utterance's lengths.  The "
+                         "values are those of the model AT THAT BATCH: the padding symbols of the shorter utterances reach the "
+                         "encoder's convolutions exactly as in training, so they are not bit-equal to a batch-size-1 run")
     a = ap.parse_args(argv)
+    if not 1 <= a.batch_size <= 16:
+        raise SystemExit("--batch-size: 1 .. 16")
 
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import satt_amd  # noqa: F401
@@ -47,6 +55,10 @@ def main(argv=None):
     hparams.parse(a.hparams)
     if hparams.use_forced_alignment_mode and not a.target_data_root:
         raise SystemExit("use_forced_alignment_mode aligns to the reference audio: --target-data-root is required")
+    if a.batch_size > 1 and not hparams.use_forced_alignment_mode:
+        # (the reference's stop rule of a batch fires only when EVERY sample is above the threshold at the same step; where to cut
+        #  each sample of a free-running batch is a decision this driver does not take)
+        raise SystemExit("--batch-size > 1 needs use_forced_alignment_mode=True: a free-running batch has no per-utterance end")
     # reference predict_mel.py:40-57: estimator = tacotron_model_factory(hparams, checkpoint_dir, run_config);
     # estimator.predict(input_fn, checkpoint_path=...)
     model = tacotron_model_factory(hparams, None, device="cuda")
@@ -62,8 +74,8 @@ def main(argv=None):
     def input_fn():
         if have_target:
             tgt = [os.path.join(a.target_data_root, "%s.%s" % (k, hparams.target_file_extension)) for k in keys]
-            # batch size 1, targets merged into the source side (reference predict_mel.py:46-50)
-            return dataset_factory(src, tgt, hparams).prepare_and_zip().group_by_batch(batch_size=1) \
+            # batch size 1 unless --batch-size, targets merged into the source side (reference predict_mel.py:46-50)
+            return dataset_factory(src, tgt, hparams).prepare_and_zip().group_by_batch(batch_size=a.batch_size) \
                 .merge_target_to_source()
         from satt_amd.datasets.ljspeech import decode_source_record, resolve_accent_types
 

@@ -47,6 +47,10 @@
 // behind P's gather of tr(t) (dual) / dout(t) (single): full, and behind every workgroup's gather of p0(t).  The teacher rows are
 // read-only global memory: no granule, no tag, nothing to overwrite.  tools/decode_stress.py's forced case under the jitter build
 // is the timing-independence evidence (profiles/decode_forced_bench_and_kernel_times.txt).
+// FORCED GROUPS (GRP and FRC together; satt_dec_mega_groups_forced): a group is the B = 2 forced launch of its pair.  The forced block
+// is ONE for the batch - teach1 / teach2 [Ba][Td][Ti], a kernel argument beside the block array - and the group adds its b0 to the
+// row index (64-bit), as it does for the dropout mask row.  Nothing else differs and nothing crosses groups; the granule argument
+// above is per group.  No group evaluates the stop rule (p.flag == NULL).
 // WHAT THE TWO KERNELS SHARE: the leaf helpers (split_mul / split_mul_fb / split_fill, gather_vec, slice_*, pin, lstm_unit,
 // mega_drop) and, on the host, one pointer list, one `spread` static and one launch function (mega_launch) behind both dispatch
 // ladders.  EVERY PHASE THEY HAVE IN COMMON IS WRITTEN OUT IN BOTH KERNELS, and a fix to one copy has to be made in the other: the
@@ -425,7 +429,7 @@ template <> struct MegaFrcT<true> { typedef satt_dec_mega_forced_params type; };
 template <int NB, bool TRES, bool LJ, bool SPK, bool OPT, bool GRP = false, bool FRC = false>
 __global__ __launch_bounds__(M2T) void dec_mega2_k(typename MegaArgT<GRP>::type p, const int spread, typename MegaOptArgT<OPT, GRP>::type o,
                                                    const typename MegaFrcT<FRC>::type f) {
-  static_assert(!(FRC && (GRP || LJ)), "forced alignments: the generic-width instantiations of a single launch");
+  static_assert(!(FRC && LJ), "forced alignments: the generic-width instantiations, of a single launch or of a group launch");
   // r6: ONE XCD.  Workgroups are dealt to the 8 XCDs round robin in launch order, so with spread = 8 the grid is 8 x 32 and only the
   // workgroups with blockIdx % 8 == 0 stay: all 32 on the same XCD (32 CUs: one each).  Every weight is register resident, so the one
   // L2 only has to carry the exchanges - and granules published with PLAIN stores stay in that L2, where the peers' polling loads find
@@ -641,7 +645,10 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(typename MegaArgT<GRP>::type 
   if constexpr (FRC) {
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
     if (w < 2 * B) {
-      const float* row = ((w & 1) ? f.teach2 : f.teach1) + ((int64_t)(w >> 1) * p.Td + min(t, p.Td - 1)) * Ti;
+      // (GRP: the teacher histories are the BATCH's, [Ba][Td][Ti] - one forced block for every group; the group's rows begin at b0)
+      const float* row;
+      if constexpr (GRP) row = ((w & 1) ? f.teach2 : f.teach1) + ((int64_t)(gb->b0 + (w >> 1)) * p.Td + min(t, p.Td - 1)) * Ti;
+      else row = ((w & 1) ? f.teach2 : f.teach1) + ((int64_t)(w >> 1) * p.Td + min(t, p.Td - 1)) * Ti;
 #pragma unroll
       for (int q = 0; q < 4; ++q) trow[q] = row[min(l + 64 * q, Ti - 1)];
     }
@@ -939,7 +946,10 @@ __global__ __launch_bounds__(M2T) void dec_mega2_k(typename MegaArgT<GRP>::type 
           eg[i] = v; em[i] = i < len ? v : 0.f;
         }
         // row t + 1, a step ahead (the last row again behind the last step: in bounds, not used)
-        const float* row = (mech ? kq->f.teach2 : kq->f.teach1) + ((int64_t)b * p.Td + min(t + 1, p.Td - 1)) * Ti;
+        // (GRP: the forced block is a kernel argument, not part of the group's block; batch row b0 + b)
+        const float* row;
+        if constexpr (GRP) row = (mech ? f.teach2 : f.teach1) + ((int64_t)(gb->b0 + b) * p.Td + min(t + 1, p.Td - 1)) * Ti;
+        else row = (mech ? kq->f.teach2 : kq->f.teach1) + ((int64_t)b * p.Td + min(t + 1, p.Td - 1)) * Ti;
 #pragma unroll
         for (int q = 0; q < 4; ++q) trow[q] = row[min(lane + 64 * q, Ti - 1)];
       }
@@ -1435,7 +1445,6 @@ __host__ __device__ inline size_t mega2s_lds_bytes(int NB, int Ti) {
 
 template <int NB, bool TRES, bool SPK, bool GRP = false, bool FRC = false>
 __global__ __launch_bounds__(M2T) void dec_mega2_single_k(typename MegaArgT<GRP>::type p, const int spread, const typename MegaFrcT<FRC>::type f) {
-  static_assert(!(FRC && GRP), "forced alignments: a single launch");
   [[maybe_unused]] int gm = 1;
   [[maybe_unused]] MegaGrpC* gb = nullptr;
   if constexpr (GRP) {      // group mode: see dec_mega2_k
@@ -1579,7 +1588,9 @@ __global__ __launch_bounds__(M2T) void dec_mega2_single_k(typename MegaArgT<GRP>
   if constexpr (FRC) {
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
     if (w < B) {
-      const float* row = f.teach1 + ((int64_t)w * p.Td + min(t, p.Td - 1)) * Ti;
+      const float* row;      // (GRP: batch row b0 + w of the batch's teacher history - dec_mega2_k)
+      if constexpr (GRP) row = f.teach1 + ((int64_t)(gb->b0 + w) * p.Td + min(t, p.Td - 1)) * Ti;
+      else row = f.teach1 + ((int64_t)w * p.Td + min(t, p.Td - 1)) * Ti;
 #pragma unroll
       for (int q = 0; q < 4; ++q) trow[q] = row[min(l + 64 * q, Ti - 1)];
     }
@@ -1810,7 +1821,9 @@ __global__ __launch_bounds__(M2T) void dec_mega2_single_k(typename MegaArgT<GRP>
           const float v = i < Ti ? trow[q] : 0.f;
           eg[i] = v; em[i] = i < len ? v : 0.f;
         }
-        const float* row = kq->f.teach1 + ((int64_t)b * p.Td + min(t + 1, p.Td - 1)) * Ti;
+        const float* row;      // (GRP: dec_mega2_k)
+        if constexpr (GRP) row = f.teach1 + ((int64_t)(gb->b0 + b) * p.Td + min(t + 1, p.Td - 1)) * Ti;
+        else row = kq->f.teach1 + ((int64_t)b * p.Td + min(t + 1, p.Td - 1)) * Ti;
 #pragma unroll
         for (int q = 0; q < 4; ++q) trow[q] = row[min(lane + 64 * q, Ti - 1)];
       }
@@ -2124,7 +2137,8 @@ extern "C" int satt_dec_mega_opt(const satt_dec_mega_params* pp, const satt_dec_
 extern "C" int satt_dec_mega(const satt_dec_mega_params* pp, void* stream) { return satt_dec_mega_opt(pp, nullptr, stream); }
 
 // ---- forced alignments (include/satt_hip.h: satt_dec_mega_forced_params; template flag FRC of both kernels).  Without teacher rows
-// the entry points ARE the ones above.  The forced instantiations are siblings of the generic-width ones only (18: 12 dual, 6 single).
+// the entry points ARE the ones above.  The forced instantiations are siblings of the generic-width ones only (18: 12 dual, 6 single;
+// six more in group mode, behind satt_dec_mega_groups below).
 namespace {
 inline bool frc_on(const satt_dec_mega_forced_params* f) { return f && f->teach1; }
 }  // namespace
@@ -2200,9 +2214,9 @@ extern "C" int satt_dec_mega_groups_variant(const satt_dec_mega_group* hb, int n
 
 extern "C" int satt_dec_mega_groups_supported(const satt_dec_mega_group* hb, int ngroups) { return satt_dec_mega_groups_variant(hb, ngroups) >= 0; }
 
-extern "C" int satt_dec_mega_groups(const satt_dec_mega_group* hb, const void* device_blocks, int ngroups, void* stream) {
-  const int var = satt_dec_mega_groups_variant(hb, ngroups);
-  if (var < 0) return SATT_E_UNSUPPORTED;
+namespace {
+// what every group launch checks behind its variant: the device copy, every block's pointers, no stop rule, nothing shared
+int mega_check_groups(const satt_dec_mega_group* hb, const void* device_blocks, int ngroups) {
   if (!device_blocks) return SATT_E_BADARG;
   for (int g = 0; g < ngroups; ++g) {
     if (const int rc = mega_check_block(hb[g].p, group_opt(hb[g]))) return rc;
@@ -2210,6 +2224,14 @@ extern "C" int satt_dec_mega_groups(const satt_dec_mega_group* hb, const void* d
     for (int h = 0; h < g; ++h)                      // exchanges, step words and state belong to ONE group
       if (hb[h].p.part == hb[g].p.part || hb[h].p.step == hb[g].p.step || hb[h].p.ha == hb[g].p.ha) return SATT_E_BADARG;
   }
+  return SATT_OK;
+}
+}  // namespace
+
+extern "C" int satt_dec_mega_groups(const satt_dec_mega_group* hb, const void* device_blocks, int ngroups, void* stream) {
+  const int var = satt_dec_mega_groups_variant(hb, ngroups);
+  if (var < 0) return SATT_E_UNSUPPORTED;
+  if (const int rc = mega_check_groups(hb, device_blocks, ngroups)) return rc;
   const satt_dec_mega_params& p = hb[0].p;
   const bool single = var & SATT_MEGA_VAR_SINGLE, lj = var & SATT_MEGA_VAR_LJ, spk = var & SATT_MEGA_VAR_SPEAKER;
   const bool has_opt = var & (SATT_MEGA_VAR_AGENT | SATT_MEGA_VAR_DROPOUT);
@@ -2228,6 +2250,43 @@ extern "C" int satt_dec_mega_groups(const satt_dec_mega_group* hb, const void* d
   return spk ? SATT_MEGA2GL(true) : SATT_MEGA2GL(false);
 #undef SATT_MEGA2GO
 #undef SATT_MEGA2GL
+}
+
+// ---- forced alignments in group mode (GRP and FRC together: six instantiations, siblings of the generic-width group ones).  ONE
+// forced block for the whole launch: teach1 / teach2 are the batch's histories [2 ngroups][Td][Ti], group g reads rows b0, b0 + 1.
+extern "C" int satt_dec_mega_groups_forced_variant(const satt_dec_mega_group* hb, int ngroups, const satt_dec_mega_forced_params* f) {
+  const int var = satt_dec_mega_groups_variant(hb, ngroups);
+  if (!frc_on(f) || var < 0) return var;
+  if (var & SATT_MEGA_VAR_AGENT) return -1;          // the agent never runs under forced alignments (the blocks agree: one is all)
+  if (!(var & SATT_MEGA_VAR_SINGLE) && !f->teach2) return -1;
+  return (var & ~SATT_MEGA_VAR_LJ) | SATT_MEGA_VAR_FORCED;
+}
+
+extern "C" int satt_dec_mega_groups_forced(const satt_dec_mega_group* hb, const void* device_blocks, int ngroups,
+                                           const satt_dec_mega_forced_params* f, void* stream) {
+  if (!frc_on(f)) return satt_dec_mega_groups(hb, device_blocks, ngroups, stream);
+  const int gvar = satt_dec_mega_groups_variant(hb, ngroups);
+  if (gvar < 0 || (gvar & SATT_MEGA_VAR_AGENT)) return SATT_E_UNSUPPORTED;
+  const bool single = gvar & SATT_MEGA_VAR_SINGLE;
+  if (!single && !f->teach2) return SATT_E_BADARG;
+  if (const int rc = mega_check_groups(hb, device_blocks, ngroups)) return rc;
+  const int var = satt_dec_mega_groups_forced_variant(hb, ngroups, f);
+  if (var < 0) return SATT_E_UNSUPPORTED;
+  const satt_dec_mega_params& p = hb[0].p;
+  const bool spk = var & SATT_MEGA_VAR_SPEAKER, has_opt = var & SATT_MEGA_VAR_DROPOUT;
+  const size_t smem = single ? mega2s_lds_bytes(2, p.Ti) : mega2_lds_bytes(2, p.Ti, has_opt);
+  if (smem > 160 * 1024) return SATT_E_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  MegaGrpP ga;                                       // (the block part is a place holder, as in satt_dec_mega_groups)
+  static_cast<satt_dec_mega_params&>(ga) = p;
+  ga.blocks = (const satt_dec_mega_group*)device_blocks; ga.ngroups = ngroups;
+#define SATT_MEGA2GFO(SP) \
+  (has_opt ? mega_launch(dec_mega2_k<2, false, false, SP, true, true, true>, smem, s, ga, hb[0].o, *f) : \
+             mega_launch(dec_mega2_k<2, false, false, SP, false, true, true>, smem, s, ga, MegaNoOpt(), *f))
+  if (single)
+    return spk ? mega_launch(dec_mega2_single_k<2, false, true, true, true>, smem, s, ga, *f) : mega_launch(dec_mega2_single_k<2, false, false, true, true>, smem, s, ga, *f);
+  return spk ? SATT_MEGA2GFO(true) : SATT_MEGA2GFO(false);
+#undef SATT_MEGA2GFO
 }
 
 extern "C" int satt_dec_stop_scan(const float* yout, int B, int rows, int NO, int t0, int nsteps, int min_steps, float stop_threshold,

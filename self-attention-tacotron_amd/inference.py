@@ -79,8 +79,10 @@ class DecodeSession:
         # Batches of 3 .. MEGA_GROUPS_MAX_B: the same kernel in GROUP mode - one pair of samples per XCD, ceil(B / 2) independent
         # B = 2 problems in one launch (csrc/decode_mega2.hip, include/satt_hip.h: satt_dec_mega_group).  Decided by the library on
         # the B = 2 block of the model.  An odd batch is padded with a copy of its last sample (`Ba` rows are allocated, B returned).
+        # A forced batch takes it too (satt_dec_mega_groups_forced: every group is the forced B = 2 launch of its pair), for the models
+        # the forced B <= 2 session takes, unless MEGA_FORCED is off.
         self._groups = 0
-        if (self.MEGA and self.MEGA_GROUPS and use_graph and not forced and (dual_form or single_form) and len(c.dec_prenet) == 2 and
+        if (self.MEGA and self.MEGA_GROUPS and use_graph and (not forced or mega_forced) and (dual_form or single_form) and len(c.dec_prenet) == 2 and
                 ops.get_precision() == "bf16" and 2 < B <= min(self.MEGA_GROUPS_MAX_B, 2 * ops.MEGA_GROUPS_MAX)):
             sh2 = dict(Ds=Ds, heads=c.dec_sa_heads, U2=U2, V2=V2) if dual_form else dict(Ds=0, heads=0, U2=0, V2=0)
             shape = dict(B=2, Td=Td, Ti=Ti, A=A, D=D, U1=U1, V1=V1, **sh2, kernel=c.att_kernel,
@@ -115,8 +117,8 @@ class DecodeSession:
         self.a_state, self.alpha_state = Z(2, B, Ti), Z(2, B, Ti)      # double-buffered by step parity
         self.e1, self.e2 = Z(B, Ti), Z(B, Ti)
         self.al1, self.al2 = ZB(1, Tdp, Ti), (ZB(1, Tdp, Ti) if c.dual else None)
-        self.teach1 = Z(B, Tdp, Ti) if forced else None
-        self.teach2 = Z(B, Tdp, Ti) if (forced and c.dual) else None
+        self.teach1 = ZB(1, Tdp, Ti) if forced else None
+        self.teach2 = ZB(1, Tdp, Ti) if (forced and c.dual) else None
         # c, h of the three cells, double-buffered by step parity (csrc/decode.hip: read [t & 1], write [(t & 1) ^ 1])
         self.states = [Z(2, B, A), Z(2, B, A), Z(2, B, D), Z(2, B, D), Z(2, B, D), Z(2, B, D)]
         ca, ha, c1, h1, c2, h2 = self.states
@@ -278,6 +280,10 @@ class DecodeSession:
             if self._groups:
                 self._group_blocks_init(mega, self.mega_opt)
                 self.mega_opt = None
+                if forced:      # ONE forced block for the launch: the teacher rows of all Ba samples (group g reads rows 2 g, 2 g + 1)
+                    self.mega_forced = ops.dec_mega_forced_params(self.teach1, self.teach2)
+                    var = ops.dec_mega_groups_forced_variant(self.mega_groups, self.mega_forced)
+                    assert var >= 0 and var & ops.MEGA_VAR_FORCED and var & ops.MEGA_VAR_GROUPS
             else:
                 self.mega = mega
                 if forced:      # the teacher rows of the utterance (infer() rewrites them in place; zeros for the warm-up launch below)
@@ -440,7 +446,8 @@ class DecodeSession:
     # steps per group launch: no group can evaluate the stop rule, so a launch runs all its steps, the stop scan runs behind it and the
     # host reads the flag once per launch - the overshoot past the stop token is bounded by the launch length
     MEGA_GROUPS_STEPS = 32
-    # forced-alignment sessions (B <= MEGA_MAX_B) on the kernel's forced instantiations; False / SATT_DECODE_MEGA_FORCED=0: the hipGraph path
+    # forced-alignment sessions (B <= MEGA_MAX_B, and in group mode up to MEGA_GROUPS_MAX_B) on the kernel's forced instantiations;
+    # False / SATT_DECODE_MEGA_FORCED=0: the hipGraph path
     MEGA_FORCED = __import__("os").environ.get("SATT_DECODE_MEGA_FORCED", "1") != "0"
     MEGA_FOLD_FEEDBACK = __import__("os").environ.get("SATT_DECODE_FOLD_FEEDBACK", "1") != "0"     # projection -> pre-net 0 folded (csrc/decode_mega2.hip)
     FUSE = True         # chain short Dense launches into their consumers (csrc/decode.hip dec_chain_k); tests switch it off
@@ -493,7 +500,7 @@ class DecodeSession:
         c = self.eng.cfg
         full = lambda t: t if t._base is None else t._base      # all Ba allocated samples (group mode; otherwise the tensor itself)
         if self.mega_groups is not None and self.B % 2:      # the padding sample of an odd batch: a copy of the last one's inputs
-            for t in (self.lengths, self.values1, self.keys1, self.values2, self.keys2, self.sproj, self.tin):
+            for t in (self.lengths, self.values1, self.keys1, self.values2, self.keys2, self.sproj, self.tin, self.teach1, self.teach2):
                 if t is not None:
                     rows = full(t).view(self.Ba, -1)
                     rows[self.B].copy_(rows[self.B - 1])
@@ -521,7 +528,10 @@ class DecodeSession:
         if self.mega_groups is not None:
             # every group runs its n steps (no stop rule inside); the batch's stop rule is scanned over the n new rows behind them
             n = self.K if nsteps is None else max(1, min(self.K, int(nsteps)))
-            ops.dec_mega_groups(*self._group_blocks(n))
+            if self.mega_forced is not None:
+                ops.dec_mega_groups_forced(*self._group_blocks(n), self.mega_forced)
+            else:
+                ops.dec_mega_groups(*self._group_blocks(n))
             if self.tin is None:
                 ops.dec_stop_scan(self.yout, self.B, self.Tdp + 1, self.yout.shape[-1], self._t0, n, self._mega_shape["min_steps"],
                                   self._mega_shape["stop_threshold"], self.flag)

@@ -498,6 +498,10 @@ class DualSourceSelfAttentionTacotronModel:
                 out = infer(eng, b["source"], b["source_length"], max_steps=hp.max_iters, speaker_id=spk, **acc)
             mel_post = postnet_infer(eng, out["mel"]) if eng.cfg.use_postnet_v2 else None
             enc_al = out.get("enc_alignment")
+            # forced-alignment mode over a batch of several utterances: the batch is padded to its longest target and memory, so each
+            # prediction is cut to its own utterance - mel rows to ceil(target_length / r) * r, the query axis of the alignments
+            # likewise, the memory axis and `source` to source_length: the shapes of the utterance's batch-1 run
+            cut = hp.use_forced_alignment_mode and B > 1
             for i in range(B):
                 p = {"id": int(batch["id"][i]) if "id" in batch else i, "key": batch["key"][i] if "key" in batch else str(i),
                      "mel": out["mel"][i].float().cpu().numpy()}
@@ -515,6 +519,17 @@ class DualSourceSelfAttentionTacotronModel:
                 if eng.cfg.accent:                                              # models/models.py:585
                     p["accent_type"] = np.asarray(batch["accent_type"][i])
                 p["text"] = batch["text"][i] if "text" in batch else ""
+                if cut:
+                    nq, ns = -(-int(batch["target_length"][i]) // r), int(batch["source_length"][i])
+                    for k in ("mel", "mel_postnet", "ground_truth_mel"):
+                        if k in p:
+                            p[k] = p[k][:nq * r]
+                    for k in [k for k in p if k.startswith("alignment")]:
+                        # decoder histories [T_memory, T_query]; encoder heads (alignment5 ..) [T_memory, T_memory]
+                        p[k] = p[k][:ns, :(nq if k in ("alignment", "alignment2") else ns)]
+                    for k in ("source", "accent_type"):
+                        if k in p:
+                            p[k] = p[k][:ns]
                 yield p
 
 

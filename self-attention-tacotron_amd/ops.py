@@ -1260,6 +1260,19 @@ def dec_mega_groups(arr, dev_blocks):
     _lib.check(_lib.lib().satt_dec_mega_groups(arr, _p(dev_blocks), len(arr), _s()), "dec_mega_groups")
 
 
+def dec_mega_groups_forced_variant(arr, f):
+    """dec_mega_groups_variant of a launch with the batch's teacher alignments `f` (None: without): plus MEGA_VAR_FORCED, without
+    MEGA_VAR_LJ"""
+    return int(_lib.lib().satt_dec_mega_groups_forced_variant(arr, len(arr), None if f is None else C.byref(f)))
+
+
+def dec_mega_groups_forced(arr, dev_blocks, f):
+    """dec_mega_groups with forced alignments: `f` holds the teacher rows of the whole (padded) batch, [2 len(arr)][Td][Ti]; group g
+    reads batch rows b0, b0 + 1"""
+    _lib.check(_lib.lib().satt_dec_mega_groups_forced(arr, _p(dev_blocks), len(arr), None if f is None else C.byref(f), _s()),
+               "dec_mega_groups_forced")
+
+
 def dec_stop_scan(yout, B, rows, NO, t0, nsteps, min_steps, stop_threshold, flag):
     """stop rule of the batch over the steps t0 .. t0 + nsteps - 1 of yout [B][rows][NO] (row t + 1 = step t): *flag = t + 1"""
     _lib.check(_lib.lib().satt_dec_stop_scan(_p(yout), int(B), int(rows), int(NO), int(t0), int(nsteps), int(min_steps),

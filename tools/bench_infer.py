@@ -7,6 +7,8 @@ use_forward_attention_transition_agent=True or apply_dropout_on_inference=True.
 steps such batches ran on before.
 --forced: forced-alignment synthesis (infer(..., teacher_alignments=...), the second pass of predict_mel.py's
 use_forced_alignment_mode): one free-running utterance produces the alignments, the timed utterances replay them.
+--forced --batch 3 .. 16: the forced instantiations in group mode (path "persistent, groups, forced"); --no-groups returns it to the
+hipGraph path as well.
 usage: python tools/bench_infer.py [--steps 200] [--batch 1] [--no-groups] [--forced] [--hparams-json FILE] [--hparams "k=v,..."] [--repeat N]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -70,7 +72,8 @@ for _ in range(a.repeat):
     dt = out["decode_ms"] * 1e-3            # the decoder steps alone (HIP events around the replay loop)
     al = out["alignment1"]
     ses = eng._decode_sessions[next(reversed(eng._decode_sessions))]
-    path = "persistent, forced" if getattr(ses, "mega_forced", None) is not None else "persistent" if getattr(ses, "mega", None) is not None else \
+    path = "persistent, groups, forced" if (getattr(ses, "mega_groups", None) is not None and getattr(ses, "mega_forced", None) is not None) else \
+        "persistent, forced" if getattr(ses, "mega_forced", None) is not None else "persistent" if getattr(ses, "mega", None) is not None else \
         ("persistent, groups" if getattr(ses, "mega_groups", None) is not None else "launch-per-layer")
     frames = a.steps * cfg.r * B
     print(json.dumps({"metric": "forced-alignment decode" if a.forced else "free-running decode (config 5)", "model": (a.hparams_json or "ljspeech") + (" + " + a.hparams if a.hparams else ""), "path": path, "batch": B, "Ti": Ti, "decoder_steps": out["steps"],
