@@ -799,7 +799,10 @@ int satt_dec_mega_supported(const satt_dec_mega_params* p);
 int64_t satt_dec_mega_scratch_floats(int B, int heads, int head_dim);      /* (B, 0, 0): the single-source form */
 int satt_dec_mega(const satt_dec_mega_params* p, void* stream);
 /* which instantiation of the kernel satt_dec_mega launches for the block (diagnostics, tests): an OR of the bits below, or -1
- * where satt_dec_mega_supported() == 0 */
+ * where satt_dec_mega_supported() == 0.  Every satt_dec_mega* entry point - the seven *_supported / *_variant functions and the five
+ * launchers - is answered by ONE resolver in csrc/decode_mega2.hip, given the block (or the group blocks), the option block or NULL
+ * and the forced block or NULL: a launcher launches the instantiation its *_variant function names, and a call with a block left
+ * out or switched off gets the answer of the entry point without that argument because it is resolved by the same code. */
 #define SATT_MEGA_VAR_TABLES_LDS 1   /* context tables resident in LDS (B = 1, Ti <= 112) */
 #define SATT_MEGA_VAR_LJ 2           /* the dimensions of examples/ljspeech/self-attention-tacotron.json as compile-time constants */
 #define SATT_MEGA_VAR_SPEAKER 4      /* multi-speaker pre-net (sproj != NULL) */
@@ -807,7 +810,7 @@ int satt_dec_mega(const satt_dec_mega_params* p, void* stream);
 #define SATT_MEGA_VAR_SINGLE 64      /* the single-source form (Ds == heads == U2 == V2 == 0: the baseline model) */
 int satt_dec_mega_variant(const satt_dec_mega_params* p);
 /* ---- options of the persistent decode step, in a block of their own (satt_dec_mega_params keeps its layout).  Each option is off
- * while its key field is zero; with both off satt_dec_mega_opt() IS satt_dec_mega().  The instantiations that take options are
+ * while its key field is zero; with both off satt_dec_mega_opt() resolves as satt_dec_mega() does.  The instantiations that take options are
  * siblings of the plain ones (one more template flag): a launch without options runs the kernel it ran before.
  *  - transition agent (use_forward_attention_transition_agent; reference modules/forward_attention.py:109-116; key: agentW):
  *    u_{t+1} = sigmoid([context1_t | processed_query1_t] agentW + agentb), u_0 = 0.5, replaces both 0.5 factors of the forward
@@ -832,7 +835,7 @@ typedef struct {
 } satt_dec_mega_opt_params;
 #define SATT_MEGA_VAR_AGENT 16       /* transition agent (agentW != NULL) */
 #define SATT_MEGA_VAR_DROPOUT 32     /* pre-net dropout (drop_thresh != 0) */
-/* opt == NULL or both options off: satt_dec_mega(p, stream) / satt_dec_mega_variant(p) */
+/* opt == NULL or both options off: the launch of satt_dec_mega(p, stream) / the value of satt_dec_mega_variant(p) */
 int satt_dec_mega_opt(const satt_dec_mega_params* p, const satt_dec_mega_opt_params* opt, void* stream);
 int satt_dec_mega_opt_variant(const satt_dec_mega_params* p, const satt_dec_mega_opt_params* opt);
 /* ---- forced alignments on the persistent decode step (use_forced_alignment_mode; reference
@@ -848,9 +851,10 @@ int satt_dec_mega_opt_variant(const satt_dec_mega_params* p, const satt_dec_mega
  * the step of satt_dec_mega_opt.  Two exchanges per step fewer than the free-running step (pq, e): nine in the dual form, six
  * in the single-source form.  The forced instantiations are siblings of the GENERIC-width ones: a block with the dimensions
  * SATT_MEGA_VAR_LJ is keyed on runs forced on its generic sibling.
- *  - f == NULL or f->teach1 == NULL: the call IS satt_dec_mega_opt / satt_dec_mega_opt_variant.
+ *  - f == NULL or f->teach1 == NULL: the call resolves as satt_dec_mega_opt / satt_dec_mega_opt_variant (same launch, same codes).
  *  - otherwise the variant is that of the same block without f, without SATT_MEGA_VAR_LJ, | SATT_MEGA_VAR_FORCED;
- *  - the dual form needs teach2 (NULL: SATT_E_BADARG, variant -1); the single-source form never reads it;
+ *  - the dual form needs teach2 (NULL: SATT_E_BADARG, behind the checks of the block's own pointers and nsteps; variant -1); the
+ *    single-source form never reads it;
  *  - the transition agent switched on in `opt` together with f: SATT_E_UNSUPPORTED, variant -1 (the agent never runs under
  *    forced alignments: the caller leaves its fields NULL); the single-source form takes no options, as ever;
  *  - batches of 3 .. 16 under forced alignments: satt_dec_mega_groups_forced below (group mode with ONE forced block). */
@@ -898,10 +902,11 @@ int satt_dec_mega_groups(const satt_dec_mega_group* host_blocks, const void* dev
  * and ONE forced block serves the whole launch: teach1 / teach2 are the BATCH's histories [2 ngroups][Td][Ti] (the padding sample
  * of an odd batch has rows of its own), and group g reads batch rows b0 and b0 + 1 of them.  Each group runs the statements of
  * the B = 2 launch of satt_dec_mega_forced on its pair; nothing crosses groups and no group evaluates the stop rule.
- *  - f == NULL or f->teach1 == NULL: the call IS satt_dec_mega_groups / satt_dec_mega_groups_variant;
+ *  - f == NULL or f->teach1 == NULL: the call resolves as satt_dec_mega_groups / satt_dec_mega_groups_variant;
  *  - otherwise the variant is (that of satt_dec_mega_groups_variant & ~SATT_MEGA_VAR_LJ) | SATT_MEGA_VAR_FORCED;
  *  - the transition agent switched on in the blocks: SATT_E_UNSUPPORTED, variant -1;
- *  - the dual form without teach2: SATT_E_BADARG, variant -1; the single-source form never reads it;
+ *  - the dual form without teach2: SATT_E_BADARG (in FRONT of the checks of the blocks' pointers and nsteps), variant -1; the
+ *    single-source form never reads it;
  *  - everything satt_dec_mega_groups checks is checked (p.flag == NULL, part / step / state of their own per group, blocks that
  *    agree), and every refusal returns before anything is launched. */
 int satt_dec_mega_groups_forced_variant(const satt_dec_mega_group* host_blocks, int ngroups, const satt_dec_mega_forced_params* f);

@@ -52,8 +52,8 @@
 // row index (64-bit), as it does for the dropout mask row.  Nothing else differs and nothing crosses groups; the granule argument
 // above is per group.  No group evaluates the stop rule (p.flag == NULL).
 // WHAT THE TWO KERNELS SHARE: the leaf helpers (split_mul / split_mul_fb / split_fill, gather_vec, slice_*, pin, lstm_unit,
-// mega_drop) and, on the host, one pointer list, one `spread` static and one launch function (mega_launch) behind both dispatch
-// ladders.  EVERY PHASE THEY HAVE IN COMMON IS WRITTEN OUT IN BOTH KERNELS, and a fix to one copy has to be made in the other: the
+// mega_drop) and, on the host, one pointer list, one `spread` static, one resolver and one dispatcher (mega_resolve, mega_dispatch,
+// mega_launch).  EVERY PHASE THEY HAVE IN COMMON IS WRITTEN OUT IN BOTH KERNELS, and a fix to one copy has to be made in the other: the
 // launch prologue (zeroing of every LDS word, placement handshake, staging, state loads), A1 / A2, the three cell steps, the
 // location features, phase C (requests, poll, softmax, recursion, write of al / e1), the history and hand-over stores, G2
 // (projection, yout, stop rule, step and flag words) and the hand-over contexts.  Each was moved into a __forceinline__ helper and
@@ -2010,23 +2010,31 @@ extern "C" int64_t satt_dec_mega_scratch_floats(int B, int heads, int hd) {
   return 2 * (int64_t)B * gl_of(hd, true).total;      // (the multi-speaker layout: the plain one is a prefix of it per sample)
 }
 
+#include <utility>
+
+extern "C" int64_t satt_dec_mega_groups_scratch_floats(int ngroups, int heads, int hd) {
+  if (ngroups < 1 || ngroups > SATT_MEGA_GROUPS_MAX) return 0;
+  return ngroups * satt_dec_mega_scratch_floats(2, heads, hd);
+}
+
+// ---- the host side of a launch: ONE resolver (mega_resolve: the variant bits or the refusal of whatever a caller brings, and for a
+// launch the pointer checks and the LDS bytes) and ONE dispatcher (mega_dispatch: variant bits -> instantiation) behind every entry
+// point.  A rule about what runs where is stated once, in mega_resolve.
 namespace {
+typedef satt_dec_mega_params Blk; typedef satt_dec_mega_opt_params Opt; typedef satt_dec_mega_forced_params Frc; typedef satt_dec_mega_group Grp;
 // the single-source form is keyed on the block itself; a block that is only half single (Ds == 0 with a second memory, or the
 // reverse) is neither form and is refused by the dual form's conditions
-inline bool mega_single(const satt_dec_mega_params& p) { return p.Ds == 0 && p.heads == 0 && p.U2 == 0 && p.V2 == 0; }
+inline bool mega_single(const Blk& p) { return p.Ds == 0 && p.heads == 0 && p.U2 == 0 && p.V2 == 0; }
 // the shape conditions both forms share (batch, memory length, cell widths, pre-net, fed frame, projection, location layer)
-inline bool mega_common_shapes(const satt_dec_mega_params& p) {
+inline bool mega_common_shapes(const Blk& p) {
   return p.B >= 1 && p.B <= 2 && p.Td >= 1 && p.Ti >= 1 && p.Ti <= M2TI && (p.Ti + M2G - 1) / M2G <= 8 && p.A == M2N && p.D == M2N &&
          p.U1 % 4 == 0 && p.V1 >= 1 && p.P0 >= 8 && p.P0 <= M2N && p.P0 % 8 == 0 && p.P1 >= 8 && p.P1 <= M2N && p.P1 % 8 == 0 &&
          p.feed >= 1 && p.feed <= M2N && p.feed + 1 <= p.NO && p.NO <= M2NO && p.ldout % 8 == 0 && p.ldout >= p.NO &&
          p.kernel >= 1 && p.kernel <= 16 && p.filters >= 1 && p.filters <= 8;
 }
-}  // namespace
-
-// shapes the kernel takes (pointers are checked by satt_dec_mega)
-extern "C" int satt_dec_mega_supported(const satt_dec_mega_params* pp) {
-  if (!pp || !mega_common_shapes(*pp)) return 0;
-  const satt_dec_mega_params& p = *pp;
+// shapes the kernels take
+bool mega_shapes(const Blk& p) {
+  if (!mega_common_shapes(p)) return false;
   if (mega_single(p))      // the single-source form (dec_mega2_single_k): its own widths and its own LDS layout
     return p.U1 >= 8 && p.U1 <= M2N && p.V1 <= 32 * M2G && mega2s_lds_bytes(p.B <= 1 ? 1 : 2, p.Ti) <= 160 * 1024;
   const int hd = p.heads > 0 ? M2N / p.heads : 0, UQ = p.U1 + p.U2, CT = p.V1 + p.V2;
@@ -2036,38 +2044,121 @@ extern "C" int satt_dec_mega_supported(const satt_dec_mega_params* pp) {
          mega2_lds_bytes(p.B <= 1 ? 1 : 2, p.Ti) <= 160 * 1024;
 }
 
-// the instantiation satt_dec_mega launches for a block (satt_hip.h: SATT_MEGA_VAR_*), -1 where the kernel does not take it
-extern "C" int satt_dec_mega_variant(const satt_dec_mega_params* pp) {
-  if (!pp || !satt_dec_mega_supported(pp)) return -1;
-  const satt_dec_mega_params& p = *pp;
+inline bool opt_agent(const Opt* o) { return o && o->agentW; }
+inline bool opt_drop(const Opt* o) { return o && o->drop_thresh != 0u; }
+inline bool frc_on(const Frc* f) { return f && f->teach1; }
+inline const Opt* group_opt(const Grp& g) { return g.has_opt ? &g.o : nullptr; }
+
+// the variant bits of ONE block with its options (include/satt_hip.h: SATT_MEGA_VAR_*), -1 where the kernels do not take it
+int mega_block_variant(const Blk& p, const Opt* opt) {
+  if (!mega_shapes(p)) return -1;
   const int form = (p.B <= 1 && p.Ti <= M2TR ? SATT_MEGA_VAR_TABLES_LDS : 0) | (p.sproj ? SATT_MEGA_VAR_SPEAKER : 0) | (p.B > 1 ? SATT_MEGA_VAR_TWO_SAMPLES : 0);
-  if (mega_single(p)) return SATT_MEGA_VAR_SINGLE | form;
+  if (mega_single(p)) return opt_agent(opt) || opt_drop(opt) ? -1 : SATT_MEGA_VAR_SINGLE | form;      // the single form takes no options
   const bool lj = p.U1 == 224 && p.U2 == 32 && p.V1 == 256 && p.V2 == 32 && p.heads == 2 && p.NO == 161 && p.feed == 80 && p.P0 == 256 &&
                   p.P1 == 128 && p.kernel == 10 && p.filters == 5 && getenv("SATT_DECODE_GENERIC") == nullptr;
-  return form | (lj ? SATT_MEGA_VAR_LJ : 0);
+  return form | (lj ? SATT_MEGA_VAR_LJ : 0) | (opt_agent(opt) ? SATT_MEGA_VAR_AGENT : 0) | (opt_drop(opt) ? SATT_MEGA_VAR_DROPOUT : 0);
 }
 
-namespace {
-inline bool opt_agent(const satt_dec_mega_opt_params* o) { return o && o->agentW; }
-inline bool opt_drop(const satt_dec_mega_opt_params* o) { return o && o->drop_thresh != 0u; }
-}  // namespace
-
-// the same with options (satt_hip.h: satt_dec_mega_opt_params); with none on: satt_dec_mega_variant
-extern "C" int satt_dec_mega_opt_variant(const satt_dec_mega_params* pp, const satt_dec_mega_opt_params* opt) {
-  const int var = satt_dec_mega_variant(pp);
-  if (var < 0) return var;
-  if ((var & SATT_MEGA_VAR_SINGLE) && (opt_agent(opt) || opt_drop(opt))) return -1;      // the single form takes no options
-  return var | (opt_agent(opt) ? SATT_MEGA_VAR_AGENT : 0) | (opt_drop(opt) ? SATT_MEGA_VAR_DROPOUT : 0);
+// a block (and its options) whose variant exists, before a launch: the pointers the kernel of its form dereferences
+int mega_check_block(const Blk& p, const Opt* opt) {
+  if (p.nsteps < 1) return SATT_E_UNSUPPORTED;
+  // what both forms read ...
+  if (!p.Wp0 || !p.Wp1 || !p.Wa || !p.Wq || !p.W1 || !p.W2 || !p.Wout || !p.bp0 || !p.bp1 || !p.ba || !p.b1l || !p.b2l || !p.bout ||
+      !p.locF || !p.locFb || !p.locU || !p.v1 || !p.b1 || !p.lengths || !p.keys1 || !p.values1 || !p.ca || !p.ha || !p.c1 || !p.h1 ||
+      !p.c2 || !p.h2 || !p.a_state || !p.alpha_state || !p.ctx || !p.yout || !p.align1 || !p.part || !p.ctab || !p.step || !p.err)
+    return SATT_E_BADARG;
+  // ... and the dual form's second memory and self-attention block (NULL and never read in the single-source form)
+  if (!mega_single(p) && (!p.Wkvq || !p.Wot || !p.bkvq || !p.bot || !p.v2 || !p.keys2 || !p.values2 || !p.align2 || !p.kvq)) return SATT_E_BADARG;
+  if (p.sproj && (!p.Wp02 || !p.bp02)) return SATT_E_BADARG;      // multi-speaker pre-net: its second Dense comes with the speaker term
+  // options: the agent belongs to the forward recursion and comes with its bias, table and state word; dropout with its seed word
+  if (opt_agent(opt) && (!opt->agentb || !opt->agent_tab || !opt->u_state || p.att1_mode != 0)) return SATT_E_BADARG;
+  if (opt_drop(opt) && (!opt->drop_seed || opt->drop_T < 1)) return SATT_E_BADARG;
+  return SATT_OK;
 }
 
-namespace {
+// group blocks: every shape field, the form and nsteps
+bool groups_agree(const Grp& a, const Grp& b) {
+  const satt_dec_mega_params &p = a.p, &q = b.p;
+  const satt_dec_mega_opt_params *o = group_opt(a), *r = group_opt(b);
+  return p.B == q.B && p.Td == q.Td && p.Ti == q.Ti && p.A == q.A && p.D == q.D && p.Ds == q.Ds && p.heads == q.heads && p.U1 == q.U1 &&
+         p.V1 == q.V1 && p.U2 == q.U2 && p.V2 == q.V2 && p.kernel == q.kernel && p.filters == q.filters && p.att1_mode == q.att1_mode &&
+         p.cumulative == q.cumulative && p.P0 == q.P0 && p.P1 == q.P1 && p.feed == q.feed && p.NO == q.NO && p.ldout == q.ldout &&
+         p.zc == q.zc && p.zh == q.zh && p.stop_threshold == q.stop_threshold && p.min_steps == q.min_steps && p.nsteps == q.nsteps &&
+         !p.sproj == !q.sproj && !p.tin == !q.tin && !p.Wfh == !q.Wfh && !p.Wfl == !q.Wfl && !p.bfb == !q.bfb &&
+         !a.has_opt == !b.has_opt && opt_agent(o) == opt_agent(r) && opt_drop(o) == opt_drop(r) &&
+         (!opt_drop(o) || (o->drop_thresh == r->drop_thresh && o->drop_scale == r->drop_scale && o->drop_T == r->drop_T &&
+                           o->drop_stream[0] == r->drop_stream[0] && o->drop_stream[1] == r->drop_stream[1]));
+}
+// what every group launch checks behind its variant: the device copy, every block's pointers, no stop rule, nothing shared
+int mega_check_groups(const Grp* hb, const void* device_blocks, int ngroups) {
+  if (!device_blocks) return SATT_E_BADARG;
+  for (int g = 0; g < ngroups; ++g) {
+    if (const int rc = mega_check_block(hb[g].p, group_opt(hb[g]))) return rc;
+    if (hb[g].p.flag) return SATT_E_BADARG;          // no stop rule inside a group launch: satt_dec_stop_scan behind it
+    for (int h = 0; h < g; ++h)                      // exchanges, step words and state belong to ONE group
+      if (hb[h].p.part == hb[g].p.part || hb[h].p.step == hb[g].p.step || hb[h].p.ha == hb[g].p.ha) return SATT_E_BADARG;
+  }
+  return SATT_OK;
+}
+
+// what a call is given - ONE block with its options, or (groups) a host array of group blocks with its device copy; forced alignments
+// or NULL with either - and what becomes of it.  var: the SATT_MEGA_VAR_* bits, -1 where no kernel takes the call.  For a launch, rc:
+// SATT_OK, or what the launcher returns without launching anything; then the kernel's arguments and its dynamic LDS bytes.
+struct MegaAsk {
+  const Blk* p; const Opt* opt; const Grp* hb; const void* device_blocks; int ngroups; bool groups; const Frc* f;
+  MegaAsk(const Blk* p, const Opt* opt, const Frc* f) : p(p), opt(opt), hb(nullptr), device_blocks(nullptr), ngroups(0), groups(false), f(f) {}
+  MegaAsk(const Grp* hb, const void* dev, int ngroups, const Frc* f) : p(nullptr), opt(nullptr), hb(hb), device_blocks(dev), ngroups(ngroups), groups(true), f(f) {}
+};
+struct MegaPlan {
+  int var = -1, rc = SATT_E_UNSUPPORTED;
+  size_t smem = 0;
+  MegaGrpP a{};                                      // the block; in group mode a place holder (every group reads its own from the array)
+  const Opt* opt = nullptr; const Frc* f = nullptr;
+};
+
+MegaPlan mega_resolve(MegaAsk q, bool launch) {
+  MegaPlan pl;
+  // a group launch: 1 .. 8 two-sample blocks that agree, every one a block a single launch takes; the first one names the kernel
+  if (q.groups) {
+    if (!q.hb || q.ngroups < 1 || q.ngroups > SATT_MEGA_GROUPS_MAX) return pl;
+    for (int g = 0; g < q.ngroups; ++g)
+      if (q.hb[g].p.B != 2 || q.hb[g].b0 < 0 || mega_block_variant(q.hb[g].p, group_opt(q.hb[g])) < 0 || !groups_agree(q.hb[0], q.hb[g])) return pl;
+    q.p = &q.hb[0].p; q.opt = group_opt(q.hb[0]);
+  }
+  if (!q.p) return pl;
+  int var = mega_block_variant(*q.p, q.opt);
+  if (var < 0) return pl;
+  if (q.groups) var |= SATT_MEGA_VAR_GROUPS;
+  // forced alignments (without teacher rows the call is the free-running one)
+  bool no_teach2 = false;
+  if (frc_on(q.f)) {
+    if (var & SATT_MEGA_VAR_AGENT) return pl;        // the agent never runs under forced alignments
+    no_teach2 = !(var & SATT_MEGA_VAR_SINGLE) && !q.f->teach2;      // the dual form reads both histories, the single form one
+    var = (var & ~SATT_MEGA_VAR_LJ) | SATT_MEGA_VAR_FORCED;         // the compile-time widths have no forced sibling
+  }
+  pl.var = no_teach2 ? -1 : var;
+  if (!launch) return pl;
+  // the pointers.  A missing teach2 is SATT_E_BADARG like them; a single launch looks at its block first (so nsteps < 1 wins), a
+  // group launch at teach2 first - the order each entry point had when it was written, and callers may have come to rely on it
+  pl.rc = q.groups ? mega_check_groups(q.hb, q.device_blocks, q.ngroups) : mega_check_block(*q.p, q.opt);
+  if (no_teach2 && (q.groups || pl.rc == SATT_OK)) pl.rc = SATT_E_BADARG;
+  const bool has_opt = var & (SATT_MEGA_VAR_AGENT | SATT_MEGA_VAR_DROPOUT);
+  const int NB = (var & SATT_MEGA_VAR_TWO_SAMPLES) ? 2 : 1;
+  pl.smem = (var & SATT_MEGA_VAR_SINGLE) ? mega2s_lds_bytes(NB, q.p->Ti) : mega2_lds_bytes(NB, q.p->Ti, has_opt);
+  if (pl.rc == SATT_OK && pl.smem > 160 * 1024) pl.rc = SATT_E_UNSUPPORTED;      // (B = 2 with options: 163 104 bytes - every supported shape fits)
+  static_cast<Blk&>(pl.a) = *q.p;
+  pl.a.blocks = (const Grp*)q.device_blocks; pl.a.ngroups = q.ngroups;
+  pl.opt = q.opt; pl.f = q.f;
+  return pl;
+}
+
 // one XCD (grid 8 x 32, every eighth workgroup works: see dec_mega2_k) unless SATT_DECODE_ONE_XCD=0
 inline int mega_spread() {
   static const int spread = [] { const char* e = getenv("SATT_DECODE_ONE_XCD"); return (e && atoi(e) == 0) ? 1 : 8; }();
   return spread;
 }
 // workgroups of a launch: 32 on one XCD of 8; group mode: 32 per group, the groups side by side on the XCDs
-inline int mega_grid(const satt_dec_mega_params&, int spread) { return M2G * spread; }
+inline int mega_grid(const Blk&, int spread) { return M2G * spread; }
 inline int mega_grid(const MegaGrpP& a, int spread) { return M2G * (spread > 1 ? spread : a.ngroups); }
 // one instantiation of either kernel: its dynamic LDS size, then the launch
 template <class... KA, class P, class... A>
@@ -2081,212 +2172,86 @@ int mega_launch(void (*kernel)(KA...), size_t smem, hipStream_t s, const P& p, c
   SATT_LAUNCH_CHECK();
   return SATT_OK;
 }
-}  // namespace
 
-namespace {
-// a supported block (and its options) before a launch: the pointers the kernel of its form dereferences
-int mega_check_block(const satt_dec_mega_params& p, const satt_dec_mega_opt_params* opt) {
-  if (p.nsteps < 1) return SATT_E_UNSUPPORTED;
-  const bool single = mega_single(p);
-  if (single && (opt_agent(opt) || opt_drop(opt))) return SATT_E_UNSUPPORTED;
-  // what both forms read ...
-  if (!p.Wp0 || !p.Wp1 || !p.Wa || !p.Wq || !p.W1 || !p.W2 || !p.Wout || !p.bp0 || !p.bp1 || !p.ba || !p.b1l || !p.b2l || !p.bout ||
-      !p.locF || !p.locFb || !p.locU || !p.v1 || !p.b1 || !p.lengths || !p.keys1 || !p.values1 || !p.ca || !p.ha || !p.c1 || !p.h1 ||
-      !p.c2 || !p.h2 || !p.a_state || !p.alpha_state || !p.ctx || !p.yout || !p.align1 || !p.part || !p.ctab || !p.step || !p.err)
-    return SATT_E_BADARG;
-  // ... and the dual form's second memory and self-attention block (NULL and never read in the single-source form)
-  if (!single && (!p.Wkvq || !p.Wot || !p.bkvq || !p.bot || !p.v2 || !p.keys2 || !p.values2 || !p.align2 || !p.kvq)) return SATT_E_BADARG;
-  if (p.sproj && (!p.Wp02 || !p.bp02)) return SATT_E_BADARG;      // multi-speaker pre-net: its second Dense comes with the speaker term
-  // options: the agent belongs to the forward recursion and comes with its bias, table and state word; dropout with its seed word
-  if (opt_agent(opt) && (!opt->agentb || !opt->agent_tab || !opt->u_state || p.att1_mode != 0)) return SATT_E_BADARG;
-  if (opt_drop(opt) && (!opt->drop_seed || opt->drop_T < 1)) return SATT_E_BADARG;
-  return SATT_OK;
+// ---- variant bits -> instantiation.  A kernel is named by its variant with the two option bits folded into one (both or neither:
+// OPT is ONE template flag), and every template argument below is an expression in that key - no bit can reach another parameter.
+// mega_kernel_exists() states which kernels there are, M2KERNELS lists them, and nothing else is instantiated (this file is the
+// longest translation unit of the build).  The list is in the order the device compiler has emitted the kernels since each was
+// added - free running, forced, groups, forced groups, the single form first in each - so that the device code of two revisions
+// compares byte for byte (profiles/decode_launcher_kernel_regs.txt).
+constexpr int M2V_OPT = SATT_MEGA_VAR_AGENT | SATT_MEGA_VAR_DROPOUT, M2V_KEYS = 2 * SATT_MEGA_VAR_FORCED, M2V_KERNELS = 64;
+constexpr int mega_key(int var) { return (var & M2V_OPT) ? var | M2V_OPT : var; }
+constexpr bool mega_kernel_exists(int key) {
+  const bool tres = key & SATT_MEGA_VAR_TABLES_LDS, lj = key & SATT_MEGA_VAR_LJ, two = key & SATT_MEGA_VAR_TWO_SAMPLES, opt = key & M2V_OPT,
+             single = key & SATT_MEGA_VAR_SINGLE, grp = key & SATT_MEGA_VAR_GROUPS, frc = key & SATT_MEGA_VAR_FORCED;
+  return key >= 0 && key < M2V_KEYS && key == mega_key(key) &&
+         !(tres && two) &&                           // the context tables fit LDS beside one sample only
+         !(lj && frc) &&                             // no compile-time-width kernel with forced alignments
+         !(grp && (!two || tres)) &&                 // a group is a two-sample problem
+         !(single && (lj || opt));                   // the single form: generic widths, no options
+}
+constexpr int M2KERNELS[M2V_KERNELS] = {
+    69, 65, 68, 64, 76, 72, 55, 7, 53, 5, 51, 3, 49, 1, 54, 6, 52, 4, 50, 2, 48, 0, 62, 14, 60, 12, 58, 10, 56, 8,      // free running
+    325, 321, 324, 320, 332, 328, 309, 261, 305, 257, 308, 260, 304, 256, 316, 268, 312, 264,                        // forced
+    204, 200, 190, 142, 188, 140, 186, 138, 184, 136,                                                                // groups
+    460, 456, 444, 396, 440, 392};                                                                                   // forced groups
+constexpr bool mega_kernels_listed() {             // the list is the set: distinct keys that exist, as many as exist
+  int n = 0;
+  for (int k = 0; k < M2V_KEYS; ++k) n += mega_kernel_exists(k);
+  for (int i = 0; i < M2V_KERNELS; ++i)
+    for (int j = 0; j <= i; ++j) if (!mega_kernel_exists(M2KERNELS[i]) || (j < i && M2KERNELS[j] == M2KERNELS[i])) return false;
+  return n == M2V_KERNELS;
+}
+static_assert(mega_kernels_listed(), "the instantiations of dec_mega2_k / dec_mega2_single_k");
+
+template <bool ON, class Off, class T> inline auto mega_arg(const T* on) { if constexpr (ON) return *on; else return Off(); }
+
+template <int KEY> int mega_launch_key(const MegaPlan& pl, hipStream_t s) {
+  constexpr int NB = (KEY & SATT_MEGA_VAR_TWO_SAMPLES) ? 2 : 1;
+  constexpr bool TRES = KEY & SATT_MEGA_VAR_TABLES_LDS, LJ = KEY & SATT_MEGA_VAR_LJ, SPK = KEY & SATT_MEGA_VAR_SPEAKER, OPT = KEY & M2V_OPT,
+                 GRP = KEY & SATT_MEGA_VAR_GROUPS, FRC = KEY & SATT_MEGA_VAR_FORCED;
+  const typename MegaArgT<GRP>::type& a = pl.a;      // (a single launch is given the block alone)
+  const auto f = mega_arg<FRC, MegaNoFrc>(pl.f);
+  if constexpr (KEY & SATT_MEGA_VAR_SINGLE) return mega_launch(dec_mega2_single_k<NB, TRES, SPK, GRP, FRC>, pl.smem, s, a, f);
+  else return mega_launch(dec_mega2_k<NB, TRES, LJ, SPK, OPT, GRP, FRC>, pl.smem, s, a, mega_arg<OPT, MegaNoOpt>(pl.opt), f);
+}
+
+typedef int (*MegaLaunchFn)(const MegaPlan&, hipStream_t);
+struct MegaLaunchTable { MegaLaunchFn of[M2V_KEYS]; };
+template <int... I> constexpr MegaLaunchTable mega_launch_table(std::integer_sequence<int, I...>) {
+  MegaLaunchTable t{};
+  ((t.of[M2KERNELS[M2V_KERNELS - 1 - I]] = &mega_launch_key<M2KERNELS[M2V_KERNELS - 1 - I]>), ...);      // (emitted last named first)
+  return t;
+}
+
+// resolve, refuse or launch
+int mega_dispatch(const MegaAsk& q, void* stream) {
+  static constexpr MegaLaunchTable table = mega_launch_table(std::make_integer_sequence<int, M2V_KERNELS>());
+  const MegaPlan pl = mega_resolve(q, true);
+  if (pl.rc != SATT_OK) return pl.rc;
+  const MegaLaunchFn fn = table.of[mega_key(pl.var)];
+  return fn ? fn(pl, (hipStream_t)stream) : SATT_E_UNSUPPORTED;
 }
 }  // namespace
 
-extern "C" int satt_dec_mega_opt(const satt_dec_mega_params* pp, const satt_dec_mega_opt_params* opt, void* stream) {
-  if (!pp || !satt_dec_mega_supported(pp)) return SATT_E_UNSUPPORTED;
-  const satt_dec_mega_params& p = *pp;
-  const bool single = mega_single(p);
-  if (const int rc = mega_check_block(p, opt)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const int var = satt_dec_mega_opt_variant(pp, opt);
-  const bool tables = var & SATT_MEGA_VAR_TABLES_LDS, lj = var & SATT_MEGA_VAR_LJ, spk = var & SATT_MEGA_VAR_SPEAKER;
-  const bool has_opt = var & (SATT_MEGA_VAR_AGENT | SATT_MEGA_VAR_DROPOUT);
-  const int NB = (var & SATT_MEGA_VAR_TWO_SAMPLES) ? 2 : 1;
-  const size_t smem = single ? mega2s_lds_bytes(NB, p.Ti) : mega2_lds_bytes(NB, p.Ti, has_opt);
-  if (smem > 160 * 1024) return SATT_E_UNSUPPORTED;      // (B = 2 with options: 163 104 bytes - every supported shape fits)
-#define SATT_MEGA2S(NBV, TR) \
-  (spk ? mega_launch(dec_mega2_single_k<NBV, TR, true>, smem, s, p, MegaNoFrc()) : mega_launch(dec_mega2_single_k<NBV, TR, false>, smem, s, p, MegaNoFrc()))
-#define SATT_MEGA2O(NBV, TR, LJV, SP) \
-  (has_opt ? mega_launch(dec_mega2_k<NBV, TR, LJV, SP, true>, smem, s, p, *opt, MegaNoFrc()) : \
-             mega_launch(dec_mega2_k<NBV, TR, LJV, SP, false>, smem, s, p, MegaNoOpt(), MegaNoFrc()))
-#define SATT_MEGA2L(NBV, TR, SP) (lj ? SATT_MEGA2O(NBV, TR, true, SP) : SATT_MEGA2O(NBV, TR, false, SP))
-#define SATT_MEGA2D(NBV, TR) (spk ? SATT_MEGA2L(NBV, TR, true) : SATT_MEGA2L(NBV, TR, false))
-  // (the ladders name the 30 instantiations in the order they always had, the single form's first: the device compiler emits them
-  //  in that order, and listings of two revisions compare line by line)
-#define SATT_MEGA2(K) (tables ? K(1, true) : NB == 1 ? K(1, false) : K(2, false))
-  return single ? SATT_MEGA2(SATT_MEGA2S) : SATT_MEGA2(SATT_MEGA2D);
-#undef SATT_MEGA2S
-#undef SATT_MEGA2O
-#undef SATT_MEGA2L
-#undef SATT_MEGA2D
-#undef SATT_MEGA2
+// ---- the entry points (include/satt_hip.h)
+extern "C" int satt_dec_mega_supported(const Blk* p) { return mega_resolve({p, nullptr, nullptr}, false).var >= 0; }
+extern "C" int satt_dec_mega_variant(const Blk* p) { return mega_resolve({p, nullptr, nullptr}, false).var; }
+extern "C" int satt_dec_mega_opt_variant(const Blk* p, const Opt* opt) { return mega_resolve({p, opt, nullptr}, false).var; }
+extern "C" int satt_dec_mega_forced_variant(const Blk* p, const Opt* opt, const Frc* f) { return mega_resolve({p, opt, f}, false).var; }
+extern "C" int satt_dec_mega_groups_variant(const Grp* hb, int ngroups) { return mega_resolve({hb, nullptr, ngroups, nullptr}, false).var; }
+extern "C" int satt_dec_mega_groups_supported(const Grp* hb, int ngroups) { return satt_dec_mega_groups_variant(hb, ngroups) >= 0; }
+extern "C" int satt_dec_mega_groups_forced_variant(const Grp* hb, int ngroups, const Frc* f) { return mega_resolve({hb, nullptr, ngroups, f}, false).var; }
+
+extern "C" int satt_dec_mega(const Blk* p, void* stream) { return mega_dispatch({p, nullptr, nullptr}, stream); }
+extern "C" int satt_dec_mega_opt(const Blk* p, const Opt* opt, void* stream) { return mega_dispatch({p, opt, nullptr}, stream); }
+extern "C" int satt_dec_mega_forced(const Blk* p, const Opt* opt, const Frc* f, void* stream) { return mega_dispatch({p, opt, f}, stream); }
+extern "C" int satt_dec_mega_groups(const Grp* hb, const void* device_blocks, int ngroups, void* stream) {
+  return mega_dispatch({hb, device_blocks, ngroups, nullptr}, stream);
 }
-
-extern "C" int satt_dec_mega(const satt_dec_mega_params* pp, void* stream) { return satt_dec_mega_opt(pp, nullptr, stream); }
-
-// ---- forced alignments (include/satt_hip.h: satt_dec_mega_forced_params; template flag FRC of both kernels).  Without teacher rows
-// the entry points ARE the ones above.  The forced instantiations are siblings of the generic-width ones only (18: 12 dual, 6 single;
-// six more in group mode, behind satt_dec_mega_groups below).
-namespace {
-inline bool frc_on(const satt_dec_mega_forced_params* f) { return f && f->teach1; }
-}  // namespace
-
-extern "C" int satt_dec_mega_forced_variant(const satt_dec_mega_params* pp, const satt_dec_mega_opt_params* opt, const satt_dec_mega_forced_params* f) {
-  if (!frc_on(f)) return satt_dec_mega_opt_variant(pp, opt);
-  if (opt_agent(opt)) return -1;                     // the agent never runs under forced alignments
-  const int var = satt_dec_mega_opt_variant(pp, opt);
-  if (var < 0) return var;
-  if (!(var & SATT_MEGA_VAR_SINGLE) && !f->teach2) return -1;
-  return (var & ~SATT_MEGA_VAR_LJ) | SATT_MEGA_VAR_FORCED;
-}
-
-extern "C" int satt_dec_mega_forced(const satt_dec_mega_params* pp, const satt_dec_mega_opt_params* opt, const satt_dec_mega_forced_params* f,
-                                    void* stream) {
-  if (!frc_on(f)) return satt_dec_mega_opt(pp, opt, stream);
-  if (!pp || !satt_dec_mega_supported(pp)) return SATT_E_UNSUPPORTED;
-  const satt_dec_mega_params& p = *pp;
-  if (opt_agent(opt)) return SATT_E_UNSUPPORTED;
-  if (const int rc = mega_check_block(p, opt)) return rc;
-  const bool single = mega_single(p);
-  if (!single && !f->teach2) return SATT_E_BADARG;
-  hipStream_t s = (hipStream_t)stream;
-  const int var = satt_dec_mega_forced_variant(pp, opt, f);
-  if (var < 0) return SATT_E_UNSUPPORTED;
-  const bool tables = var & SATT_MEGA_VAR_TABLES_LDS, spk = var & SATT_MEGA_VAR_SPEAKER, has_opt = var & SATT_MEGA_VAR_DROPOUT;
-  const int NB = (var & SATT_MEGA_VAR_TWO_SAMPLES) ? 2 : 1;
-  const size_t smem = single ? mega2s_lds_bytes(NB, p.Ti) : mega2_lds_bytes(NB, p.Ti, has_opt);
-  if (smem > 160 * 1024) return SATT_E_UNSUPPORTED;
-#define SATT_MEGA2FS(NBV, TR) \
-  (spk ? mega_launch(dec_mega2_single_k<NBV, TR, true, false, true>, smem, s, p, *f) : mega_launch(dec_mega2_single_k<NBV, TR, false, false, true>, smem, s, p, *f))
-#define SATT_MEGA2FO(NBV, TR, SP) \
-  (has_opt ? mega_launch(dec_mega2_k<NBV, TR, false, SP, true, false, true>, smem, s, p, *opt, *f) : \
-             mega_launch(dec_mega2_k<NBV, TR, false, SP, false, false, true>, smem, s, p, MegaNoOpt(), *f))
-#define SATT_MEGA2FD(NBV, TR) (spk ? SATT_MEGA2FO(NBV, TR, true) : SATT_MEGA2FO(NBV, TR, false))
-#define SATT_MEGA2F(K) (tables ? K(1, true) : NB == 1 ? K(1, false) : K(2, false))
-  return single ? SATT_MEGA2F(SATT_MEGA2FS) : SATT_MEGA2F(SATT_MEGA2FD);
-#undef SATT_MEGA2FS
-#undef SATT_MEGA2FO
-#undef SATT_MEGA2FD
-#undef SATT_MEGA2F
-}
-
-// ---- group mode (include/satt_hip.h: satt_dec_mega_group)
-extern "C" int64_t satt_dec_mega_groups_scratch_floats(int ngroups, int heads, int hd) {
-  if (ngroups < 1 || ngroups > SATT_MEGA_GROUPS_MAX) return 0;
-  return ngroups * satt_dec_mega_scratch_floats(2, heads, hd);
-}
-
-namespace {
-inline const satt_dec_mega_opt_params* group_opt(const satt_dec_mega_group& g) { return g.has_opt ? &g.o : nullptr; }
-// every shape field, the form and nsteps
-bool groups_agree(const satt_dec_mega_group& a, const satt_dec_mega_group& b) {
-  const satt_dec_mega_params &p = a.p, &q = b.p;
-  const satt_dec_mega_opt_params *o = group_opt(a), *r = group_opt(b);
-  return p.B == q.B && p.Td == q.Td && p.Ti == q.Ti && p.A == q.A && p.D == q.D && p.Ds == q.Ds && p.heads == q.heads && p.U1 == q.U1 &&
-         p.V1 == q.V1 && p.U2 == q.U2 && p.V2 == q.V2 && p.kernel == q.kernel && p.filters == q.filters && p.att1_mode == q.att1_mode &&
-         p.cumulative == q.cumulative && p.P0 == q.P0 && p.P1 == q.P1 && p.feed == q.feed && p.NO == q.NO && p.ldout == q.ldout &&
-         p.zc == q.zc && p.zh == q.zh && p.stop_threshold == q.stop_threshold && p.min_steps == q.min_steps && p.nsteps == q.nsteps &&
-         !p.sproj == !q.sproj && !p.tin == !q.tin && !p.Wfh == !q.Wfh && !p.Wfl == !q.Wfl && !p.bfb == !q.bfb &&
-         !a.has_opt == !b.has_opt && opt_agent(o) == opt_agent(r) && opt_drop(o) == opt_drop(r) &&
-         (!opt_drop(o) || (o->drop_thresh == r->drop_thresh && o->drop_scale == r->drop_scale && o->drop_T == r->drop_T &&
-                           o->drop_stream[0] == r->drop_stream[0] && o->drop_stream[1] == r->drop_stream[1]));
-}
-}  // namespace
-
-extern "C" int satt_dec_mega_groups_variant(const satt_dec_mega_group* hb, int ngroups) {
-  if (!hb || ngroups < 1 || ngroups > SATT_MEGA_GROUPS_MAX) return -1;
-  for (int g = 0; g < ngroups; ++g)
-    if (hb[g].p.B != 2 || hb[g].b0 < 0 || satt_dec_mega_opt_variant(&hb[g].p, group_opt(hb[g])) < 0 || !groups_agree(hb[0], hb[g])) return -1;
-  return satt_dec_mega_opt_variant(&hb[0].p, group_opt(hb[0])) | SATT_MEGA_VAR_GROUPS;
-}
-
-extern "C" int satt_dec_mega_groups_supported(const satt_dec_mega_group* hb, int ngroups) { return satt_dec_mega_groups_variant(hb, ngroups) >= 0; }
-
-namespace {
-// what every group launch checks behind its variant: the device copy, every block's pointers, no stop rule, nothing shared
-int mega_check_groups(const satt_dec_mega_group* hb, const void* device_blocks, int ngroups) {
-  if (!device_blocks) return SATT_E_BADARG;
-  for (int g = 0; g < ngroups; ++g) {
-    if (const int rc = mega_check_block(hb[g].p, group_opt(hb[g]))) return rc;
-    if (hb[g].p.flag) return SATT_E_BADARG;          // no stop rule inside a group launch: satt_dec_stop_scan behind it
-    for (int h = 0; h < g; ++h)                      // exchanges, step words and state belong to ONE group
-      if (hb[h].p.part == hb[g].p.part || hb[h].p.step == hb[g].p.step || hb[h].p.ha == hb[g].p.ha) return SATT_E_BADARG;
-  }
-  return SATT_OK;
-}
-}  // namespace
-
-extern "C" int satt_dec_mega_groups(const satt_dec_mega_group* hb, const void* device_blocks, int ngroups, void* stream) {
-  const int var = satt_dec_mega_groups_variant(hb, ngroups);
-  if (var < 0) return SATT_E_UNSUPPORTED;
-  if (const int rc = mega_check_groups(hb, device_blocks, ngroups)) return rc;
-  const satt_dec_mega_params& p = hb[0].p;
-  const bool single = var & SATT_MEGA_VAR_SINGLE, lj = var & SATT_MEGA_VAR_LJ, spk = var & SATT_MEGA_VAR_SPEAKER;
-  const bool has_opt = var & (SATT_MEGA_VAR_AGENT | SATT_MEGA_VAR_DROPOUT);
-  const size_t smem = single ? mega2s_lds_bytes(2, p.Ti) : mega2_lds_bytes(2, p.Ti, has_opt);
-  if (smem > 160 * 1024) return SATT_E_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  MegaGrpP ga;                                       // (the block part is a place holder: every group reads its own from the array)
-  static_cast<satt_dec_mega_params&>(ga) = p;
-  ga.blocks = (const satt_dec_mega_group*)device_blocks; ga.ngroups = ngroups;
-#define SATT_MEGA2GO(LJV, SP) \
-  (has_opt ? mega_launch(dec_mega2_k<2, false, LJV, SP, true, true>, smem, s, ga, hb[0].o, MegaNoFrc()) : \
-             mega_launch(dec_mega2_k<2, false, LJV, SP, false, true>, smem, s, ga, MegaNoOpt(), MegaNoFrc()))
-#define SATT_MEGA2GL(SP) (lj ? SATT_MEGA2GO(true, SP) : SATT_MEGA2GO(false, SP))
-  if (single)
-    return spk ? mega_launch(dec_mega2_single_k<2, false, true, true>, smem, s, ga, MegaNoFrc()) : mega_launch(dec_mega2_single_k<2, false, false, true>, smem, s, ga, MegaNoFrc());
-  return spk ? SATT_MEGA2GL(true) : SATT_MEGA2GL(false);
-#undef SATT_MEGA2GO
-#undef SATT_MEGA2GL
-}
-
-// ---- forced alignments in group mode (GRP and FRC together: six instantiations, siblings of the generic-width group ones).  ONE
-// forced block for the whole launch: teach1 / teach2 are the batch's histories [2 ngroups][Td][Ti], group g reads rows b0, b0 + 1.
-extern "C" int satt_dec_mega_groups_forced_variant(const satt_dec_mega_group* hb, int ngroups, const satt_dec_mega_forced_params* f) {
-  const int var = satt_dec_mega_groups_variant(hb, ngroups);
-  if (!frc_on(f) || var < 0) return var;
-  if (var & SATT_MEGA_VAR_AGENT) return -1;          // the agent never runs under forced alignments (the blocks agree: one is all)
-  if (!(var & SATT_MEGA_VAR_SINGLE) && !f->teach2) return -1;
-  return (var & ~SATT_MEGA_VAR_LJ) | SATT_MEGA_VAR_FORCED;
-}
-
-extern "C" int satt_dec_mega_groups_forced(const satt_dec_mega_group* hb, const void* device_blocks, int ngroups,
-                                           const satt_dec_mega_forced_params* f, void* stream) {
-  if (!frc_on(f)) return satt_dec_mega_groups(hb, device_blocks, ngroups, stream);
-  const int gvar = satt_dec_mega_groups_variant(hb, ngroups);
-  if (gvar < 0 || (gvar & SATT_MEGA_VAR_AGENT)) return SATT_E_UNSUPPORTED;
-  const bool single = gvar & SATT_MEGA_VAR_SINGLE;
-  if (!single && !f->teach2) return SATT_E_BADARG;
-  if (const int rc = mega_check_groups(hb, device_blocks, ngroups)) return rc;
-  const int var = satt_dec_mega_groups_forced_variant(hb, ngroups, f);
-  if (var < 0) return SATT_E_UNSUPPORTED;
-  const satt_dec_mega_params& p = hb[0].p;
-  const bool spk = var & SATT_MEGA_VAR_SPEAKER, has_opt = var & SATT_MEGA_VAR_DROPOUT;
-  const size_t smem = single ? mega2s_lds_bytes(2, p.Ti) : mega2_lds_bytes(2, p.Ti, has_opt);
-  if (smem > 160 * 1024) return SATT_E_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  MegaGrpP ga;                                       // (the block part is a place holder, as in satt_dec_mega_groups)
-  static_cast<satt_dec_mega_params&>(ga) = p;
-  ga.blocks = (const satt_dec_mega_group*)device_blocks; ga.ngroups = ngroups;
-#define SATT_MEGA2GFO(SP) \
-  (has_opt ? mega_launch(dec_mega2_k<2, false, false, SP, true, true, true>, smem, s, ga, hb[0].o, *f) : \
-             mega_launch(dec_mega2_k<2, false, false, SP, false, true, true>, smem, s, ga, MegaNoOpt(), *f))
-  if (single)
-    return spk ? mega_launch(dec_mega2_single_k<2, false, true, true, true>, smem, s, ga, *f) : mega_launch(dec_mega2_single_k<2, false, false, true, true>, smem, s, ga, *f);
-  return spk ? SATT_MEGA2GFO(true) : SATT_MEGA2GFO(false);
-#undef SATT_MEGA2GFO
+// (ONE forced block for the whole group launch: teach1 / teach2 are the batch's histories [2 ngroups][Td][Ti], group g reads rows b0, b0 + 1)
+extern "C" int satt_dec_mega_groups_forced(const Grp* hb, const void* device_blocks, int ngroups, const Frc* f, void* stream) {
+  return mega_dispatch({hb, device_blocks, ngroups, f}, stream);
 }
 
 extern "C" int satt_dec_stop_scan(const float* yout, int B, int rows, int NO, int t0, int nsteps, int min_steps, float stop_threshold,

@@ -64,36 +64,24 @@ class DecodeSession:
         live_drop = c.apply_dropout_on_inference and c.dec_prenet_drop > 0
         dual_form = c.dual and bool(Ds) and c.dec_sa_num_hop == 1
         single_form = not c.dual and not Ds and (not c.transition_agent or mega_forced) and not live_drop
-        self._mega_single = False
+        # Batches of 3 .. MEGA_GROUPS_MAX_B take the same kernel in GROUP mode - one pair of samples per XCD, ceil(B / 2) independent
+        # B = 2 problems in one launch (include/satt_hip.h: satt_dec_mega_group) -, so the library decides on the B = 2 block of the
+        # model.  An odd batch is padded with a copy of its last sample (`Ba` rows are allocated, B returned).  A forced batch takes
+        # group mode too (satt_dec_mega_groups_forced: every group is the forced B = 2 launch of its pair).
+        groups = self.MEGA_GROUPS and 2 < B <= min(self.MEGA_GROUPS_MAX_B, 2 * ops.MEGA_GROUPS_MAX)
+        self._mega_single, self._groups = False, 0
         if (self.MEGA and use_graph and (not forced or mega_forced) and (dual_form or single_form) and len(c.dec_prenet) == 2 and
-                ops.get_precision() == "bf16" and B <= self.MEGA_MAX_B):
+                ops.get_precision() == "bf16" and (groups or B <= self.MEGA_MAX_B)):
             sh2 = dict(Ds=Ds, heads=c.dec_sa_heads, U2=U2, V2=V2) if dual_form else dict(Ds=0, heads=0, U2=0, V2=0)
-            shape = dict(B=B, Td=Td, Ti=Ti, A=A, D=D, U1=U1, V1=V1, **sh2, kernel=c.att_kernel,
+            shape = dict(B=2 if groups else B, Td=Td, Ti=Ti, A=A, D=D, U1=U1, V1=V1, **sh2, kernel=c.att_kernel,
                          filters=c.att_filters, att1_mode=int(c.attention == "location_sensitive"), cumulative=int(c.cumulative_weights),
                          P0=c.dec_prenet[0], P1=c.dec_prenet[1], feed=feed, NO=NO, ldout=(NO + 7) // 8 * 8, zc=c.zc, zh=c.zh,
                          stop_threshold=float(stop_threshold), min_steps=int(min_steps))
             if ops.dec_mega_supported(ops.dec_mega_params(**shape)):
                 self._mega_shape = shape
                 self._mega_single = not dual_form
-                self.K = max(self.K, self.MEGA_STEPS)
-        # Batches of 3 .. MEGA_GROUPS_MAX_B: the same kernel in GROUP mode - one pair of samples per XCD, ceil(B / 2) independent
-        # B = 2 problems in one launch (csrc/decode_mega2.hip, include/satt_hip.h: satt_dec_mega_group).  Decided by the library on
-        # the B = 2 block of the model.  An odd batch is padded with a copy of its last sample (`Ba` rows are allocated, B returned).
-        # A forced batch takes it too (satt_dec_mega_groups_forced: every group is the forced B = 2 launch of its pair), for the models
-        # the forced B <= 2 session takes, unless MEGA_FORCED is off.
-        self._groups = 0
-        if (self.MEGA and self.MEGA_GROUPS and use_graph and (not forced or mega_forced) and (dual_form or single_form) and len(c.dec_prenet) == 2 and
-                ops.get_precision() == "bf16" and 2 < B <= min(self.MEGA_GROUPS_MAX_B, 2 * ops.MEGA_GROUPS_MAX)):
-            sh2 = dict(Ds=Ds, heads=c.dec_sa_heads, U2=U2, V2=V2) if dual_form else dict(Ds=0, heads=0, U2=0, V2=0)
-            shape = dict(B=2, Td=Td, Ti=Ti, A=A, D=D, U1=U1, V1=V1, **sh2, kernel=c.att_kernel,
-                         filters=c.att_filters, att1_mode=int(c.attention == "location_sensitive"), cumulative=int(c.cumulative_weights),
-                         P0=c.dec_prenet[0], P1=c.dec_prenet[1], feed=feed, NO=NO, ldout=(NO + 7) // 8 * 8, zc=c.zc, zh=c.zh,
-                         stop_threshold=float(stop_threshold), min_steps=int(min_steps))
-            if ops.dec_mega_supported(ops.dec_mega_params(**shape)):
-                self._mega_shape = shape
-                self._mega_single = not dual_form
-                self._groups = (B + 1) // 2
-                self.K = max(self.K, self.MEGA_GROUPS_STEPS)
+                self._groups = (B + 1) // 2 if groups else 0
+                self.K = max(self.K, self.MEGA_GROUPS_STEPS if groups else self.MEGA_STEPS)
         Ba = self.Ba = 2 * self._groups if self._groups else B
         Tdp = self.Tdp = (Td + self.K - 1) // self.K * self.K          # whole graphs: rows past Td are scratch
         f32 = dict(dtype=torch.float32, device=dev)
