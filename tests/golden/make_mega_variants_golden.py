@@ -13,7 +13,7 @@ still tell a refusal of the shapes (SATT_E_UNSUPPORTED) from one of the pointers
 from the block's own check) shows which of the two a launcher looks at first.  No GPU is needed or touched.
 
 The grid:
-  blocks   the four shipped example configurations, PRODUCTION and LJ_KEYED (tests/test_decode_speaker_cpu.py), each with
+  blocks   the four shipped example configurations, PRODUCTION and LJ_KEYED (tests/decode_common.py), each with
            B in {1, 2, 3} x Ti in {1, 57, 112, 113, 256 (the largest), 257} x nsteps in {0, 8} x speaker term set / unset, plus eight
            single-field perturbations that make the block unsupported (B = 2, Ti = 57, nsteps = 8);
            per block: supported, variant, satt_dec_mega; per option block (OPTS): opt_variant, satt_dec_mega_opt; per option block
@@ -42,8 +42,7 @@ SHAPES = ["self-attention-tacotron/ljspeech", "self-attention-tacotron/vctk", "t
 
 @functools.lru_cache(None)
 def _shape(name):
-    from test_decode_groups_cpu import example_config, shape_of
-    from test_decode_speaker_cpu import LJ_KEYED, PRODUCTION
+    from decode_common import LJ_KEYED, PRODUCTION, example_config, shape_of
     if "/" not in name:
         return dict(PRODUCTION=PRODUCTION, LJ_KEYED=LJ_KEYED)[name]
     return shape_of(example_config(*name.split("/")))
@@ -61,18 +60,18 @@ def perturbations(s):
 
 def make_block(name, B, Ti, nsteps, speaker, change):
     from satt_amd import ops
-    from test_decode_groups_cpu import SPEAKER
+    from decode_common import SPEAKER
     return ops.dec_mega_params(B=B, Td=16, Ti=Ti, nsteps=nsteps, **(SPEAKER if speaker else {}), **dict(shape(name), **change))
 
 
 def make_opt(o):
-    from test_decode_groups_cpu import options
+    from decode_common import options
     return None if o is None else options(o in ("agent", "both"), o in ("dropout", "both"))
 
 
 def make_forced(f):
     from satt_amd import ops
-    from test_decode_groups_cpu import FAKE
+    from decode_common import FAKE
     return None if f is None else ops.dec_mega_forced_params(FAKE if f in ("teach1", "both") else None, FAKE + 64 if f in ("no_teach1", "both") else None)
 
 
@@ -97,7 +96,7 @@ def block_row(name, B, Ti, nsteps, speaker, change):
 def make_groups(name, case, nsteps, speaker, opt):
     """(host array or None, ngroups) of a group case"""
     from satt_amd import ops
-    from test_decode_groups_cpu import FAKE
+    from decode_common import FAKE
     n = dict(n1=1, n2=2, n8=8, n9=9, n0=9).get(case, 2)
     blocks = [make_block(name, 2, 57, nsteps, speaker, {}) for _ in range(n)]
     if case == "ti_disagree":
@@ -113,7 +112,7 @@ def make_groups(name, case, nsteps, speaker, opt):
 
 def group_row(name, case, nsteps, speaker):
     from satt_amd import _lib
-    from test_decode_groups_cpu import FAKE
+    from decode_common import FAKE
     L = _lib.lib()
     dev = C.c_void_p(FAKE)          # (never read: no block holds the pointers a launch needs)
     out = []

@@ -11,16 +11,7 @@ import subprocess
 import pytest
 
 import satt_amd  # noqa: F401
-from test_decode_options_cpu import FAKE, SPEAKER, options
-from test_decode_single_cpu import example_config, single_shape
-from test_decode_speaker_cpu import LJ_KEYED, PRODUCTION, medium_shape
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def forced(two=True):
-    from satt_amd import ops
-    return ops.dec_mega_forced_params(FAKE, FAKE + 64 if two else None)
+from decode_common import FAKE, LJ_KEYED, PRODUCTION, ROOT, SPEAKER, example_config, forced, medium_shape, options, shape_of
 
 
 def test_forced_block_layout_matches_c(tmp_path):
@@ -74,7 +65,7 @@ def test_forced_adds_its_bit_to_the_generic_variant(B, Ti, speaker, widths):
 @pytest.mark.parametrize("speaker", [False, True])
 def test_single_form_with_forced_alignments(example, speaker):
     from satt_amd import ops
-    shape = single_shape(example_config(example))
+    shape = shape_of(example_config(example))
     for B, Ti in ((1, 33), (1, 113), (2, 57)):
         p = ops.dec_mega_params(B=B, Td=16, Ti=Ti, **(SPEAKER if speaker else {}), **shape)
         plain = ops.dec_mega_variant(p)

@@ -15,17 +15,16 @@ TEST 1 FAILS ON THE PARENT (a forced session never takes the kernel there: `ses.
 the path through run().
 Bar: 2e-5 relative to the largest element, the bar of tests/test_decode_speaker_gpu.py for exactly this comparison (same bf16
 weights, same buffers, fp32 sums in another order, fed back through the steps)."""
-import numpy as np
 import pytest
 import torch
 
-from common import make_params, rel_err, small_batch
+from common import rel_err
+from decode_common import (BAR, BASELINE, Engines, expected_variant, history_is_as_given, host_outputs, infer_kwargs, inputs, same, switches,
+                           teacher_rows, traced_infer)
 
 pytestmark = pytest.mark.gpu
 
-BAR = 2e-5
 STEPS = 19
-BASELINE = dict(sa_units=0, att2_units=0, dec_sa_units=0, att1_units=256)
 SPK = dict(num_speakers=4, speaker_dim=16, speaker_offset=225)
 MODELS = {
     "dual": dict(),
@@ -40,105 +39,41 @@ FORMS = {"tables": (8, True), "nofold": (8, False), "long": (32, True)}         
 IDS = {1: (226,), 2: (225, 227)}
 B2 = "B=2 Ti=57"
 
-_engines, _runs = {}, {}
+engine = Engines(MODELS, stats=True)
+_runs = {}
 
 
-def engine(model, stop=False):
-    """one bf16 engine per (model, stop-logit bias), shared by the tests of this file (sessions are cached on it)"""
-    from satt_amd import ops
-    from satt_amd.engine import Engine
-    key = (model, stop)
-    if key not in _engines:
-        cfg, P = make_params(MODELS[model], seed=4)
-        P = dict(P)
-        if cfg.num_speakers:
-            P["speaker_embedding"] = np.random.default_rng(9).normal(0, 0.5, P["speaker_embedding"].shape).astype(np.float32)
-        if stop:
-            b = np.array(P["dec.out.b"], dtype=np.float32).copy(); b[-1] = 50.0          # stop logit always large
-            P["dec.out.b"] = b
-        ops.set_precision("bf16")
-        eng = Engine(cfg, "cuda", params=P, rng_seed=7)
-        g = np.random.default_rng(11)
-        mv = {}
-        for name, (mean, var) in eng.bn.items():        # non-trivial moving statistics, shared with the oracle
-            m = g.normal(0, 0.2, mean.shape[0]).astype(np.float32); v = g.uniform(0.5, 1.5, var.shape[0]).astype(np.float32)
-            mean.copy_(torch.as_tensor(m)); var.copy_(torch.as_tensor(v))
-            mv[name] = (torch.as_tensor(m, dtype=torch.float64), torch.as_tensor(v, dtype=torch.float64))
-        _engines[key] = (eng, cfg, P, mv)
-    ops.set_precision("bf16")
-    return _engines[key]
-
-
-def inputs(cfg, shape):
+def inputs_of(cfg, shape):
     """source, lengths (the shape's own: B = 2 has (57, 41)) and the target frames of `shape`"""
     B, Ti, lens = SHAPES[shape]
-    batch = small_batch(cfg, B, Ti, STEPS * cfg.r, seed=6)
-    sl = np.array(lens, np.int64)
-    src = np.array(batch["source"]).copy()
-    src[np.arange(Ti)[None, :] >= sl[:, None]] = 0
-    return torch.as_tensor(src), torch.as_tensor(sl), torch.as_tensor(batch["mel"])
+    return inputs(cfg, B, Ti, STEPS, lens)
 
 
-def teacher_rows(shape, dual, masked=True, seed=3):
-    """random row-normalised alignments (tests/test_inference_gpu.py test_forced_alignment_mode); masked=False: mass beyond the lengths"""
+def rows_of(shape, dual, **kw):
+    """the teacher rows of `shape` (masked=False: mass beyond the lengths)"""
     B, Ti, lens = SHAPES[shape]
-    g = torch.Generator().manual_seed(seed)
-    mask = (torch.arange(Ti)[None, None, :] < torch.as_tensor(lens)[:, None, None]).double()
-    ta = []
-    for _ in range(2 if dual else 1):
-        a = torch.rand(B, STEPS, Ti, generator=g, dtype=torch.float64)
-        if masked:
-            a = a * mask
-        ta.append((a / a.sum(-1, keepdim=True)).float())
-    return (ta[0], ta[1] if dual else None)
+    return teacher_rows(B, STEPS, Ti, lens, dual, **kw)
 
 
 def run(model, shape, mega, form="tables", mode="free", ta=None, tag="masked", poison=None, fresh=False, forced_switch=True):
     """one forced utterance; returns (outputs on the host, the session, the set of variants the persistent kernel was launched with).
     Results are computed once per key and shared (fresh=True: computed again).  The launch-per-layer result does not depend on the form."""
-    from satt_amd import _lib, ops
-    from satt_amd.inference import infer, DecodeSession
     key = (model, shape, mega, form if mega else None, mode, tag, poison, forced_switch)
     if key in _runs and not fresh:
         return _runs[key]
     eng, cfg, _, _ = engine(model, stop=(mode == "stop"))
     B = SHAPES[shape][0]
-    src, sl, mel = inputs(cfg, shape)
+    src, sl, mel = inputs_of(cfg, shape)
     if ta is None:
-        ta = teacher_rows(shape, cfg.dual)
-    kw = dict(teacher=mel) if mode == "teacher" else dict(max_steps=STEPS, min_steps=(5 if mode == "stop" else 10 ** 6))
-    if cfg.num_speakers:
-        kw["speaker_id"] = torch.as_tensor(np.array(IDS[B], np.int64))
-    if cfg.apply_dropout_on_inference:
-        kw["dropout_seed"] = 1234          # the same masks on both paths
-    real = (ops.dec_mega, ops.dec_mega_opt, ops.dec_mega_forced)
-    launched, others, used = set(), [], []
-    tables = DecodeSession.build_context_tables          # (infer() calls it on the session it uses, cached or new)
-
-    def recording(p, o, f, n):          # (inference.py calls ops.dec_mega_forced through the module attribute)
-        if poison is not None:          # the pattern in every LDS word of every CU in front of EVERY launch of the persistent kernel
-            _lib.check(_lib.lib().satt_debug_poison_lds(poison, 100, ops.current_stream().cuda_stream), "poison_lds")
-        launched.add(ops.dec_mega_forced_variant(p, o, f))
-        return real[2](p, o, f, n)
-    saved = (DecodeSession.MEGA, DecodeSession.MEGA_STEPS, DecodeSession.MEGA_FOLD_FEEDBACK, DecodeSession.MEGA_FORCED)
-    try:
-        DecodeSession.MEGA, DecodeSession.MEGA_FORCED = mega, forced_switch
-        DecodeSession.MEGA_STEPS, DecodeSession.MEGA_FOLD_FEEDBACK = FORMS[form]
-        ops.dec_mega_forced = recording
-        DecodeSession.build_context_tables = lambda self: (used.append(self), tables(self))[1]
-        ops.dec_mega = lambda *a: others.append("dec_mega") or real[0](*a)
-        ops.dec_mega_opt = lambda *a: others.append("dec_mega_opt") or real[1](*a)
-        out = infer(eng, src, sl, teacher_alignments=ta, **kw)
-        ses, = used
-    finally:
-        DecodeSession.build_context_tables = tables
-        ops.dec_mega, ops.dec_mega_opt, ops.dec_mega_forced = real
-        DecodeSession.MEGA, DecodeSession.MEGA_STEPS, DecodeSession.MEGA_FOLD_FEEDBACK, DecodeSession.MEGA_FORCED = saved
+        ta = rows_of(shape, cfg.dual)
+    kw = infer_kwargs(mode, STEPS, mel, IDS[B] if cfg.num_speakers else None,
+                      1234 if cfg.apply_dropout_on_inference else None)          # the same masks on both paths
+    K, fold = FORMS[form]
+    out, ses, launches = traced_infer(eng, src, sl, dict(MEGA=mega, MEGA_FORCED=forced_switch, MEGA_STEPS=K, MEGA_FOLD_FEEDBACK=fold),
+                                      poison, teacher_alignments=ta, **kw)
+    others = [l.name for l in launches if l.name != "dec_mega_forced"]
     assert not others, others          # a forced session launches through ops.dec_mega_forced only
-    res = {k: out[k].detach().cpu() for k in ("mel", "stop", "alignment1")}
-    res["alignment2"] = out["alignment2"].detach().cpu() if out["alignment2"] is not None else None
-    res["steps"] = out["steps"]
-    _runs[key] = (res, ses, launched)
+    _runs[key] = (host_outputs(out), ses, {l.variant for l in launches})
     return _runs[key]
 
 
@@ -152,28 +87,9 @@ def took_the_forced_kernel(ses, launched, model, shape, form="tables", mode="fre
     drop = cfg.apply_dropout_on_inference and cfg.dual
     assert (ses.mega_opt is not None) == bool(drop)
     assert (ses._fb is not None) == (FORMS[form][1] and mode != "teacher")
-    want = ops.MEGA_VAR_FORCED | (ops.MEGA_VAR_TABLES_LDS if (B == 1 and Ti <= 112) else 0) | (ops.MEGA_VAR_TWO_SAMPLES if B == 2 else 0) | \
-        (0 if cfg.dual else ops.MEGA_VAR_SINGLE) | (ops.MEGA_VAR_SPEAKER if cfg.num_speakers else 0) | (ops.MEGA_VAR_DROPOUT if drop else 0)
+    want = expected_variant(cfg, B, Ti, forced=True)
     assert launched == {want}, (launched, want)          # every launch carried MEGA_VAR_FORCED, none MEGA_VAR_LJ (no such sibling)
     assert ops.dec_mega_forced_variant(ses.mega, ses.mega_opt, ses.mega_forced) == want
-
-
-def same(new, old, what, keys=("mel", "stop")):
-    assert new["steps"] == old["steps"], (what, new["steps"], old["steps"])
-    for k in keys:
-        e = rel_err(new[k].numpy(), old[k].numpy())
-        print("%s %-10s rel_err=%.3e (bar %.0e)" % (what, k, e, BAR))
-        assert e < BAR, (what, k, e)
-    assert torch.isfinite(new["mel"]).all()
-
-
-def history_is_as_given(res, ta):
-    n = res["steps"]
-    assert torch.equal(res["alignment1"], ta[0][:, :n]), "alignment1 is not bit-equal to the rows given"
-    if ta[1] is not None:
-        assert torch.equal(res["alignment2"], ta[1][:, :n]), "alignment2 is not bit-equal to the rows given"
-    else:
-        assert res["alignment2"] is None
 
 
 # ---- 1: the path taken
@@ -200,7 +116,7 @@ def test_forced_persistent_equals_the_launch_per_layer_path(model, form, shape):
     assert ses_old.mega is None and not none
     assert new["steps"] == STEPS
     same(new, old, "%s %s %s" % (model, form, shape))
-    ta = teacher_rows(shape, engine(model)[1].dual)
+    ta = rows_of(shape, engine(model)[1].dual)
     history_is_as_given(new, ta)
     history_is_as_given(old, ta)
 
@@ -216,7 +132,7 @@ def test_teacher_feeding_and_the_stop_rule_under_forced_alignments(model, mode):
     assert ses_old.mega is None and not none
     assert new["steps"] == (7 if mode == "stop" else STEPS)
     same(new, old, "%s %s" % (model, mode))
-    history_is_as_given(new, teacher_rows(B2, engine(model)[1].dual))
+    history_is_as_given(new, rows_of(B2, engine(model)[1].dual))
 
 
 # ---- 3: masking
@@ -224,7 +140,7 @@ def test_teacher_feeding_and_the_stop_rule_under_forced_alignments(model, mode):
 def test_rows_are_masked_in_the_products_and_not_in_the_history(model):
     """lengths (57, 41) and teacher rows with mass BEYOND row 41 of sample 1: the contexts weight row r with r < length ? a[r] : 0
     (csrc/decode.hip dec_attn_context_k), the histories show the rows as given"""
-    ta = teacher_rows(B2, engine(model)[1].dual, masked=False)
+    ta = rows_of(B2, engine(model)[1].dual, masked=False)
     assert float(ta[0][1, :, 41:].sum()) > 1.0
     new, ses, launched = run(model, B2, True, "tables", ta=ta, tag="unmasked")
     took_the_forced_kernel(ses, launched, model, B2)
@@ -240,7 +156,7 @@ def test_teacher_rows_are_live_and_belong_to_their_sample(form):
     """the two samples' teacher rows swapped ON THE CACHED SESSION (the rows are rewritten in place, no pointer changes): the result
     equals the launch-per-layer result for the swapped rows and differs from the first run by more than 100 bars; the first input
     again gives the first run's bits"""
-    ta = teacher_rows(B2, True)
+    ta = rows_of(B2, True)
     sw = (ta[0].flip(0).contiguous(), ta[1].flip(0).contiguous())
     first, ses, launched = run("dual", B2, True, form, fresh=True)
     took_the_forced_kernel(ses, launched, "dual", B2, form)
@@ -261,15 +177,11 @@ def test_teacher_rows_are_live_and_belong_to_their_sample(form):
 # ---- 5: self-consistency
 @pytest.mark.parametrize("model", ["dual", "baseline"])
 def test_a_free_run_fed_its_own_alignments_reproduces_itself(model):
-    from satt_amd.inference import infer, DecodeSession
+    from satt_amd.inference import infer
     eng, cfg, _, _ = engine(model)
-    src, sl, _ = inputs(cfg, B2)
-    saved = DecodeSession.MEGA_STEPS
-    try:
-        DecodeSession.MEGA_STEPS = 8
+    src, sl, _ = inputs_of(cfg, B2)
+    with switches(MEGA_STEPS=8):
         free = infer(eng, src, sl, max_steps=STEPS, min_steps=10 ** 6)
-    finally:
-        DecodeSession.MEGA_STEPS = saved
     ta = (free["alignment1"].cpu(), free["alignment2"].cpu() if cfg.dual else None)
     again, ses, launched = run(model, B2, True, "tables", ta=ta, tag="own", fresh=True)
     took_the_forced_kernel(ses, launched, model, B2)
@@ -296,7 +208,7 @@ def test_forced_kernel_hands_over_to_the_launch_per_layer_path(model):
     mixed = {"mel": y[:, :, :NO - 1].reshape(old["mel"].shape), "stop": y[:, :, NO - 1:], "steps": STEPS,
              "alignment1": ses.al1[:, :STEPS].cpu(), "alignment2": ses.al2[:, :STEPS].cpu() if ses.al2 is not None else None}
     same(mixed, old, model + " 8 steps persistent + 11 launch per layer")
-    history_is_as_given(mixed, teacher_rows(B2, engine(model)[1].dual))
+    history_is_as_given(mixed, rows_of(B2, engine(model)[1].dual))
 
 
 # ---- 7: float64 oracle
@@ -306,8 +218,8 @@ def test_forced_persistent_path_is_as_close_to_the_float64_oracle_as_the_launch_
     persistent path may be at most twice as far (tests/test_decode_speaker_gpu.py)."""
     from oracle import torch_ref
     eng, cfg, P, mv = engine("dual")
-    src, sl, _ = inputs(cfg, B2)
-    ta = teacher_rows(B2, True)
+    src, sl, _ = inputs_of(cfg, B2)
+    ta = rows_of(B2, True)
     ref = torch_ref.infer(torch_ref.to_torch(P), src, sl, torch_ref.Cfg(), STEPS, mv, min_steps=10 ** 6,
                           teacher_alignments=[a.double() for a in ta])
     new, ses, launched = run("dual", B2, True)

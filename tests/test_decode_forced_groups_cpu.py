@@ -10,16 +10,9 @@ import subprocess
 import pytest
 
 import satt_amd  # noqa: F401
-from test_decode_groups_cpu import FAKE, FAMILIES, block, example_config, groups, options
-from test_decode_speaker_cpu import LJ_KEYED, PRODUCTION
+from decode_common import FAKE, FAMILIES, LJ_KEYED, PRODUCTION, ROOT, block, example_config, forced, groups, options
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_BADARG, E_UNSUPPORTED = -1, -2          # include/satt_hip.h: SATT_E_BADARG, SATT_E_UNSUPPORTED
-
-
-def forced(two=True):
-    from satt_amd import ops
-    return ops.dec_mega_forced_params(FAKE, FAKE + 64 if two else None)
 
 
 def keyed(shape, n=2, opt=None, **kw):

@@ -21,14 +21,14 @@ import numpy as np
 import pytest
 import torch
 
-from common import make_params, rel_err, small_batch
+from common import rel_err
+from decode_common import (BAR, BASELINE, Engines, expected_variant, history_is_as_given, host_outputs, infer_kwargs, inputs, keys_of,
+                           recording, same, sessions_used, switches, teacher_rows, traced_infer)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BAR = 2e-5
 K = 8                                          # steps per launch
-BASELINE = dict(sa_units=0, att2_units=0, dec_sa_units=0, att1_units=256)
 SPK = dict(num_speakers=7, speaker_dim=16, speaker_offset=225)
 MODELS = {
     "dual": dict(),
@@ -42,65 +42,13 @@ MODELS = {
 }
 SIX = (225, 230, 226, 229, 227, 228)          # six DIFFERENT speakers in the six rows
 
-_engines, _runs = {}, {}
-
-
-def engine(model, stop=False):
-    """one bf16 engine per (model, stop-logit bias), shared by the tests of this file (sessions are cached on it); non-trivial
-    moving statistics, shared with the oracle"""
-    from satt_amd import ops
-    from satt_amd.engine import Engine
-    key = (model, stop)
-    if key not in _engines:
-        cfg, P = make_params(MODELS[model], seed=4)
-        P = dict(P)
-        if cfg.num_speakers:
-            P["speaker_embedding"] = np.random.default_rng(9).normal(0, 0.5, P["speaker_embedding"].shape).astype(np.float32)
-        if stop:
-            b = np.array(P["dec.out.b"], dtype=np.float32).copy(); b[-1] = 50.0          # stop logit always large
-            P["dec.out.b"] = b
-        ops.set_precision("bf16")
-        eng = Engine(cfg, "cuda", params=P, rng_seed=7)
-        g = np.random.default_rng(11)
-        mv = {}
-        for name, (mean, var) in eng.bn.items():
-            m = g.normal(0, 0.2, mean.shape[0]).astype(np.float32); v = g.uniform(0.5, 1.5, var.shape[0]).astype(np.float32)
-            mean.copy_(torch.as_tensor(m)); var.copy_(torch.as_tensor(v))
-            mv[name] = (torch.as_tensor(m, dtype=torch.float64), torch.as_tensor(v, dtype=torch.float64))
-        _engines[key] = (eng, cfg, P, mv)
-    ops.set_precision("bf16")
-    return _engines[key]
-
-
-def inputs(cfg, B, Ti, steps, lens=None):
-    """source, lengths (the batch's own ragged ones unless given) and the target frames"""
-    batch = small_batch(cfg, B, Ti, steps * cfg.r, seed=6)
-    sl = np.array(batch["source_length"] if lens is None else lens, np.int64)
-    src = np.array(batch["source"]).copy()
-    src[np.arange(Ti)[None, :] >= sl[:, None]] = 0
-    return torch.as_tensor(src), torch.as_tensor(sl), torch.as_tensor(batch["mel"])
-
-
-def teacher_rows(B, steps, Ti, lens, dual, masked=True, seed=3, sharp=1):
-    """random row-normalised alignments (tests/test_decode_forced_gpu.py); masked=False: mass beyond the lengths; sharp > 1: the
-    uniform draws raised to that power before the normalisation - rows with a few large entries, whose contexts differ from row to
-    row (the contexts of flat rows over one memory are all close to the memory's mean)"""
-    g = torch.Generator().manual_seed(seed)
-    mask = (torch.arange(Ti)[None, None, :] < torch.as_tensor(lens)[:, None, None]).double()
-    ta = []
-    for _ in range(2 if dual else 1):
-        a = torch.rand(B, steps, Ti, generator=g, dtype=torch.float64) ** sharp
-        if masked:
-            a = a * mask
-        ta.append((a / a.sum(-1, keepdim=True)).float())
-    return (ta[0], ta[1] if dual else None)
+engine = Engines(MODELS, stats=True)
+_runs = {}
 
 
 def run(model, B, Ti, steps, mega=True, mode="free", lens=None, ta=None, tag="masked", poison=None, fresh=False, switches=None):
     """one forced utterance; returns (outputs on the host, the session, the recorded forced group launches (variant, groups, nsteps)).
     mega=False: DecodeSession.MEGA = False, the hipGraph of launch-per-layer steps.  Results are computed once per key and shared."""
-    from satt_amd import _lib, ops
-    from satt_amd.inference import infer, DecodeSession
     key = (model, B, Ti, steps, mega, mode, None if lens is None else tuple(lens), tag, poison, None if switches is None else tuple(sorted(switches.items())))
     if key in _runs and not fresh:
         return _runs[key]
@@ -108,46 +56,13 @@ def run(model, B, Ti, steps, mega=True, mode="free", lens=None, ta=None, tag="ma
     src, sl, mel = inputs(cfg, B, Ti, steps, lens)
     if ta is None:
         ta = teacher_rows(B, steps, Ti, sl, cfg.dual)
-    kw = dict(teacher=mel) if mode == "teacher" else dict(max_steps=steps, min_steps=(5 if mode == "stop" else 10 ** 6))
-    if cfg.num_speakers:
-        kw["speaker_id"] = torch.as_tensor(np.array([SIX[b % 6] for b in range(B)], np.int64))
-    if cfg.apply_dropout_on_inference:
-        kw["dropout_seed"] = 1234          # the same masks on both paths
-    names = ("dec_mega", "dec_mega_opt", "dec_mega_forced", "dec_mega_groups", "dec_mega_groups_forced")
-    real = {n: getattr(ops, n) for n in names}
-    launched, others, used = [], [], []
-    tables = DecodeSession.build_context_tables          # (infer() calls it on the session it uses, cached or new)
-
-    def recording(arr, dev, f):          # (inference.py calls ops.dec_mega_groups_forced through the module attribute)
-        if poison is not None:          # the pattern in every LDS word of every CU in front of EVERY launch
-            _lib.check(_lib.lib().satt_debug_poison_lds(poison, 100, ops.current_stream().cuda_stream), "poison_lds")
-        launched.append((ops.dec_mega_groups_forced_variant(arr, f), len(arr), arr[0].p.nsteps))
-        return real["dec_mega_groups_forced"](arr, dev, f)
-
-    def other(name):
-        return lambda *a: others.append(name) or real[name](*a)
-    sw = dict(MEGA=mega, MEGA_STEPS=K, MEGA_GROUPS_STEPS=K, **(switches or {}))
-    saved = {k: getattr(DecodeSession, k) for k in sw}
-    try:
-        for k, v in sw.items():
-            setattr(DecodeSession, k, v)
-        for n in names[:4]:
-            setattr(ops, n, other(n))
-        ops.dec_mega_groups_forced = recording
-        DecodeSession.build_context_tables = lambda self: (used.append(self), tables(self))[1]
-        out = infer(eng, src, sl, teacher_alignments=ta, **kw)
-        ses, = used
-    finally:
-        DecodeSession.build_context_tables = tables
-        for n in names:
-            setattr(ops, n, real[n])
-        for k, v in saved.items():
-            setattr(DecodeSession, k, v)
+    kw = infer_kwargs(mode, steps, mel, [SIX[b % 6] for b in range(B)] if cfg.num_speakers else None,
+                      1234 if cfg.apply_dropout_on_inference else None)          # the same masks on both paths
+    out, ses, launches = traced_infer(eng, src, sl, dict(MEGA=mega, MEGA_STEPS=K, MEGA_GROUPS_STEPS=K, **(switches or {})), poison,
+                                      teacher_alignments=ta, **kw)
+    others = [l.name for l in launches if l.name != "dec_mega_groups_forced"]
     assert B <= 2 or not others, others          # a forced group session launches through ops.dec_mega_groups_forced only
-    res = {k: out[k].detach().cpu() for k in ("mel", "stop", "alignment1")}
-    res["alignment2"] = out["alignment2"].detach().cpu() if out["alignment2"] is not None else None
-    res["steps"] = out["steps"]
-    _runs[key] = (res, ses, launched)
+    _runs[key] = (host_outputs(out), ses, [l[1:] for l in launches if l.name == "dec_mega_groups_forced"])
     return _runs[key]
 
 
@@ -160,33 +75,9 @@ def took_forced_groups(ses, launched, model, B):
     assert len(ses.mega_groups) == (B + 1) // 2 and ses.Ba == 2 * ((B + 1) // 2)
     assert ses.agent_tab is None and ses.u_state is None          # the agent is dead under forced alignments
     assert ses.teach1._base.shape[0] == ses.Ba and ses.teach1.shape[0] == B
-    drop = cfg.apply_dropout_on_inference and cfg.dual
-    want = ops.MEGA_VAR_FORCED | ops.MEGA_VAR_GROUPS | ops.MEGA_VAR_TWO_SAMPLES | (0 if cfg.dual else ops.MEGA_VAR_SINGLE) | \
-        (ops.MEGA_VAR_SPEAKER if cfg.num_speakers else 0) | (ops.MEGA_VAR_DROPOUT if drop else 0)
+    want = expected_variant(cfg, B, ses.Ti, forced=True, groups=True)
     assert ops.dec_mega_groups_forced_variant(ses.mega_groups, ses.mega_forced) == want
     assert launched and {v for v, _, _ in launched} == {want} and {n for _, n, _ in launched} == {(B + 1) // 2}, (launched, want)
-
-
-def keys_of(cfg):
-    return ("mel", "stop", "alignment1") + (("alignment2",) if cfg.dual else ())
-
-
-def same(new, old, what, keys=("mel", "stop")):
-    assert new["steps"] == old["steps"], (what, new["steps"], old["steps"])
-    for k in keys:
-        e = rel_err(new[k].numpy(), old[k].numpy())
-        print("%s %-10s rel_err=%.3e (bar %.0e)" % (what, k, e, BAR))
-        assert e < BAR, (what, k, e)
-    assert torch.isfinite(new["mel"]).all()
-
-
-def history_is_as_given(res, ta):
-    n = res["steps"]
-    assert torch.equal(res["alignment1"], ta[0][:, :n]), "alignment1 is not bit-equal to the rows given"
-    if ta[1] is not None:
-        assert torch.equal(res["alignment2"], ta[1][:, :n]), "alignment2 is not bit-equal to the rows given"
-    else:
-        assert res["alignment2"] is None
 
 
 def compare(model, B, Ti, steps, mode="free", lens=None, want_steps=None):
@@ -318,16 +209,12 @@ def test_a_forced_group_computes_what_the_forced_two_sample_launch_computes():
 # ---- 6: self-consistency
 @pytest.mark.parametrize("model", ["dual", "baseline"])
 def test_a_free_run_fed_its_own_alignments_reproduces_itself(model):
-    from satt_amd.inference import infer, DecodeSession
+    from satt_amd.inference import infer
     B, Ti, steps = 6, 57, 19
     eng, cfg, _, _ = engine(model)
     src, sl, _ = inputs(cfg, B, Ti, steps)
-    saved = DecodeSession.MEGA_GROUPS_STEPS
-    try:
-        DecodeSession.MEGA_GROUPS_STEPS = K
+    with switches(MEGA_GROUPS_STEPS=K):
         free = infer(eng, src, sl, max_steps=steps, min_steps=10 ** 6)
-    finally:
-        DecodeSession.MEGA_GROUPS_STEPS = saved
     ta = (free["alignment1"].cpu(), free["alignment2"].cpu() if cfg.dual else None)
     again, ses, launched = run(model, B, Ti, steps, True, ta=ta, tag="own", fresh=True)
     took_forced_groups(ses, launched, model, B)
@@ -382,23 +269,15 @@ def test_the_switches_return_a_forced_batch_to_the_launch_per_layer_path(switch)
 
 
 def test_a_free_running_batch_still_launches_through_the_group_entry_point():
-    from satt_amd import ops
     from satt_amd.inference import infer
     eng, cfg, _, _ = engine("dual")
     src, sl, _ = inputs(cfg, 4, 33, 9)
-    from satt_amd.inference import DecodeSession
-    real, calls, used = ops.dec_mega_groups, [], []
-    real_forced, tables = ops.dec_mega_groups_forced, DecodeSession.build_context_tables
-    try:
-        ops.dec_mega_groups = lambda *a: calls.append("groups") or real(*a)
-        ops.dec_mega_groups_forced = lambda *a: calls.append("forced") or real_forced(*a)
-        DecodeSession.build_context_tables = lambda self: (used.append(self), tables(self))[1]
+    with recording() as launches, sessions_used() as used:
         out = infer(eng, src, sl, max_steps=9, min_steps=10 ** 6)
-    finally:
-        ops.dec_mega_groups, ops.dec_mega_groups_forced, DecodeSession.build_context_tables = real, real_forced, tables
     ses, = used
     assert ses.mega_groups is not None and ses.mega_forced is None and out["steps"] == 9
-    assert calls and set(calls) == {"groups"}
+    calls = [l.name for l in launches]
+    assert calls and set(calls) == {"dec_mega_groups"}
 
 
 # ---- 10: the driver
@@ -459,22 +338,13 @@ def corpus(tmp_path_factory):
 
 def predict(corpus, name, forced, extra=(), mega=True):
     """predict_mel.main in process; returns (output directory, the recorded forced group launches)"""
-    from satt_amd import ops
-    from satt_amd.inference import DecodeSession
     import predict_mel
     tmp, keys, common = corpus
     out = tmp / name
     out.mkdir()
-    real, launched = ops.dec_mega_groups_forced, []
-    saved = DecodeSession.MEGA
-    try:
-        DecodeSession.MEGA = mega
-        ops.dec_mega_groups_forced = lambda arr, dev, f: launched.append((ops.dec_mega_groups_forced_variant(arr, f), len(arr))) or real(arr, dev, f)
+    with switches(MEGA=mega), recording() as launches:
         predict_mel.main(["--output-dir", str(out), "--hparams", "use_forced_alignment_mode=%s" % forced] + common + list(extra))
-    finally:
-        ops.dec_mega_groups_forced = real
-        DecodeSession.MEGA = saved
-    return out, launched
+    return out, [(l.variant, l.groups) for l in launches if l.name == "dec_mega_groups_forced"]
 
 
 def prepared(T, r=2):

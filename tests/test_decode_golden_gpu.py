@@ -12,16 +12,13 @@ import numpy as np
 import pytest
 import torch
 
+from decode_common import GOLDEN_BARS as BARS, golden_engine, last_session, switches
+
 pytestmark = pytest.mark.gpu
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
-# (mel abs, stop abs, alignment rows abs, per-step mean |mel| abs, argmax path agreement)
-# measured (MI355X, r5): bf16 mel 7.4e-4 (the float64 oracle with bf16-rounded weights: 7.7e-4 - the path sits AT the rounding floor
-# of its weights), stop 1.5e-4, alignment rows 4.0e-4, drift 2.5e-5, path 0.995; f32 mode (recurrent weights are consumed as bf16 in
-# both modes): mel 2.0e-4, stop 2.3e-5, alignment rows 8.0e-5, drift 1.1e-5, path 1.000
-BARS = {"bf16": dict(mel=2.2e-3, stop=4.5e-4, align=1.2e-3, drift=8e-5, path=0.985),
-        "f32": dict(mel=6e-4, stop=7e-5, align=2.5e-4, drift=3.5e-5, path=0.995)}
+# (mel abs, stop abs, alignment rows abs, per-step mean |mel| abs, argmax path agreement): BARS are decode_common.GOLDEN_BARS, ~3x measured
 # *_sharp (r6): alignment 1 near one-hot through the 200-step feedback chain (make_decode_golden.py); a row moves by a whole position
 # where two neighbouring energies are close, so the alignment / path distances are judged against the oracle's OWN bf16-weight floor
 # stored in the fixture; bars ~3x measured (profiles/r06_decode_golden.log)
@@ -31,27 +28,6 @@ BARS_SHARP = {"bf16": dict(mel=2.2e-3, stop=4.5e-4, align=5e-2, drift=8e-5, path
               "f32": dict(mel=6e-4, stop=7e-5, align=4.5e-3, drift=3.5e-5, path=0.995)}
 
 
-def _engine(z, prec, stop_shift=0.0, case=""):
-    from satt_amd import ops
-    from satt_amd.engine import Engine
-    from satt_amd.params import ModelConfig, init_params
-    cfg = ModelConfig()
-    P = dict(init_params(cfg, int(z["param_seed"])))
-    if case.endswith("_sharp"):
-        from golden.make_bench_golden import sharpen_params
-        from golden.make_decode_golden import CASES
-        P = sharpen_params(P, **CASES[case]["sharpen"])
-    if stop_shift:
-        b = np.array(P["dec.out.b"], dtype=np.float32).copy()
-        b[-1] += np.float32(stop_shift)
-        P["dec.out.b"] = b
-    ops.set_precision(prec)
-    eng = Engine(cfg, "cuda", params=P, rng_seed=7)
-    for name, (mean, var) in eng.bn.items():
-        mean.copy_(torch.as_tensor(z["bn_mean." + name])); var.copy_(torch.as_tensor(z["bn_var." + name]))
-    return cfg, eng
-
-
 @pytest.mark.parametrize("path", ["persistent", "graph"])
 @pytest.mark.parametrize("prec", ["bf16", "f32"])
 @pytest.mark.parametrize("case", ["b1", "b8", "b2", "b1_sharp", "b2_sharp"])
@@ -59,21 +35,20 @@ def test_graph_decode_vs_frozen_float64_oracle(case, prec, path):
     """path: the persistent step kernel (csrc/decode_mega2.hip: bf16, B <= 2 - the benchmark's path) or the hipGraph of
     launch-per-layer steps (every other configuration, and the reference point of the persistent kernel)"""
     from satt_amd import ops
-    from satt_amd.inference import infer, DecodeSession
+    from satt_amd.inference import infer
     z = np.load(os.path.join(GOLD, "decode_ljspeech_%s.npz" % case))
     steps = int(z["steps"])
     try:
-        DecodeSession.MEGA = path == "persistent"
-        cfg, eng = _engine(z, prec, case=case)
-        out = infer(eng, z["source"], z["source_length"], max_steps=steps, min_steps=10 ** 6, use_graph=True)
-        torch.cuda.synchronize()
-        took = eng._decode_sessions[next(reversed(eng._decode_sessions))].mega is not None
-        if path == "persistent" and not took:
-            pytest.skip("the persistent kernel does not take this case (precision / batch size)")
-        assert took == (path == "persistent")
+        with switches(MEGA=path == "persistent"):
+            cfg, eng = golden_engine(z, prec, case=case)
+            out = infer(eng, z["source"], z["source_length"], max_steps=steps, min_steps=10 ** 6, use_graph=True)
+            torch.cuda.synchronize()
+            took = last_session(eng).mega is not None          # (a new engine: the session is new)
+            if path == "persistent" and not took:
+                pytest.skip("the persistent kernel does not take this case (precision / batch size)")
+            assert took == (path == "persistent")
     finally:
         ops.set_precision("bf16")
-        DecodeSession.MEGA = True
     assert out["steps"] == steps
     B = z["source"].shape[0]
     mel = out["mel"].float().cpu().numpy().astype(np.float64)
@@ -110,7 +85,7 @@ def test_stop_rule_fires_where_the_oracle_fires(case, use_graph):
     sigmoid(stop) > 0.5 and t > min_steps = 10) fire at `stop_steps` with every decision `stop_margin` clear in float64"""
     from satt_amd.inference import infer
     z = np.load(os.path.join(GOLD, "decode_ljspeech_%s.npz" % case))
-    cfg, eng = _engine(z, "bf16", float(z["stop_shift"]))
+    cfg, eng = golden_engine(z, "bf16", float(z["stop_shift"]))
     out = infer(eng, z["source"], z["source_length"], max_steps=int(z["steps"]), min_steps=10, use_graph=use_graph)
     n = int(z["stop_steps"])
     stop = out["stop"].float().cpu().numpy()[..., 0]

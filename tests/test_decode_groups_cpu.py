@@ -9,49 +9,7 @@ import subprocess
 import pytest
 
 import satt_amd  # noqa: F401
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FAKE = 4096          # a non-NULL address (never dereferenced here)
-SPEAKER = dict(sproj=FAKE, Wp02=FAKE, bp02=FAKE)
-FAMILIES = [(m, d) for m in ("self-attention-tacotron", "tacotron") for d in ("ljspeech", "vctk")]
-
-
-def example_config(model, data):
-    from satt_amd.hparams import hparams
-    from satt_amd.params import ModelConfig
-    hp = hparams.copy()
-    hp.parse_json(open(os.path.join(ROOT, "examples", data, model + ".json")).read())
-    return ModelConfig.from_hparams(hp)
-
-
-def shape_of(c):
-    """the shape block DecodeSession offers for a configuration (dual form, or the baseline model's single-source form)"""
-    NO = c.num_mels * c.r + 1
-    second = dict(Ds=c.dec_sa_units, heads=c.dec_sa_heads, U2=c.att2_units, V2=c.sa_units) if c.dual else dict(Ds=0, heads=0, U2=0, V2=0)
-    return dict(A=c.att_rnn_units, D=c.dec_units, U1=c.att1_units, V1=c.cbhg_out_units, **second, kernel=c.att_kernel,
-                filters=c.att_filters, att1_mode=int(c.attention == "location_sensitive"), cumulative=int(c.cumulative_weights),
-                P0=c.dec_prenet[0], P1=c.dec_prenet[1], feed=c.num_mels * c.n_feed_frame, NO=NO, ldout=(NO + 7) // 8 * 8, zc=c.zc, zh=c.zh,
-                stop_threshold=0.5, min_steps=10)
-
-
-def block(c, B=2, Ti=57, nsteps=8, **kw):
-    from satt_amd import ops
-    extra = SPEAKER if c.num_speakers else {}
-    p = ops.dec_mega_params(B=B, Td=16, Ti=Ti, **extra, **dict(shape_of(c), **kw))
-    p.nsteps = nsteps
-    return p
-
-
-def groups(blocks, opt=None):
-    from satt_amd import ops
-    return ops.dec_mega_groups_blocks([(p, opt, 2 * g) for g, p in enumerate(blocks)])
-
-
-def options(agent, dropout):
-    from satt_amd import ops
-    kw = dict(agentW=FAKE, agentb=FAKE, agent_tab=FAKE, u_state=FAKE) if agent else {}
-    return ops.dec_mega_opt_params(drop=ops.Drop(0.5, 0, FAKE) if dropout else None, drop_T=16, drop_streams=(7, 8), **kw)
-
+from decode_common import FAMILIES, ROOT, SPEAKER, block, example_config, groups, options, shape_of
 
 @pytest.mark.parametrize("model,data", FAMILIES)
 def test_groups_supported_truth_table(model, data):

@@ -14,13 +14,13 @@ import numpy as np
 import pytest
 import torch
 
-from common import make_params, rel_err, small_batch
+from common import rel_err, small_batch
+from decode_common import (BAR, BASELINE, GOLDEN_BARS, Engines, expected_variant, golden_engine, infer_kwargs, keys_of, last_session, switches,
+                           traced_infer)
 
 pytestmark = pytest.mark.gpu
 
-BAR = 2e-5
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-BASELINE = dict(sa_units=0, att2_units=0, dec_sa_units=0, att1_units=256)          # the single-source model (tests/test_decode_single_gpu.py)
 SPK = dict(num_speakers=7, speaker_dim=16, speaker_offset=225)
 MODELS = {
     "plain": dict(),
@@ -38,63 +38,18 @@ MODELS = {
 }
 SIX = (225, 230, 226, 229, 227, 228)          # six DIFFERENT speakers in the six rows
 
-_engines = {}
-
-
-def engine(model, stop=False):
-    """one bf16 engine per (model, stop-logit bias), shared by the tests of this file (sessions are cached on it)"""
-    from satt_amd import ops
-    from satt_amd.engine import Engine
-    key = (model, stop)
-    if key not in _engines:
-        cfg, P = make_params(MODELS[model], seed=4)
-        P = dict(P)
-        if cfg.num_speakers:
-            P["speaker_embedding"] = np.random.default_rng(9).normal(0, 0.5, P["speaker_embedding"].shape).astype(np.float32)
-        if cfg.transition_agent:        # u far from 0.5, different per step and sample (tests/test_decode_options_gpu.py)
-            P["dec.att1.Wa"] = (3.0 * P["dec.att1.Wa"]).astype(np.float32)
-            P["dec.att1.ba"] = np.full_like(P["dec.att1.ba"], 1.5)
-        if stop:
-            b = np.array(P["dec.out.b"], dtype=np.float32).copy(); b[-1] = 50.0          # stop logit always large
-            P["dec.out.b"] = b
-        ops.set_precision("bf16")
-        _engines[key] = (Engine(cfg, "cuda", params=P, rng_seed=7), cfg)
-    ops.set_precision("bf16")
-    return _engines[key]
-
-
-def last_session(eng):
-    return eng._decode_sessions[next(reversed(eng._decode_sessions))]
+engine = Engines(MODELS, agent={None: (3.0, 1.5)})          # u far from 0.5, different per step and sample (tests/test_decode_options_gpu.py)
 
 
 def run(eng, cfg, B, Ti, steps, mode, grouped, gsteps=8, poison=None, source=None):
-    """one utterance; returns (outputs, session, the variants of the group launches).  grouped=False: DecodeSession.MEGA = False, the
-    hipGraph of launch-per-layer steps."""
-    from satt_amd import _lib, ops
-    from satt_amd.inference import infer, DecodeSession
+    """one utterance; returns (outputs, session, the (variant, groups, nsteps) of the group launches).  grouped=False:
+    DecodeSession.MEGA = False, the hipGraph of launch-per-layer steps."""
     batch = small_batch(cfg, B, Ti, steps * cfg.r, seed=6) if source is None else source
-    kw = dict(teacher=torch.as_tensor(batch["mel"])) if mode == "teacher" else dict(max_steps=steps, min_steps=(5 if mode == "stop" else 10 ** 6))
-    if cfg.num_speakers:
-        kw["speaker_id"] = torch.as_tensor(np.array([SIX[b % 6] for b in range(B)], np.int64))
-    if cfg.apply_dropout_on_inference:
-        kw["dropout_seed"] = 1234          # the same masks on both paths
-    dec_mega_groups, launched = ops.dec_mega_groups, []
-
-    def recording(arr, dev):
-        if poison is not None:          # the pattern in every LDS word of every CU in front of EVERY group launch
-            _lib.check(_lib.lib().satt_debug_poison_lds(poison, 100, ops.current_stream().cuda_stream), "poison_lds")
-        launched.append((ops.dec_mega_groups_variant(arr), len(arr), arr[0].p.nsteps))
-        return dec_mega_groups(arr, dev)
-    saved = (DecodeSession.MEGA, DecodeSession.MEGA_STEPS, DecodeSession.MEGA_GROUPS_STEPS)
-    try:
-        DecodeSession.MEGA, DecodeSession.MEGA_STEPS, DecodeSession.MEGA_GROUPS_STEPS = grouped, gsteps, gsteps
-        ops.dec_mega_groups = recording
-        out = infer(eng, batch["source"], batch["source_length"], **kw)
-        ses = last_session(eng)
-    finally:
-        ops.dec_mega_groups = dec_mega_groups
-        DecodeSession.MEGA, DecodeSession.MEGA_STEPS, DecodeSession.MEGA_GROUPS_STEPS = saved
-    return out, ses, launched
+    kw = infer_kwargs(mode, steps, batch.get("mel"), [SIX[b % 6] for b in range(B)] if cfg.num_speakers else None,
+                      1234 if cfg.apply_dropout_on_inference else None)          # the same masks on both paths
+    out, ses, launches = traced_infer(eng, batch["source"], batch["source_length"],
+                                      dict(MEGA=grouped, MEGA_STEPS=gsteps, MEGA_GROUPS_STEPS=gsteps), poison, **kw)
+    return out, ses, [l[1:] for l in launches if l.name == "dec_mega_groups"]
 
 
 def took_groups(ses, launched, B, cfg):
@@ -103,16 +58,10 @@ def took_groups(ses, launched, B, cfg):
     assert ses.mega_groups is not None and ses.mega is None and ses.kernel_launches == 1          # FAILS ON THE PARENT
     assert len(ses.mega_groups) == (B + 1) // 2 and ses.graph is None
     var = ops.dec_mega_groups_variant(ses.mega_groups)
-    want = ops.MEGA_VAR_GROUPS | ops.MEGA_VAR_TWO_SAMPLES | (0 if cfg.dual else ops.MEGA_VAR_SINGLE) | \
-        (ops.MEGA_VAR_SPEAKER if cfg.num_speakers else 0) | (ops.MEGA_VAR_AGENT if cfg.transition_agent else 0) | \
-        (ops.MEGA_VAR_DROPOUT if cfg.apply_dropout_on_inference else 0) | (ops.MEGA_VAR_LJ if (cfg.dual and cfg.n_feed_frame == 1) else 0)
+    want = expected_variant(cfg, B, ses.Ti, groups=True)
     assert var == want, (var, want)
     assert launched and {v for v, _, _ in launched} == {want} and {n for _, n, _ in launched} == {(B + 1) // 2}, launched
     return var
-
-
-def keys_of(cfg):
-    return ("mel", "stop", "alignment1") + (("alignment2",) if cfg.dual else ())
 
 
 def compare(model, B, Ti, steps, mode="free", gsteps=8, want_steps=None):
@@ -269,13 +218,12 @@ def test_stop_scan_refuses_rows_beyond_the_buffer():
 def test_grouped_decode_vs_frozen_float64_oracle():
     """tests/golden/decode_ljspeech_b8.npz (production dimensions, B = 8 with ragged lengths, 200 free-running steps) through the
     grouped path, with the bars tests/test_decode_golden_gpu.py applies to b8 in bf16"""
-    from test_decode_golden_gpu import BARS, _engine
     from satt_amd import ops
     from satt_amd.inference import infer
     z = np.load(os.path.join(GOLD, "decode_ljspeech_b8.npz"))
     steps = int(z["steps"])
     try:
-        cfg, eng = _engine(z, "bf16", case="b8")
+        cfg, eng = golden_engine(z, "bf16", case="b8")
         out = infer(eng, z["source"], z["source_length"], max_steps=steps, min_steps=10 ** 6, use_graph=True)
         torch.cuda.synchronize()
         ses = last_session(eng)
@@ -300,7 +248,7 @@ def test_grouped_decode_vs_frozen_float64_oracle():
              path=min((al1.argmax(-1) == z["path1"]).mean(), (al2.argmax(-1) == z["path2"]).mean()))
     print("grouped decode b8 bf16 vs frozen float64: mel %.3e, stop %.3e, alignment rows %.3e, per-step mean|mel| %.3e, argmax path "
           "agreement %.4f" % (e["mel"], e["stop"], e["align"], e["drift"], e["path"]))
-    bar = BARS["bf16"]
+    bar = GOLDEN_BARS["bf16"]
     for k in ("mel", "stop", "align", "drift"):
         assert e[k] <= bar[k], (k, e[k], bar[k])
     assert e["path"] >= bar["path"], e["path"]
@@ -328,8 +276,7 @@ def test_the_switches_fall_back_to_the_launch_per_layer_path():
     eng, cfg = engine("plain")
     batch = small_batch(cfg, 4, 33, 9 * cfg.r, seed=6)
     kw = dict(max_steps=9, min_steps=10 ** 6)
-    saved = (DecodeSession.MEGA_GROUPS, DecodeSession.MEGA_GROUPS_MAX_B)
-    try:
+    with switches("MEGA_GROUPS", "MEGA_GROUPS_MAX_B"):
         on = infer(eng, batch["source"], batch["source_length"], **kw)
         assert last_session(eng).mega_groups is not None
         DecodeSession.MEGA_GROUPS = False
@@ -338,6 +285,4 @@ def test_the_switches_fall_back_to_the_launch_per_layer_path():
         DecodeSession.MEGA_GROUPS, DecodeSession.MEGA_GROUPS_MAX_B = True, 3
         infer(eng, batch["source"], batch["source_length"], **kw)
         assert last_session(eng).mega_groups is None and last_session(eng).graph is not None
-    finally:
-        DecodeSession.MEGA_GROUPS, DecodeSession.MEGA_GROUPS_MAX_B = saved
     assert rel_err(on["mel"].cpu().numpy(), off["mel"].cpu().numpy()) < BAR

@@ -9,17 +9,7 @@ import subprocess
 import pytest
 
 import satt_amd  # noqa: F401
-from test_decode_speaker_cpu import LJ_KEYED, PRODUCTION, medium_shape
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FAKE = 4096          # a non-NULL address (never dereferenced here)
-SPEAKER = dict(sproj=FAKE, Wp02=FAKE, bp02=FAKE)
-
-
-def options(agent, dropout):
-    from satt_amd import ops
-    kw = dict(agentW=FAKE, agentb=FAKE, agent_tab=FAKE, u_state=FAKE) if agent else {}
-    return ops.dec_mega_opt_params(drop=ops.Drop(0.5, 0, FAKE) if dropout else None, drop_T=16, drop_streams=(7, 8), **kw)
+from decode_common import FAKE, LJ_KEYED, PRODUCTION, ROOT, SPEAKER, example_config, medium_shape, options, shape_of
 
 
 def test_option_block_layout_matches_c(tmp_path):
@@ -76,17 +66,9 @@ def test_the_spk_decoder_example_is_supported_with_its_wide_memories():
     V2 = 48 - and the kernel, generic in the memory widths, takes them for B <= 2, Ti <= 256: the generic instantiation with the
     speaker bit (the model has the multi-speaker pre-net too)"""
     from satt_amd import ops
-    from satt_amd.hparams import hparams
-    from satt_amd.params import ModelConfig
-    hp = hparams.copy()
-    hp.parse_json(open(os.path.join(ROOT, "examples", "vctk", "self-attention-tacotron-spk-decoder.json")).read())
-    c = ModelConfig.from_hparams(hp)
+    c = example_config("self-attention-tacotron-spk-decoder", "vctk")
     assert c.speaker_to_decoder and c.mem_speaker == 16
-    NO = c.num_mels * c.r + 1
-    shape = dict(A=c.att_rnn_units, D=c.dec_units, Ds=c.dec_sa_units, heads=c.dec_sa_heads, U1=c.att1_units, V1=c.cbhg_out_units + c.mem_speaker,
-                 U2=c.att2_units, V2=c.sa_units + c.mem_speaker, kernel=c.att_kernel, filters=c.att_filters, att1_mode=0, cumulative=0,
-                 P0=c.dec_prenet[0], P1=c.dec_prenet[1], feed=c.num_mels * c.n_feed_frame, NO=NO, ldout=(NO + 7) // 8 * 8, zc=c.zc, zh=c.zh,
-                 stop_threshold=0.5, min_steps=10)
+    shape = shape_of(c)
     assert (shape["V1"], shape["V2"], shape["feed"]) == (272, 48, 160)
     assert shape == dict(PRODUCTION, V1=272, V2=48, zc=c.zc, zh=c.zh)
     for B, Ti, base in ((1, 33, ops.MEGA_VAR_TABLES_LDS), (1, 140, 0), (1, 256, 0), (2, 57, ops.MEGA_VAR_TWO_SAMPLES), (2, 256, ops.MEGA_VAR_TWO_SAMPLES)):

@@ -13,18 +13,16 @@ and the masks' step index cross launch boundaries; the fold off; one long launch
 EVERY TEST HERE FAILS ON THE PARENT: there these models never take the kernel (`ses.mega is None`).
 Bars: those of tests/test_decode_speaker_gpu.py (2e-5 relative to the largest element: same bf16 weights, fp32 sums in another
 order, fed back through the steps; "live" means a difference of more than 100 bars)."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from common import make_params, rel_err, small_batch
+from decode_common import (BAR, KEYS, Engines, example_config, expected_variant, host_outputs, infer_kwargs, last_session, same, switches,
+                           traced_infer)
 
 pytestmark = pytest.mark.gpu
 
-BAR = 2e-5
-KEYS = ("mel", "stop", "alignment1", "alignment2")
 SPK = dict(num_speakers=4, speaker_dim=16, speaker_offset=225)
 WIDE = dict(SPK, speaker_to_decoder=True)
 MODELS = {
@@ -48,44 +46,14 @@ TI = {1: 33, 2: 57}
 IDS = {1: (226,), 2: (225, 227)}                            # two DIFFERENT speakers in the two rows
 FORMS = {"tables": (8, True), "nofold": (8, False), "tables32": (32, True)}          # -> (MEGA_STEPS, MEGA_FOLD_FEEDBACK)
 
-_engines, _runs = {}, {}
-
-
-def engine(model, stop=False):
-    """one bf16 engine per (model, stop-logit bias), shared by the tests of this file (sessions are cached on it)"""
-    from satt_amd import ops
-    from satt_amd.engine import Engine
-    key = (model, stop)
-    if key not in _engines:
-        cfg, P = make_params(MODELS[model], seed=4)
-        P = dict(P)
-        if cfg.num_speakers:
-            P["speaker_embedding"] = np.random.default_rng(9).normal(0, 0.5, P["speaker_embedding"].shape).astype(np.float32)
-        if cfg.transition_agent:        # u far from 0.5, different per step and sample (tests/test_inference_gpu.py scales Wa the same way)
-            z = model == "agent0"
-            P["dec.att1.Wa"] = ((0.0 if z else 3.0) * P["dec.att1.Wa"]).astype(np.float32)
-            P["dec.att1.ba"] = np.full_like(P["dec.att1.ba"], 0.0 if z else 1.5)
-        if stop:
-            b = np.array(P["dec.out.b"], dtype=np.float32).copy(); b[-1] = 50.0          # stop logit always large
-            P["dec.out.b"] = b
-        ops.set_precision("bf16")
-        eng = Engine(cfg, "cuda", params=P, rng_seed=7)
-        g = np.random.default_rng(11)
-        mv = {}
-        for name, (mean, var) in eng.bn.items():        # non-trivial moving statistics, shared with the oracle
-            m = g.normal(0, 0.2, mean.shape[0]).astype(np.float32); v = g.uniform(0.5, 1.5, var.shape[0]).astype(np.float32)
-            mean.copy_(torch.as_tensor(m)); var.copy_(torch.as_tensor(v))
-            mv[name] = (torch.as_tensor(m, dtype=torch.float64), torch.as_tensor(v, dtype=torch.float64))
-        _engines[key] = (eng, cfg, P, mv)
-    ops.set_precision("bf16")
-    return _engines[key]
+# u far from 0.5, different per step and sample (tests/test_inference_gpu.py scales Wa the same way); "agent0": u = 0.5 at every step
+engine = Engines(MODELS, stats=True, agent={None: (3.0, 1.5), "agent0": (0.0, 0.0)})
+_runs = {}
 
 
 def run(model, B, mode, mega, form="tables", Ti=None, ids=None, poison=None, fresh=False, seed=None):
     """one utterance; returns (outputs on the host, the instantiation of the persistent kernel that was LAUNCHED for it - None if
     none was).  Results are computed once and shared between the tests (fresh=True: computed again)."""
-    from satt_amd import _lib, ops
-    from satt_amd.inference import infer, DecodeSession
     Ti = TI[B] if Ti is None else Ti
     ids = IDS[B] if ids is None else ids
     key = (model, B, Ti, mode, mega, form, ids, poison, seed)
@@ -94,40 +62,13 @@ def run(model, B, mode, mega, form="tables", Ti=None, ids=None, poison=None, fre
     eng, cfg, _, _ = engine(model, stop=(mode == "stop"))
     steps = SHAPES[(B, Ti)]
     batch = small_batch(cfg, B, Ti, steps * cfg.r, seed=6)
-    kw = dict(teacher=torch.as_tensor(batch["mel"])) if mode == "teacher" else dict(max_steps=steps, min_steps=(5 if mode == "stop" else 10 ** 6))
-    if cfg.num_speakers:
-        kw["speaker_id"] = torch.as_tensor(np.array(ids, np.int64))
-    if seed is not None:
-        kw["dropout_seed"] = seed
-    dec_mega, dec_mega_opt, launched = ops.dec_mega, ops.dec_mega_opt, set()
-
-    def before(var):
-        if poison is not None:          # the pattern in every LDS word of every CU in front of EVERY launch of the persistent kernel
-            _lib.check(_lib.lib().satt_debug_poison_lds(poison, 100, ops.current_stream().cuda_stream), "poison_lds")
-        launched.add(var)
-
-    def recording(p, n):              # (inference.py calls ops.dec_mega without options, ops.dec_mega_opt with)
-        before(ops.dec_mega_variant(p))
-        return dec_mega(p, n)
-
-    def recording_opt(p, o, n):
-        before(ops.dec_mega_opt_variant(p, o))
-        return dec_mega_opt(p, o, n)
-    try:
-        DecodeSession.MEGA = mega
-        DecodeSession.MEGA_STEPS, DecodeSession.MEGA_FOLD_FEEDBACK = FORMS[form]
-        ops.dec_mega, ops.dec_mega_opt = recording, recording_opt
-        out = infer(eng, batch["source"], batch["source_length"], **kw)
-        assert len(launched) <= 1
-        var = launched.pop() if launched else None
-    finally:
-        ops.dec_mega, ops.dec_mega_opt = dec_mega, dec_mega_opt
-        DecodeSession.MEGA = True
-        DecodeSession.MEGA_STEPS = 128
-        DecodeSession.MEGA_FOLD_FEEDBACK = True
-    res = {k: out[k].detach().cpu() for k in KEYS}
-    res["steps"] = out["steps"]
-    _runs[key] = (res, var)
+    kw = infer_kwargs(mode, steps, batch["mel"], ids if cfg.num_speakers else None, seed)
+    K, fold = FORMS[form]
+    out, _, launches = traced_infer(eng, batch["source"], batch["source_length"], dict(MEGA=mega, MEGA_STEPS=K, MEGA_FOLD_FEEDBACK=fold),
+                                    poison, **kw)
+    launched = {l.variant for l in launches}          # (without options through ops.dec_mega, with them through ops.dec_mega_opt)
+    assert len(launched) <= 1
+    _runs[key] = (host_outputs(out), launched.pop() if launched else None)
     return _runs[key]
 
 
@@ -136,17 +77,8 @@ def took(var, B, bits, Ti=None, lj=False):
     LJ-keyed ones, exactly the option / speaker bits `bits`"""
     from satt_amd import ops
     assert var is not None, "the model did not take the persistent kernel"          # FAILS ON THE PARENT
-    form = ops.MEGA_VAR_TWO_SAMPLES if B == 2 else (ops.MEGA_VAR_TABLES_LDS if (Ti or TI[B]) <= 112 else 0)
+    form = expected_variant(engine.config("plain"), B, Ti or TI[B])          # (the plain model's instantiation is the form of the shape)
     assert var == form | (ops.MEGA_VAR_LJ if lj else 0) | bits, (var, form, bits)
-
-
-def same(new, old, what):
-    assert new["steps"] == old["steps"]
-    for k in KEYS:
-        e = rel_err(new[k].numpy(), old[k].numpy())
-        print("%s %-10s rel_err=%.3e (bar %.0e)" % (what, k, e, BAR))
-        assert e < BAR, (what, k, e)
-    assert torch.isfinite(new["mel"]).all()
 
 
 def against_launch_per_layer(model, B, mode, form, bits, Ti=None, lj=False, **kw):
@@ -155,7 +87,7 @@ def against_launch_per_layer(model, B, mode, form, bits, Ti=None, lj=False, **kw
     old, none = run(model, B, mode, False, Ti=Ti, **kw)
     assert none is None
     assert new["steps"] == (7 if mode == "stop" else SHAPES[(B, Ti or TI[B])])
-    same(new, old, "%s %s %s B=%d" % (model, form, mode, B))
+    same(new, old, "%s %s %s B=%d" % (model, form, mode, B), KEYS)
     return new
 
 
@@ -198,7 +130,7 @@ def test_the_agent_is_live_in_each_row():
     flat, var0 = run("agent0", 2, "free", True, "tables")
     took(var0, 2, ops.MEGA_VAR_AGENT)
     old, _ = run("agent0", 2, "free", False)
-    same(flat, old, "u = 0.5")
+    same(flat, old, "u = 0.5", KEYS)
     for row in (0, 1):
         d = rel_err(live["alignment1"][row].numpy(), flat["alignment1"][row].numpy())
         print("row %d: alignment1 with the agent against u = 0.5 differs by %.3e (must exceed %.0e)" % (row, d, 100 * BAR))
@@ -312,7 +244,7 @@ def test_the_speaker_columns_are_live_and_belong_to_their_row():
     took(var, 2, ops.MEGA_VAR_SPEAKER)
     swapped, _ = run("wide", 2, "free", True, "tables", ids=(b, a))
     old, _ = run("wide", 2, "free", False, ids=(b, a))
-    same(swapped, old, "swapped ids")
+    same(swapped, old, "swapped ids", KEYS)
     d = rel_err(swapped["mel"][0].numpy(), first["mel"][0].numpy())
     print("row 0: other speaker, same text: mel differs by %.3e (must exceed %.0e)" % (d, 100 * BAR))
     assert d > 100 * BAR, d
@@ -343,13 +275,8 @@ def test_the_spk_decoder_example_widths():
     """examples/vctk/self-attention-tacotron-spk-decoder.json itself: 152 speakers, two fed-back frames per step (feed = 160)"""
     from satt_amd import ops
     from satt_amd.engine import Engine
-    from satt_amd.hparams import hparams
     from satt_amd.inference import infer, DecodeSession
-    from satt_amd.params import ModelConfig
-    hp = hparams.copy()
-    hp.parse_json(open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples", "vctk",
-                                    "self-attention-tacotron-spk-decoder.json")).read())
-    want = ModelConfig.from_hparams(hp)
+    want = example_config("self-attention-tacotron-spk-decoder", "vctk")
     cfg, P = make_params(dict(num_speakers=152, speaker_dim=16, speaker_offset=225, n_feed_frame=2, speaker_to_decoder=True), seed=4)
     for f in ("n_feed_frame", "num_speakers", "speaker_dim", "speaker_offset", "dec_prenet", "att_rnn_units", "att1_units", "att2_units", "dec_units",
               "dec_sa_units", "dec_sa_heads", "cbhg_out_units", "sa_units", "num_mels", "r", "att_kernel", "att_filters", "mem_speaker", "speaker_to_decoder"):
@@ -358,18 +285,15 @@ def test_the_spk_decoder_example_widths():
     eng = Engine(cfg, "cuda", params=P, rng_seed=7)
     batch = small_batch(cfg, 1, 33, 9 * cfg.r, seed=6)
     call = lambda: infer(eng, batch["source"], batch["source_length"], max_steps=9, min_steps=10 ** 6, speaker_id=torch.as_tensor([225 + 151]))
-    try:
-        DecodeSession.MEGA, DecodeSession.MEGA_STEPS = True, 8
+    with switches(MEGA=True, MEGA_STEPS=8):
         new = call()
-        ses = eng._decode_sessions[next(reversed(eng._decode_sessions))]
+        ses = last_session(eng)          # (a new engine: the session is new)
         assert ses.mega is not None          # FAILS ON THE PARENT
         assert ops.dec_mega_variant(ses.mega) == ops.MEGA_VAR_TABLES_LDS | ops.MEGA_VAR_SPEAKER and ses.mega_opt is None
         DecodeSession.MEGA = False
         old = call()
-        assert eng._decode_sessions[next(reversed(eng._decode_sessions))].mega is None
-    finally:
-        DecodeSession.MEGA, DecodeSession.MEGA_STEPS = True, 128
-    same({**{k: new[k].cpu() for k in KEYS}, "steps": new["steps"]}, {**{k: old[k].cpu() for k in KEYS}, "steps": old["steps"]}, "spk-decoder example")
+        assert last_session(eng).mega is None
+    same(host_outputs(new), host_outputs(old), "spk-decoder example", KEYS)
 
 
 # ---- 7: LDS poison

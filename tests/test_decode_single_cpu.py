@@ -8,34 +8,9 @@ import subprocess
 import pytest
 
 import satt_amd  # noqa: F401
+from decode_common import ROOT, SPEAKER, example_config, options, shape_of
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FAKE = 4096          # a non-NULL address (never dereferenced here)
-SPEAKER = dict(sproj=FAKE, Wp02=FAKE, bp02=FAKE)
 EXAMPLES = ("ljspeech", "vctk")
-
-
-def example_config(name):
-    from satt_amd.hparams import hparams
-    from satt_amd.params import ModelConfig
-    hp = hparams.copy()
-    hp.parse_json(open(os.path.join(ROOT, "examples", name, "tacotron.json")).read())
-    return ModelConfig.from_hparams(hp)
-
-
-def single_shape(c):
-    """the shape block DecodeSession offers for a baseline configuration"""
-    NO = c.num_mels * c.r + 1
-    return dict(A=c.att_rnn_units, D=c.dec_units, Ds=0, heads=0, U1=c.att1_units, V1=c.cbhg_out_units, U2=0, V2=0, kernel=c.att_kernel,
-                filters=c.att_filters, att1_mode=int(c.attention == "location_sensitive"), cumulative=int(c.cumulative_weights),
-                P0=c.dec_prenet[0], P1=c.dec_prenet[1], feed=c.num_mels * c.n_feed_frame, NO=NO, ldout=(NO + 7) // 8 * 8, zc=c.zc, zh=c.zh,
-                stop_threshold=0.5, min_steps=10)
-
-
-def options(agent, dropout):
-    from satt_amd import ops
-    kw = dict(agentW=FAKE, agentb=FAKE, agent_tab=FAKE, u_state=FAKE) if agent else {}
-    return ops.dec_mega_opt_params(drop=ops.Drop(0.5, 0, FAKE) if dropout else None, drop_T=16, drop_streams=(7, 8), **kw)
 
 
 @pytest.mark.parametrize("example", EXAMPLES)
@@ -51,7 +26,7 @@ def test_the_baseline_examples_are_single_source_models(example):
 def test_supported_table_and_variants(example, speaker):
     from satt_amd import ops
     LDS, SPK, TWO, SINGLE = ops.MEGA_VAR_TABLES_LDS, ops.MEGA_VAR_SPEAKER, ops.MEGA_VAR_TWO_SAMPLES, ops.MEGA_VAR_SINGLE
-    shape = single_shape(example_config(example))
+    shape = shape_of(example_config(example))
     extra = SPEAKER if speaker else {}
     for B, Ti, want in ((1, 33, LDS | SINGLE), (1, 112, LDS | SINGLE), (1, 113, SINGLE), (1, 256, SINGLE), (2, 57, TWO | SINGLE),
                         (2, 256, TWO | SINGLE)):
@@ -66,7 +41,7 @@ def test_supported_table_and_variants(example, speaker):
 @pytest.mark.parametrize("B,Ti", [(1, 33), (2, 57)])
 def test_half_single_blocks_are_refused(B, Ti):
     from satt_amd import ops
-    shape = single_shape(example_config("ljspeech"))
+    shape = shape_of(example_config("ljspeech"))
     for half in (dict(U2=32, V2=32), dict(Ds=256, heads=2), dict(U2=32), dict(V2=32), dict(heads=2), dict(Ds=256)):
         p = ops.dec_mega_params(B=B, Td=16, Ti=Ti, **dict(shape, **half))
         assert not ops.dec_mega_supported(p) and ops.dec_mega_variant(p) == -1, half
@@ -76,7 +51,7 @@ def test_half_single_blocks_are_refused(B, Ti):
 def test_the_single_form_keeps_the_production_widths_of_the_cells(B, Ti):
     """MEDIUM widths (A = D = 64), and the edges of the single form's own conditions"""
     from satt_amd import ops
-    shape = single_shape(example_config("ljspeech"))
+    shape = shape_of(example_config("ljspeech"))
     for bad in (dict(A=64, D=64, U1=32, V1=32, P0=32, P1=32), dict(A=64), dict(D=64), dict(U1=4), dict(U1=260), dict(U1=130), dict(V1=0),
                 dict(V1=1028), dict(P0=260), dict(P1=12), dict(NO=169), dict(kernel=17), dict(filters=9)):
         assert not ops.dec_mega_supported(ops.dec_mega_params(B=B, Td=16, Ti=Ti, **dict(shape, **bad))), bad
@@ -88,7 +63,7 @@ def test_the_single_form_keeps_the_production_widths_of_the_cells(B, Ti):
 @pytest.mark.parametrize("B,Ti", [(1, 33), (1, 140), (2, 57)])
 def test_the_single_form_takes_no_options(B, Ti, speaker):
     from satt_amd import ops
-    p = ops.dec_mega_params(B=B, Td=16, Ti=Ti, **(SPEAKER if speaker else {}), **single_shape(example_config("vctk")))
+    p = ops.dec_mega_params(B=B, Td=16, Ti=Ti, **(SPEAKER if speaker else {}), **shape_of(example_config("vctk")))
     plain = ops.dec_mega_variant(p)
     assert plain > 0 and plain & ops.MEGA_VAR_SINGLE
     assert ops.dec_mega_opt_variant(p, None) == plain

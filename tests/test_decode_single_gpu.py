@@ -6,19 +6,16 @@ EVERY TEST HERE FAILS ON THE PARENT: there the baseline model never takes the ke
 Bar: 2e-5 relative to the largest element, the bar test_persistent_decode_kernel_equals_the_launch_per_layer_path (tests/
 test_inference_gpu.py) sets for exactly this comparison of the dual form.  Production widths (A = D = 256), short memories, few
 steps; MEGA_STEPS = 8 gives several launches, a ragged last one, and an unfolded step every eighth."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
-from common import make_params, rel_err, small_batch
+from common import rel_err, small_batch
+from decode_common import BAR, BASELINE, Engines, example_config, expected_variant, infer_kwargs, last_session, switches, traced_infer
 
 pytestmark = pytest.mark.gpu
 
-BAR = 2e-5
 KEYS = ("mel", "stop", "alignment1")
-BASELINE = dict(sa_units=0, att2_units=0, dec_sa_units=0, att1_units=256)          # baseline_kw(dict()) of tests/test_model_gpu.py
 SPK = dict(num_speakers=7, speaker_dim=16, speaker_offset=225)
 MODELS = {
     "plain": BASELINE,
@@ -33,66 +30,25 @@ MODELS = {
 }
 IDS = {1: (226,), 2: (225, 230)}                            # two DIFFERENT speakers in the two rows
 
-_engines = {}
-
-
-def engine(model, stop=False):
-    """one bf16 engine per (model, stop-logit bias), shared by the tests of this file (sessions are cached on it)"""
-    from satt_amd import ops
-    from satt_amd.engine import Engine
-    key = (model, stop)
-    if key not in _engines:
-        cfg, P = make_params(MODELS[model], seed=4)
-        assert not cfg.dual and cfg.dec_sa_units == 0
-        P = dict(P)
-        if cfg.num_speakers:
-            P["speaker_embedding"] = np.random.default_rng(9).normal(0, 0.5, P["speaker_embedding"].shape).astype(np.float32)
-        if stop:
-            b = np.array(P["dec.out.b"], dtype=np.float32).copy(); b[-1] = 50.0          # stop logit always large
-            P["dec.out.b"] = b
-        ops.set_precision("bf16")
-        _engines[key] = (Engine(cfg, "cuda", params=P, rng_seed=7), cfg)
-    ops.set_precision("bf16")
-    return _engines[key]
-
-
-def last_session(eng):
-    return eng._decode_sessions[next(reversed(eng._decode_sessions))]
+engine = Engines(MODELS)
 
 
 def run(eng, cfg, B, Ti, steps, mode, mega, mega_steps=8, fold=True, poison=None):
     """one utterance; returns (outputs, session, the variants of the persistent kernel that were launched)"""
-    from satt_amd import _lib, ops
-    from satt_amd.inference import infer, DecodeSession
+    assert not cfg.dual and cfg.dec_sa_units == 0
     batch = small_batch(cfg, B, Ti, steps * cfg.r, seed=6)
-    kw = dict(teacher=torch.as_tensor(batch["mel"])) if mode == "teacher" else dict(max_steps=steps, min_steps=(5 if mode == "stop" else 10 ** 6))
-    if cfg.num_speakers:
-        kw["speaker_id"] = torch.as_tensor(np.array(IDS[B], np.int64))
-    dec_mega, launched = ops.dec_mega, set()
-
-    def recording(p, n):
-        if poison is not None:          # the pattern in every LDS word of every CU in front of EVERY launch of the persistent kernel
-            _lib.check(_lib.lib().satt_debug_poison_lds(poison, 100, ops.current_stream().cuda_stream), "poison_lds")
-        launched.add(ops.dec_mega_variant(p))
-        return dec_mega(p, n)
-    saved = (DecodeSession.MEGA, DecodeSession.MEGA_STEPS, DecodeSession.MEGA_FOLD_FEEDBACK)
-    try:
-        DecodeSession.MEGA, DecodeSession.MEGA_STEPS, DecodeSession.MEGA_FOLD_FEEDBACK = mega, mega_steps, fold
-        ops.dec_mega = recording
-        out = infer(eng, batch["source"], batch["source_length"], **kw)
-        ses = last_session(eng)
-    finally:
-        ops.dec_mega = dec_mega
-        DecodeSession.MEGA, DecodeSession.MEGA_STEPS, DecodeSession.MEGA_FOLD_FEEDBACK = saved
-    return out, ses, launched
+    kw = infer_kwargs(mode, steps, batch["mel"], IDS[B] if cfg.num_speakers else None)
+    out, ses, launches = traced_infer(eng, batch["source"], batch["source_length"],
+                                      dict(MEGA=mega, MEGA_STEPS=mega_steps, MEGA_FOLD_FEEDBACK=fold), poison, **kw)
+    return out, ses, {l.variant for l in launches}
 
 
 def took_single(ses, launched, B, Ti, speaker=False):
     """the session holds the kernel's block and the instantiation that was launched is the single form's for the shape"""
     from satt_amd import ops
     assert ses.mega is not None and ses.mega_opt is None and ses.kernel_launches == 1
-    want = ops.MEGA_VAR_SINGLE | (ops.MEGA_VAR_TABLES_LDS if (B == 1 and Ti <= 112) else 0) | (ops.MEGA_VAR_TWO_SAMPLES if B == 2 else 0) | \
-        (ops.MEGA_VAR_SPEAKER if speaker else 0)
+    want = expected_variant(ses.eng.cfg, B, Ti)
+    assert want & ops.MEGA_VAR_SINGLE and bool(want & ops.MEGA_VAR_SPEAKER) == speaker
     assert ops.dec_mega_variant(ses.mega) == want
     assert launched == {want}, launched
 
@@ -182,33 +138,25 @@ def test_single_source_kernel_hands_over_to_the_launch_per_layer_path_and_back(B
 def test_the_shipped_baseline_examples_take_the_kernel(example):
     from satt_amd import ops
     from satt_amd.engine import Engine
-    from satt_amd.hparams import hparams
-    from satt_amd.params import ModelConfig
-    hp = hparams.copy()
-    hp.parse_json(open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples", example, "tacotron.json")).read())
-    cfg = ModelConfig.from_hparams(hp)
+    from satt_amd.inference import infer, DecodeSession
+    cfg = example_config(example)
     ops.set_precision("bf16")
     eng = Engine(cfg, "cuda", param_seed=3, rng_seed=7)
     B, Ti, steps = 1, 33, 9
     g = np.random.default_rng(5)
     batch = dict(source=g.integers(1, cfg.num_symbols, (B, Ti)).astype(np.int64), source_length=np.full((B,), Ti, np.int64))
-    from satt_amd.inference import infer, DecodeSession
     kw = dict(max_steps=steps, min_steps=10 ** 6)
     if cfg.num_speakers:
         kw["speaker_id"] = torch.as_tensor(np.array([cfg.speaker_offset + 3], np.int64))
-    saved = DecodeSession.MEGA
-    try:
-        DecodeSession.MEGA = True
+    with switches(MEGA=True):
         new = infer(eng, batch["source"], batch["source_length"], **kw)
-        ses = last_session(eng)
+        ses = last_session(eng)          # (a new engine: the session is new)
         assert ses.mega is not None
         want = ops.MEGA_VAR_TABLES_LDS | ops.MEGA_VAR_SINGLE | (ops.MEGA_VAR_SPEAKER if example == "vctk" else 0)
         assert ops.dec_mega_variant(ses.mega) == want
         DecodeSession.MEGA = False
         old = infer(eng, batch["source"], batch["source_length"], **kw)
         assert last_session(eng).mega is None
-    finally:
-        DecodeSession.MEGA = saved
     assert new["steps"] == old["steps"] == steps
     for k in KEYS:
         e = rel_err(new[k].cpu().numpy(), old[k].cpu().numpy())

@@ -4,37 +4,14 @@ the dimensions and `sproj != NULL`.  No compute calls (there is no GPU here).  F
 import pytest
 
 import satt_amd  # noqa: F401
-from common import MEDIUM
-
-# examples/vctk/self-attention-tacotron.json (= the LJSpeech layer sizes, two fed-back frames): the shape block DecodeSession hands to
-# the library; LJ_KEYED: the same with ONE fed-back frame - the widths the compile-time specialisation of the kernel is keyed on
-PRODUCTION = dict(A=256, D=256, Ds=256, heads=2, U1=224, V1=256, U2=32, V2=32, kernel=10, filters=5, att1_mode=0, cumulative=0,
-                  P0=256, P1=128, feed=160, NO=161, ldout=168, zc=0.1, zh=0.1, stop_threshold=0.5, min_steps=10)
-LJ_KEYED = dict(PRODUCTION, feed=80)
+from decode_common import LJ_KEYED, PRODUCTION, example_config, medium_shape, shape_of
 
 
 def test_production_is_what_the_session_builds_for_the_vctk_example():
-    import os
-    from satt_amd.hparams import hparams
-    from satt_amd.params import ModelConfig
-    hp = hparams.copy()
-    hp.parse_json(open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples", "vctk", "self-attention-tacotron.json")).read())
-    c = ModelConfig.from_hparams(hp)
-    NO = c.num_mels * c.r + 1
-    got = dict(A=c.att_rnn_units, D=c.dec_units, Ds=c.dec_sa_units, heads=c.dec_sa_heads, U1=c.att1_units, V1=c.cbhg_out_units + c.mem_speaker,
-               U2=c.att2_units, V2=c.sa_units + c.mem_speaker, kernel=c.att_kernel, filters=c.att_filters, P0=c.dec_prenet[0], P1=c.dec_prenet[1],
-               feed=c.num_mels * c.n_feed_frame, NO=NO, ldout=(NO + 7) // 8 * 8)
-    assert c.num_speakers == 152 and got == {k: PRODUCTION[k] for k in got}
-
-
-def medium_shape():
-    from satt_amd.params import ModelConfig
-    c = ModelConfig(**MEDIUM)
-    NO = c.num_mels * c.r + 1
-    return dict(A=c.att_rnn_units, D=c.dec_units, Ds=c.dec_sa_units, heads=c.dec_sa_heads, U1=c.att1_units, V1=c.cbhg_out_units,
-                U2=c.att2_units, V2=c.sa_units, kernel=c.att_kernel, filters=c.att_filters, att1_mode=0, cumulative=0, P0=c.dec_prenet[0],
-                P1=c.dec_prenet[1], feed=c.num_mels * c.n_feed_frame, NO=NO, ldout=(NO + 7) // 8 * 8, zc=c.zc, zh=c.zh, stop_threshold=0.5,
-                min_steps=10)
+    c = example_config("self-attention-tacotron", "vctk")
+    got = {k: v for k, v in shape_of(c).items() if k in ("A", "D", "Ds", "heads", "U1", "V1", "U2", "V2", "kernel", "filters", "P0", "P1",
+                                                         "feed", "NO", "ldout")}
+    assert c.num_speakers == 152 and len(got) == 15 and got == {k: PRODUCTION[k] for k in got}
 
 
 def test_the_parameter_block_ends_with_the_speaker_term():

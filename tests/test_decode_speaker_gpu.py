@@ -17,10 +17,10 @@ import pytest
 import torch
 
 from common import make_params, rel_err, small_batch
+from decode_common import BAR, Engines, example_config, host_outputs, infer_kwargs, last_session, same, switches, traced_infer
 
 pytestmark = pytest.mark.gpu
 
-BAR = 2e-5
 KEYS = ("mel", "stop", "alignment1", "alignment2")
 SPK = dict(num_speakers=4, speaker_dim=16, speaker_offset=225)
 # what the model is built with, per speaker source (test 3); "table" is the model of every other test
@@ -29,39 +29,13 @@ SHAPES = {1: (33, 9), 2: (57, 19)}            # B -> (Ti, steps)
 IDS = {1: (226,), 2: (225, 227)}              # two DIFFERENT speakers in the two rows
 FORMS = {"tables": (8, True), "nofold": (8, False), "tables32": (32, True)}          # -> (MEGA_STEPS, MEGA_FOLD_FEEDBACK)
 
-_engines, _runs = {}, {}
-
-
-def engine(source="table", stop=False):
-    """one bf16 engine per (model, stop-logit bias), shared by the tests of this file (sessions are cached on it)"""
-    from satt_amd import ops
-    from satt_amd.engine import Engine
-    key = (source, stop)
-    if key not in _engines:
-        cfg, P = make_params(SOURCES[source], seed=4)
-        P = dict(P)
-        P["speaker_embedding"] = np.random.default_rng(9).normal(0, 0.5, P["speaker_embedding"].shape).astype(np.float32)
-        if stop:
-            b = np.array(P["dec.out.b"], dtype=np.float32).copy(); b[-1] = 50.0          # stop logit always large
-            P["dec.out.b"] = b
-        ops.set_precision("bf16")
-        eng = Engine(cfg, "cuda", params=P, rng_seed=7)
-        g = np.random.default_rng(11)
-        mv = {}
-        for name, (mean, var) in eng.bn.items():        # non-trivial moving statistics, shared with the oracle
-            m = g.normal(0, 0.2, mean.shape[0]).astype(np.float32); v = g.uniform(0.5, 1.5, var.shape[0]).astype(np.float32)
-            mean.copy_(torch.as_tensor(m)); var.copy_(torch.as_tensor(v))
-            mv[name] = (torch.as_tensor(m, dtype=torch.float64), torch.as_tensor(v, dtype=torch.float64))
-        _engines[key] = (eng, cfg, P, mv)
-    ops.set_precision("bf16")
-    return _engines[key]
+engine = Engines(SOURCES, stats=True)
+_runs = {}
 
 
 def run(B, mode, mega, form="tables", ids=None, source="table", poison=None, fresh=False, **spk_kw):
     """one utterance; returns (outputs on the host, the instantiation of the persistent kernel that was LAUNCHED for it - None if
     none was).  Results are computed once and shared between the tests (fresh=True: computed again)."""
-    from satt_amd import _lib, ops
-    from satt_amd.inference import infer, DecodeSession
     ids = IDS[B] if ids is None else ids
     key = (B, mode, mega, form, ids, source, poison, tuple(sorted(spk_kw)))
     if key in _runs and not fresh:
@@ -69,32 +43,14 @@ def run(B, mode, mega, form="tables", ids=None, source="table", poison=None, fre
     eng, cfg, _, _ = engine(source, stop=(mode == "stop"))
     Ti, steps = SHAPES[B]
     batch = small_batch(cfg, B, Ti, steps * cfg.r, seed=6)
-    kw = dict(teacher=torch.as_tensor(batch["mel"])) if mode == "teacher" else dict(max_steps=steps, min_steps=(5 if mode == "stop" else 10 ** 6))
-    if "speaker_embed" not in spk_kw and ids != "none":
-        kw["speaker_id"] = torch.as_tensor(np.array(ids, np.int64))
+    kw = infer_kwargs(mode, steps, batch["mel"], ids if ("speaker_embed" not in spk_kw and ids != "none") else None)
     kw.update(spk_kw)
-    dec_mega, launched = ops.dec_mega, set()
-
-    def recording(p, n):          # (inference.py calls ops.dec_mega)
-        if poison is not None:          # the pattern in every LDS word of every CU in front of EVERY launch of the persistent kernel
-            _lib.check(_lib.lib().satt_debug_poison_lds(poison, 100, ops.current_stream().cuda_stream), "poison_lds")
-        launched.add(ops.dec_mega_variant(p))
-        return dec_mega(p, n)
-    try:
-        DecodeSession.MEGA = mega
-        DecodeSession.MEGA_STEPS, DecodeSession.MEGA_FOLD_FEEDBACK = FORMS[form]
-        ops.dec_mega = recording
-        out = infer(eng, batch["source"], batch["source_length"], **kw)
-        assert len(launched) <= 1
-        var = launched.pop() if launched else None
-    finally:
-        ops.dec_mega = dec_mega
-        DecodeSession.MEGA = True
-        DecodeSession.MEGA_STEPS = 128
-        DecodeSession.MEGA_FOLD_FEEDBACK = True
-    res = {k: out[k].detach().cpu() for k in KEYS}
-    res["steps"] = out["steps"]
-    _runs[key] = (res, var)
+    K, fold = FORMS[form]
+    out, _, launches = traced_infer(eng, batch["source"], batch["source_length"], dict(MEGA=mega, MEGA_STEPS=K, MEGA_FOLD_FEEDBACK=fold),
+                                    poison, **kw)
+    launched = {l.variant for l in launches}
+    assert len(launched) <= 1
+    _runs[key] = (host_outputs(out, KEYS), launched.pop() if launched else None)
     return _runs[key]
 
 
@@ -102,15 +58,6 @@ def took_the_speaker_kernel(var, B):
     from satt_amd import ops
     assert var is not None, "the speaker model did not take the persistent kernel"          # FAILS ON THE PARENT
     assert var & ops.MEGA_VAR_SPEAKER and bool(var & ops.MEGA_VAR_TWO_SAMPLES) == (B == 2)
-
-
-def same(new, old, what):
-    assert new["steps"] == old["steps"]
-    for k in KEYS:
-        e = rel_err(new[k].numpy(), old[k].numpy())
-        print("%s %-10s rel_err=%.3e (bar %.0e)" % (what, k, e, BAR))
-        assert e < BAR, (what, k, e)
-    assert torch.isfinite(new["mel"]).all()
 
 
 # ---- 1: persistent against launch per layer
@@ -122,7 +69,7 @@ def test_speaker_model_on_the_persistent_kernel_equals_the_launch_per_layer_path
     old, none = run(B, mode, False)
     assert none is None
     assert new["steps"] == (7 if mode == "stop" else SHAPES[B][1])
-    same(new, old, "%s %s B=%d" % (form, mode, B))
+    same(new, old, "%s %s B=%d" % (form, mode, B), KEYS)
 
 
 # ---- 2: the term is live, and per row
@@ -137,7 +84,7 @@ def test_the_speaker_term_is_live_and_belongs_to_its_row(form):
     took_the_speaker_kernel(var, 2)
     swapped, _ = run(2, "free", True, form, ids=(b, a))
     old, _ = run(2, "free", False, ids=(b, a))
-    same(swapped, old, form + " swapped ids")
+    same(swapped, old, form + " swapped ids", KEYS)
     for row in (0, 1):
         d = rel_err(swapped["mel"][row].numpy(), first["mel"][row].numpy())
         print("row %d: other speaker, same text: mel differs by %.3e (must exceed %.0e)" % (row, d, 100 * BAR))
@@ -161,7 +108,7 @@ def test_every_speaker_source_reaches_the_kernel(source):
     new, var = run(1, "free", True, "tables", ids=ids, source=source, **kw)
     took_the_speaker_kernel(var, 1)
     old, _ = run(1, "free", False, ids=ids, source=source, **kw)
-    same(new, old, source)
+    same(new, old, source, KEYS)
     if source in ("for_synthesis", "embed"):      # not the table row of the default id: the source was used
         other, _ = run(1, "free", True, "tables", source="table")
         assert rel_err(new["mel"].numpy(), other["mel"].numpy()) > 100 * BAR
@@ -176,15 +123,10 @@ def test_vctk_example_widths_and_the_specialised_instantiation(nff, B, Ti, steps
     tables (Ti <= 112) and with the tables in global memory (B = 2 generic: the tests above).
     nff = 1: the widths the specialisation is keyed on - it stays keyed on the dimensions, so a speaker model gets LJ AND SPK, in its
     three forms (B = 1 with LDS tables, B = 2, B = 1 with global tables)."""
-    import os
     from satt_amd import ops
     from satt_amd.engine import Engine
-    from satt_amd.hparams import hparams
     from satt_amd.inference import infer, DecodeSession
-    from satt_amd.params import ModelConfig
-    hp = hparams.copy()
-    hp.parse_json(open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples", "vctk", "self-attention-tacotron.json")).read())
-    want = ModelConfig.from_hparams(hp)
+    want = example_config("self-attention-tacotron", "vctk")
     kw = dict(num_speakers=152, speaker_dim=16, speaker_offset=225, n_feed_frame=nff)
     cfg, P = make_params(kw, seed=4)
     for f in (("n_feed_frame",) if nff == 2 else ()) + ("num_speakers", "speaker_dim", "speaker_offset", "dec_prenet", "att_rnn_units", "att1_units", "att2_units", "dec_units",
@@ -196,18 +138,15 @@ def test_vctk_example_widths_and_the_specialised_instantiation(nff, B, Ti, steps
     call = lambda: infer(eng, batch["source"], batch["source_length"], max_steps=steps, min_steps=10 ** 6,
                          speaker_id=torch.as_tensor([225 + 151, 225][:B]))
     form = {(1, 33): ops.MEGA_VAR_TABLES_LDS, (2, 57): ops.MEGA_VAR_TWO_SAMPLES, (1, 140): 0}[(B, Ti)]
-    try:
-        DecodeSession.MEGA, DecodeSession.MEGA_STEPS = True, 8
+    with switches(MEGA=True, MEGA_STEPS=8):
         new = call()
-        ses = eng._decode_sessions[next(reversed(eng._decode_sessions))]
+        ses = last_session(eng)          # (a new engine: the session is new)
         assert ses.mega is not None          # FAILS ON THE PARENT
         assert ops.dec_mega_variant(ses.mega) == form | (ops.MEGA_VAR_LJ if nff == 1 else 0) | ops.MEGA_VAR_SPEAKER
         DecodeSession.MEGA = False
         old = call()
-        assert eng._decode_sessions[next(reversed(eng._decode_sessions))].mega is None
-    finally:
-        DecodeSession.MEGA, DecodeSession.MEGA_STEPS = True, 128
-    same({**{k: new[k].cpu() for k in KEYS}, "steps": new["steps"]}, {**{k: old[k].cpu() for k in KEYS}, "steps": old["steps"]}, "vctk widths, %d fed frame(s), B=%d Ti=%d" % (nff, B, Ti))
+        assert last_session(eng).mega is None
+    same(host_outputs(new, KEYS), host_outputs(old, KEYS), "vctk widths, %d fed frame(s), B=%d Ti=%d" % (nff, B, Ti), KEYS)
 
 
 # ---- 5: float64 oracle

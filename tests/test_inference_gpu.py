@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from common import MEDIUM, SMALL, make_params, rel_err, small_batch
+from decode_common import last_session, switches
 
 pytestmark = pytest.mark.gpu
 
@@ -83,9 +84,7 @@ def test_dropout_on_inference(cfg_kw, B, Ti, steps, fuse):
     bt = torch_ref.batch_to_torch(batch)
     spk = dict(speaker_id=bt["speaker_id"]) if cfg.num_speakers else {}
     espk = dict(speaker_id=batch["speaker_id"]) if cfg.num_speakers else {}
-    old = DecodeSession.FUSE
-    DecodeSession.FUSE = fuse
-    try:
+    with switches(FUSE=fuse):
         ref = torch_ref.infer(Pt, bt["source"], bt["source_length"], ocfg, steps, mv, min_steps=10 ** 6, seed=7, **spk)
         out = infer(eng, bt["source"], bt["source_length"], max_steps=steps, min_steps=10 ** 6, dropout_seed=7, **espk)
         for k in ("mel", "stop", "alignment1"):
@@ -116,8 +115,6 @@ def test_dropout_on_inference(cfg_kw, B, Ti, steps, fuse):
         r3 = infer(eng, bt["source"], bt["source_length"], max_steps=steps, min_steps=10 ** 6, dropout_seed=7, **espk)["mel"]
         assert rel_err(r1, r2) > 1e-3
         assert np.array_equal(r3.detach().cpu().numpy(), out["mel"].detach().cpu().numpy())
-    finally:
-        DecodeSession.FUSE = old
 
 
 @pytest.mark.parametrize("fuse", [True, False])
@@ -135,9 +132,7 @@ def test_multi_hop_decode(cfg_kw, hops, B, Ti, steps, fuse):
     ocfg = torch_ref.Cfg(**kw)
     Pt = torch_ref.to_torch(P)
     bt = torch_ref.batch_to_torch(batch)
-    old = DecodeSession.FUSE
-    DecodeSession.FUSE = fuse
-    try:
+    with switches(FUSE=fuse):
         ref = torch_ref.infer(Pt, bt["source"], bt["source_length"], ocfg, steps, mv, min_steps=10 ** 6)
         out = infer(eng, bt["source"], bt["source_length"], max_steps=steps, min_steps=10 ** 6)
         for k in ("mel", "stop", "alignment1", "alignment2"):
@@ -149,8 +144,6 @@ def test_multi_hop_decode(cfg_kw, hops, B, Ti, steps, fuse):
         for k in ("mel", "stop", "alignment1"):
             e = rel_err(outt[k].detach().cpu().numpy(), fw[k].detach().float().cpu().numpy())
             assert e < 2e-5, (k, e)
-    finally:
-        DecodeSession.FUSE = old
 
 
 def test_free_running_stop_rule():
@@ -322,22 +315,17 @@ def test_bf16_decode_chained_launches(cfg_kw, B, Ti, steps):
     batch = small_batch(cfg, B, Ti, 12, seed=6)
     eng, _ = make_engine(cfg, P, "bf16")
     kw = dict(max_steps=steps, min_steps=10 ** 6)
-    DecodeSession.MEGA = False           # (this test is about the launch-per-layer path)
-    try:
+    with switches("MAX_CHAIN", "FUSE", MEGA=False):          # (this test is about the launch-per-layer path)
         fused = infer(eng, batch["source"], batch["source_length"], **kw)
-        ses = eng._decode_sessions[next(reversed(eng._decode_sessions))]
+        ses = last_session(eng)
         n_fused = ses.kernel_launches
         DecodeSession.MAX_CHAIN = 2          # the two-layer chain (pre-net 0 -> pre-net 1 -> attention LSTM) as well
         deep = infer(eng, batch["source"], batch["source_length"], **kw)
-        assert eng._decode_sessions[next(reversed(eng._decode_sessions))].kernel_launches < n_fused
+        assert last_session(eng).kernel_launches < n_fused
         assert rel_err(deep["mel"].cpu().numpy(), fused["mel"].cpu().numpy()) < 1e-5
         DecodeSession.FUSE = False
         plain = infer(eng, batch["source"], batch["source_length"], **kw)
-        n_plain = eng._decode_sessions[next(reversed(eng._decode_sessions))].kernel_launches
-    finally:
-        DecodeSession.FUSE = True
-        DecodeSession.MAX_CHAIN = 1
-        DecodeSession.MEGA = True
+        n_plain = last_session(eng).kernel_launches
     assert n_fused < n_plain, (n_fused, n_plain)          # the chains were actually taken
     keys = ["mel", "stop", "alignment1"] + (["alignment2"] if cfg.dual else [])
     for k in keys:
@@ -379,21 +367,15 @@ def test_persistent_decode_kernel_equals_the_launch_per_layer_path(form, mode, B
     eng, _ = make_engine(cfg, P, "bf16")
     kw = dict(teacher=torch.as_tensor(batch["mel"])) if mode == "teacher" else \
         dict(max_steps=steps, min_steps=(5 if mode == "stop" else 10 ** 6))
-    try:
-        DecodeSession.MEGA = True
-        DecodeSession.MEGA_STEPS = 32 if form == "tables32" else 8      # (8: several launches and a ragged last one within few steps)
-        DecodeSession.MEGA_FOLD_FEEDBACK = form != "nofold"
+    # (MEGA_STEPS = 8: several launches and a ragged last one within few steps)
+    with switches(MEGA=True, MEGA_STEPS=32 if form == "tables32" else 8, MEGA_FOLD_FEEDBACK=form != "nofold"):
         new = infer(eng, batch["source"], batch["source_length"], **kw)
-        ses = eng._decode_sessions[next(reversed(eng._decode_sessions))]
+        ses = last_session(eng)
         assert ses.mega is not None and ses.kernel_launches == 1          # the persistent kernel was actually taken
         again = infer(eng, batch["source"], batch["source_length"], **kw)  # the cached session, reset
         DecodeSession.MEGA = False
         old = infer(eng, batch["source"], batch["source_length"], **kw)
-        assert eng._decode_sessions[next(reversed(eng._decode_sessions))].mega is None
-    finally:
-        DecodeSession.MEGA = True
-        DecodeSession.MEGA_STEPS = 128
-        DecodeSession.MEGA_FOLD_FEEDBACK = True
+        assert last_session(eng).mega is None
     assert new["steps"] == old["steps"] == (7 if mode == "stop" else steps)
     for k in ("mel", "stop", "alignment1", "alignment2"):
         e = rel_err(new[k].cpu().numpy(), old[k].cpu().numpy())
@@ -414,12 +396,9 @@ def test_persistent_decode_kernel_hands_over_to_the_launch_per_layer_path_and_ba
     K, steps = 8, 24
     batch = small_batch(cfg, B, Ti, steps * cfg.r, seed=6)
     eng, _ = make_engine(cfg, dict(P), "bf16")
-    try:
-        DecodeSession.MEGA_STEPS = K
+    with switches(MEGA_STEPS=K):
         ref = infer(eng, batch["source"], batch["source_length"], max_steps=steps, min_steps=10 ** 6)
-    finally:
-        DecodeSession.MEGA_STEPS = 128
-    ses = eng._decode_sessions[next(reversed(eng._decode_sessions))]
+    ses = last_session(eng)
     assert ses.mega is not None and ses.K == K
     ses.reset()                      # (memories, context tables and folded weights of the utterance stay in place)
     ses.replay()
