@@ -503,7 +503,7 @@ def decoder(lstm_out, sa_out, source_length, target, P, cfg, training, seed, spe
 
 
 def infer(P, source, source_length, cfg, max_steps, bn_moving, speaker_id=None, teacher=None, min_steps=10,
-          stop_threshold=0.5, teacher_alignments=None, seed=0):
+          stop_threshold=0.5, teacher_alignments=None, seed=0, alpha0=None):
     """Step-by-step decode with is_training=False: RNNTransformer else-branch (reference
     modules/module.py:762-778) = per step, DecoderRNNV2 cell, the decoder output appended to a history
     (RNNStateHistoryWrapper, modules/rnn_wrappers.py:47-80), the causal SelfAttentionTransformer re-run over the WHOLE
@@ -514,6 +514,8 @@ def infer(P, source, source_length, cfg, max_steps, bn_moving, speaker_id=None, 
     reference's own test property says this equals the batched training-branch output (transformer_test.py:40-82).
     teacher_alignments=(a1, a2) [B,T,Ti]: forced-alignment mode (reference modules/teacher_forcing_attention.py:13-78,
     models/models.py:411-428): both mechanisms return the given alignment of the step instead of their own.
+    alpha0=[B] rows: the forward variable starts one-hot at row alpha0[b] instead of row 0 (None: row 0, the reference's
+    initial_alignments) - a start from which a short run weights high memory rows.
     Zoneout in interpolation mode, dropout off - except the plain decoder PreNet layers under apply_dropout_on_inference
     (mask of row (b, t) of a [B, max_steps, units] activation from `seed`) -, BatchNorm on moving statistics."""
     training = False
@@ -535,7 +537,9 @@ def infer(P, source, source_length, cfg, max_steps, bn_moving, speaker_id=None, 
     z = lambda n: lstm_out.new_zeros(B, n)
     c0, h0, c1, h1, c2, h2, attn = z(A), z(A), z(D), z(D), z(D), z(D), z(cfg.ctx_dim)
     st1 = (z(Ti), torch.cat([lstm_out.new_ones(B, 1), z(Ti - 1)], dim=1), 0.5)
-    x_in = z(feed)                                                   # go frame
+    if alpha0 is not None:
+        st1 = (st1[0], F.one_hot(torch.as_tensor(alpha0, dtype=torch.int64), Ti).to(lstm_out.dtype), 0.5)
+    x_in = z(feed)                                                  # go frame
     hist, mels, stops, al1, al2 = [], [], [], [], []
     for t in range(max_steps):
         pre = prenet(x_in, P, "dec.prenet", len(cfg.dec_prenet), cfg.dec_prenet_drop, training, seed,

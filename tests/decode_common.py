@@ -299,6 +299,81 @@ def teacher_rows(B, steps, Ti, lens, dual, masked=True, seed=3, sharp=1):
     return (ta[0], ta[1] if dual else None)
 
 
+# ---- inputs that look at the memory rows (tests/test_decode_rows_{cpu,gpu}.py, tests/golden/make_decode_rows_golden.py)
+# the kernel's row ownership changes at these rows: 32 rows of energies per workgroup at the most, 64 rows per wave (softmax, recursion,
+# teacher rows, gather_vec), the table forms at 112 / 113 (B = 1) and 128, the second table row of a row lane from 128 on
+FOCUS_BOUNDARIES = (32, 64, 96, 112, 128, 192, 224)
+ROWS_STEPS = 16          # the steps of the memory-length suites: two launches of 8
+
+
+def focus_visits(length):
+    """the rows a sample of `length` rows must have been focused on: both ends and both sides of every boundary below the length"""
+    rows = [0, 1, length - 1, length - 2] + [r for b in FOCUS_BOUNDARIES if b < length for r in (b - 1, b)]
+    return sorted({r for r in rows if 0 <= r < length})
+
+
+def focus_steps(lens, dual):
+    """ROWS_STEPS, or - the baseline model above 224 rows, whose one mechanism has 18 rows to visit - 24 (three launches of 8)"""
+    need = max(len(focus_visits(int(n))) for n in lens)
+    return ROWS_STEPS if need <= ROWS_STEPS * (2 if dual else 1) else 24
+
+
+def focus_plan(B, steps, lens, dual):
+    """int64 [mechanisms, B, steps]: the focus row of every (mechanism, sample, step).  Mechanism 1 walks the visit list of its
+    sample from entry b on, mechanism 2 half a list ahead of it: together they cover the list, and never the same row at one step"""
+    plan = np.zeros((2 if dual else 1, B, steps), np.int64)
+    for b in range(B):
+        v = focus_visits(int(lens[b]))
+        n = len(v)
+        assert 2 <= n <= steps * plan.shape[0], (int(lens[b]), n, steps)
+        for m in range(plan.shape[0]):
+            plan[m, b] = [v[(t + b + m * (n // 2)) % n] for t in range(steps)]
+    return plan
+
+
+def focus_rows(B, steps, Ti, lens, dual, weight=0.6, seed=5, plan=None):
+    """forced-alignment teacher histories in the shape teacher_rows returns, that LOOK at single rows: every row is a random masked
+    background of mass 1 - weight plus `weight` on the focus row of focus_plan (plan: another one).  The context of such a row is
+    weight * memory[focus] + a near-mean rest, so a mix-up of two rows inside the kernel's tables moves the frame of that step"""
+    g = torch.Generator().manual_seed(seed)
+    plan = focus_plan(B, steps, lens, dual) if plan is None else plan
+    mask = (torch.arange(Ti)[None, None, :] < torch.as_tensor(np.asarray(lens, np.int64))[:, None, None]).double()
+    ta = []
+    for m in range(2 if dual else 1):
+        a = torch.rand(B, steps, Ti, generator=g, dtype=torch.float64) * mask
+        a = (1.0 - weight) * a / a.sum(-1, keepdim=True)
+        a.scatter_add_(2, torch.as_tensor(plan[m])[:, :, None], torch.full((B, steps, 1), weight, dtype=torch.float64))
+        ta.append(a.float())
+    return (ta[0], ta[1] if dual else None)
+
+
+@contextlib.contextmanager
+def seeded_start(rows):
+    """DecodeSession.reset inside the body: the reset as it is, then the one-hot start of the forward variable moved from row 0 to
+    rows[b] of sample b - in alpha_state[0], which the persistent kernel and the launch-per-layer steps both read at the first step,
+    and in a group session's _galpha_state[:, 0] (group g holds samples 2 g, 2 g + 1; the padding sample starts where the last one
+    does).  A forward-attention run moves at most one row per step from where it starts: seeded, 16 steps weight the high rows"""
+    from satt_amd.inference import DecodeSession
+    real = DecodeSession.reset
+
+    def reset(self):
+        real(self)
+        at = [int(r) for r in rows]
+        assert len(at) == self.B and all(0 <= r < self.Ti for r in at), (at, self.B, self.Ti)
+        self.alpha_state[0].zero_()
+        for b, r in enumerate(at):
+            self.alpha_state[0, b, r] = 1.0
+        if self.mega_groups is not None:
+            self._galpha_state[:, 0].zero_()
+            for b in range(self.Ba):
+                self._galpha_state[b // 2, 0, b % 2, at[min(b, self.B - 1)]] = 1.0
+    DecodeSession.reset = reset
+    try:
+        yield
+    finally:
+        DecodeSession.reset = real
+
+
 # ---- the frozen float64 decode vectors (tests/golden/decode_ljspeech_*.npz)
 # (mel abs, stop abs, alignment rows abs, per-step mean |mel| abs, argmax path agreement)
 # measured (MI355X, r5): bf16 mel 7.4e-4 (the float64 oracle with bf16-rounded weights: 7.7e-4 - the path sits AT the rounding floor
@@ -308,13 +383,21 @@ GOLDEN_BARS = {"bf16": dict(mel=2.2e-3, stop=4.5e-4, align=1.2e-3, drift=8e-5, p
                "f32": dict(mel=6e-4, stop=7e-5, align=2.5e-4, drift=3.5e-5, path=0.995)}
 
 
-def golden_engine(z, prec, stop_shift=0.0, case=""):
-    """(cfg, engine) of the fixture `z`: its parameters (sharpened for the *_sharp cases), its moving statistics, precision `prec`"""
+def golden_engine(z, prec, stop_shift=0.0, case="", cfg_kw=None, sharpen=None):
+    """(cfg, engine) of the fixture `z`: its parameters (sharpened for the *_sharp cases), its moving statistics, precision `prec`;
+    cfg_kw / sharpen: the model and the sharpening of a tests/golden/decode_rows_*.npz case, whose parameters are common.make_params'"""
     from satt_amd import ops
     from satt_amd.engine import Engine
     from satt_amd.params import ModelConfig, init_params
-    cfg = ModelConfig()
-    P = dict(init_params(cfg, int(z["param_seed"])))
+    if cfg_kw is None:
+        cfg = ModelConfig()
+        P = dict(init_params(cfg, int(z["param_seed"])))
+    else:          # (make_decode_rows_golden.case_params)
+        cfg, P = make_params(cfg_kw, seed=int(z["param_seed"]), bias_noise=0.0)
+        P = dict(P)
+    if sharpen:
+        from golden.make_bench_golden import sharpen_params
+        P = sharpen_params(P, **sharpen)
     if case.endswith("_sharp"):
         from golden.make_bench_golden import sharpen_params
         from golden.make_decode_golden import CASES

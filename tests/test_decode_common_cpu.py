@@ -7,7 +7,7 @@ import pytest
 
 from decode_common import (LAUNCHERS, Launch, block, example_config, expected_variant, forced, groups, options, recording, switches)
 
-SUITES = ("speaker", "options", "single", "forced", "groups", "forced_groups")
+SUITES = ("speaker", "options", "single", "forced", "groups", "forced_groups", "rows")
 
 
 def test_switches_put_back_what_they_found():
@@ -70,7 +70,8 @@ def models():
 @pytest.mark.parametrize("kw", models())
 def test_expected_variant_agrees_with_the_library(kw, monkeypatch):
     """the shapes of the suites - B = 1 with the context tables in LDS (Ti = 33) and in global memory (113, 140), B = 2 with Ti = 57,
-    groups of 2 and 3 blocks -, free and forced, with the option and forced blocks the session would pass.  Where the session stays
+    groups of 2 and 3 blocks; tests/test_decode_rows_gpu.py: both ends of the range (2, 256), both sides of 112 / 113 and 128 / 129,
+    groups of 3 and 8 blocks at Ti = 256 -, free and forced, with the option and forced blocks the session would pass.  Where the session stays
     off the kernel (-1: the single-source form with the agent or live dropout) the library refuses the block it would be asked with."""
     from satt_amd import ops
     from satt_amd.params import ModelConfig
@@ -81,7 +82,7 @@ def test_expected_variant_agrees_with_the_library(kw, monkeypatch):
         agent, drop = cfg.transition_agent and not frc, cfg.apply_dropout_on_inference
         opt = options(agent, drop) if (agent or drop) else None
         f = forced(two=cfg.dual) if frc else None
-        for B, Ti in ((1, 33), (1, 113), (1, 140), (2, 57)):
+        for B, Ti in ((1, 33), (1, 113), (1, 140), (2, 57), (1, 2), (1, 112), (1, 128), (1, 129), (1, 256), (2, 64), (2, 129), (2, 256)):
             want = expected_variant(cfg, B, Ti, forced=frc)
             p = block(cfg, B, Ti)
             assert ops.dec_mega_forced_variant(p, opt, f) == want, (frc, B, Ti)
@@ -90,10 +91,10 @@ def test_expected_variant_agrees_with_the_library(kw, monkeypatch):
                 if opt is None:
                     assert ops.dec_mega_variant(p) == want, (B, Ti)
             seen.add(want)
-        for n in (2, 3):
-            arr = groups([block(cfg) for _ in range(n)], opt)
+        for n, Ti in ((2, 57), (3, 57), (3, 256), (8, 256)):
+            arr = groups([block(cfg, Ti=Ti) for _ in range(n)], opt)
             for B in (2 * n - 1, 2 * n):
-                want = expected_variant(cfg, B, 57, forced=frc, groups=True)
+                want = expected_variant(cfg, B, Ti, forced=frc, groups=True)
                 assert ops.dec_mega_groups_forced_variant(arr, f) == want, (frc, n)
                 if not frc:
                     assert ops.dec_mega_groups_variant(arr) == want, n
