@@ -283,13 +283,14 @@ def decoder(batch, lstm_out, sa_out, P, cfg, training, seed):
     return mel, stop, al1, al2, dec_out
 
 
-def forward(P, batch, cfg, training=True, seed=0):
-    """model_fn forward + losses (models/models.py:278-482)."""
+def forward(P, batch, cfg, training=True, seed=0, loss_type="l1"):
+    """model_fn forward + losses (models/models.py:278-482); loss_type = hparams spec_loss_type (l1 or mse)."""
     P = {k: np.asarray(v, dtype=np.float64) for k, v in P.items()}
     lstm_out, sa_out, enc_align = encoder(batch, P, cfg, training, seed)
     mel, stop, al1, al2, dec_out = decoder(batch, lstm_out, sa_out, P, cfg, training, seed)
     w = batch["spec_loss_mask"][:, :, None]
-    mel_loss = (np.abs(mel - batch["mel"]) * w).sum() / (mel.shape[-1] * batch["spec_loss_mask"].sum())
+    d = mel - batch["mel"]
+    mel_loss = ((np.abs(d) if loss_type == "l1" else d * d) * w).sum() / (mel.shape[-1] * batch["spec_loss_mask"].sum())
     x = stop[..., 0]; z = batch["done"]
     bce = np.maximum(x, 0) - x * z + np.log1p(np.exp(-np.abs(x)))
     done_loss = (bce * batch["binary_loss_mask"]).sum() / batch["binary_loss_mask"].sum()

@@ -611,8 +611,9 @@ def postnet_v2(mel, P, cfg, training, seed, bn_moving=None):
     return mel + (x @ P["postnet.proj.W"] + P["postnet.proj.b"])
 
 
-def forward(P, batch, cfg, training=True, seed=0, collect=None):
-    """model_fn forward, TRAIN mode (reference models/models.py:278-482)."""
+def forward(P, batch, cfg, training=True, seed=0, collect=None, loss_type="l1"):
+    """model_fn forward, TRAIN mode (reference models/models.py:278-482).  loss_type: hparams spec_loss_type ("l1" or
+    "mse"), used by the decoder output's spec_loss and by the PostNetV2 one."""
     spk = None
     if cfg.num_speakers > 0:
         spk = P["speaker_embedding"][batch["speaker_id"] - cfg.speaker_offset]
@@ -620,13 +621,13 @@ def forward(P, batch, cfg, training=True, seed=0, collect=None):
                                           collect=collect)
     mel, stop, al1, al2, dec_align = decoder(lstm_out, sa_out, batch["source_length"], batch["mel"], P, cfg,
                                              training, seed, spk, collect)
-    mel_loss, done_loss = losses(mel, stop, batch)
+    mel_loss, done_loss = losses(mel, stop, batch, loss_type)
     out = dict(mel=mel, stop=stop, alignment1=al1, alignment2=al2, enc_alignment=enc_align,
                dec_alignment=dec_align, lstm_out=lstm_out, sa_out=sa_out,
                mel_loss=mel_loss, done_loss=done_loss, loss=mel_loss + done_loss)
     if cfg.use_postnet_v2:                   # extra spec_loss term (reference models/models.py:116-118)
         post = postnet_v2(mel, P, cfg, training, seed)
-        pl, _ = losses(post, stop, batch)
+        pl, _ = losses(post, stop, batch, loss_type)
         out.update(mel_postnet=post, postnet_mel_loss=pl, loss=out["loss"] + pl)
     if cfg.l2_weight > 0 and training:       # modules/regularizers.py:11-18 with the blacklist of models/models.py:109-111
         reg = cfg.l2_weight * sum(0.5 * (P[k] ** 2).sum() for k in l2_regularized(P))

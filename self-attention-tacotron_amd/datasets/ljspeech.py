@@ -370,21 +370,24 @@ class BatchedDataset:
             q = queue.Queue(maxsize=n)
             END, stop = object(), threading.Event()
 
+            def put(x):
+                while not stop.is_set():
+                    try:
+                        q.put(x, timeout=0.1)
+                        return True
+                    except queue.Full:
+                        continue
+                return False
+
             def work():
                 try:
                     for b in make():
-                        while not stop.is_set():
-                            try:
-                                q.put(b, timeout=0.1)
-                                break
-                            except queue.Full:
-                                continue
-                        if stop.is_set():
+                        if not put(b):
                             return
-                    q.put(END)
+                    put(END)
                 except BaseException as e:          # surfaced in the consumer, never swallowed
-                    q.put(e)
-            th = threading.Thread(target=work, daemon=True)
+                    put(e)
+            th = threading.Thread(target=work, daemon=True, name="satt-prefetch")
             th.start()
             try:
                 while True:
@@ -395,7 +398,14 @@ class BatchedDataset:
                         raise b
                     yield b
             finally:
+                # the consumer is done (exhausted, closed, or dropped by a train loop that left at max_steps): the worker must be
+                # GONE before the caller goes on.  Left running, it can be inside native code (the ring's event wait, a pinned
+                # allocation) when the interpreter finalises; CPython then ends a daemon thread by unwinding it, and the unwinding
+                # through a C++ frame aborts the process ("terminate called without an active exception") after all work is done.
+                # It looks at `stop` after every batch and every 0.1 s while the queue is full; the bound is for a stuck reader.
                 stop.set()
+                if th is not threading.current_thread():
+                    th.join(timeout=30)
         return BatchedDataset(gen, self._hparams)
 
     def merge_target_to_source(self):

@@ -60,13 +60,13 @@ def rel_err(a, b):
     return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-12))
 
 
-def oracle_run(cfg_kw, P, batch, training=True, seed=0, grads=True, dalign=None):
-    """float64 torch oracle forward (+ autograd gradients of the loss wrt every parameter)."""
+def oracle_run(cfg_kw, P, batch, training=True, seed=0, grads=True, dalign=None, loss_type="l1"):
+    """float64 torch oracle forward (+ autograd gradients of the loss wrt every parameter); loss_type = spec_loss_type."""
     ocfg = oracle_cfg(cfg_kw)
     Pt = torch_ref.to_torch(P, torch.float64, requires_grad=grads)
     bt = torch_ref.batch_to_torch(batch)
     col = {}
-    out = torch_ref.forward(Pt, bt, ocfg, training, seed, collect=col)
+    out = torch_ref.forward(Pt, bt, ocfg, training, seed, collect=col, loss_type=loss_type)
     g = None
     if grads:
         loss = out["loss"]

@@ -138,6 +138,31 @@ def test_fluent_tail_prefetch_and_merge_target_to_source(tmp_path):
         factory_module.create_from_tfrecord_files(src, tgt, h)
 
 
+def test_prefetch_worker_is_gone_when_the_consumer_leaves(tmp_path):
+    """a train loop that leaves an endless prefetched dataset at max_steps drops its iterator: the background thread must have
+    ended by then (a daemon thread that is inside native code when the interpreter finalises aborts the process at exit),
+    whether the queue was full, the worker was reading, or the dataset had just run out"""
+    import threading
+    h = hp(outputs_per_step=2, batch_size=2, average_mel_level_db=[0.0], stddev_mel_level_db=[1.0])
+    src, tgt = _write_corpus(tmp_path, [(5, 9), (8, 14), (3, 12), (6, 11)])
+    workers = lambda: [t for t in threading.enumerate() if t.name == "satt-prefetch"]
+    assert not workers()
+    for repeat, take in ((True, 1), (True, 5), (False, 1), (False, 2)):
+        ds = ljspeech.dataset_factory(src, tgt, h).prepare_and_zip()
+        ds = ds.repeat() if repeat else ds
+        n = 0
+        for b in ds.group_by_batch().prefetch(1):
+            assert len(workers()) == 1
+            n += 1
+            if n == take:
+                break
+        assert n == take and not workers()
+    it = iter(ljspeech.dataset_factory(src, tgt, h).prepare_and_zip().repeat().group_by_batch().prefetch(2))
+    next(it)
+    it.close()
+    assert not workers()
+
+
 def test_create_from_tfrecord_files_interleaves_multi_record_files(tmp_path):
     """reference datasets/ljspeech/dataset.py:94-110: parallel_interleave(cycle_length, sloppy=False) - one record from
     each of `cycle_length` open files in turn"""

@@ -13,11 +13,11 @@ from decode_common import last_session, switches
 pytestmark = pytest.mark.gpu
 
 
-def make_engine(cfg, P, prec="f32"):
+def make_engine(cfg, P, prec="f32", loss_type="l1"):
     from satt_amd import ops
     from satt_amd.engine import Engine
     ops.set_precision(prec)
-    eng = Engine(cfg, "cuda", params=P, rng_seed=7)
+    eng = Engine(cfg, "cuda", params=P, rng_seed=7, loss_type=loss_type)
     g = np.random.default_rng(11)
     mv = {}
     for name, (mean, var) in eng.bn.items():        # non-trivial moving statistics, shared with the oracle
@@ -218,6 +218,33 @@ def test_eval_double_pass_matches_oracle(cfg_kw, B, Ti, Tm):
             print(k + name, got, want)
             assert abs(got - want) < 5e-4 * max(1.0, abs(want)), (k + name, got, want)
     assert abs(ev["loss"] - (ev["mel_loss"] + ev["done_loss"])) < 1e-5
+
+
+def test_eval_double_pass_mse_loss_matches_oracle():
+    """the evaluation losses of an Engine(loss_type="mse") (spec_loss_type "mse": the squared-error branch of the two-kernel
+    loss form) against torch_ref.losses(..., "mse") on the oracle's free run and teacher-fed pass; the L1 value is far away"""
+    from oracle import torch_ref
+    from satt_amd.inference import evaluate
+    cfg_kw, B, Ti, Tm = MEDIUM, 4, 33, 28
+    cfg, P = make_params(cfg_kw, seed=2)
+    batch = small_batch(cfg, B, Ti, Tm, seed=5)
+    eng, mv = make_engine(cfg, P, loss_type="mse")
+    assert eng.loss_l2
+    ocfg = torch_ref.Cfg(**cfg_kw)
+    Pt = torch_ref.to_torch(P)
+    bt = torch_ref.batch_to_torch(batch)
+    Td = Tm // cfg.r
+    free = torch_ref.infer(Pt, bt["source"], bt["source_length"], ocfg, Td, mv, min_steps=10 ** 9)
+    tf = torch_ref.infer(Pt, bt["source"], bt["source_length"], ocfg, None, mv, teacher=bt["mel"])
+    ev = evaluate(eng, batch)
+    for name, o in (("", free), ("_with_teacher", tf)):
+        ml, dl = torch_ref.losses(o["mel"], o["stop"], bt, "mse")
+        l1, _ = torch_ref.losses(o["mel"], o["stop"], bt, "l1")
+        assert abs(float(ml) - float(l1)) > 1e-2 * float(ml)
+        for k, v in (("mel_loss", ml), ("done_loss", dl), ("loss", ml + dl)):
+            got, want = ev[k + name], float(v)
+            print(k + name, got, want)
+            assert abs(got - want) < 5e-4 * max(1.0, abs(want)), (k + name, got, want)
 
 
 @pytest.mark.parametrize("cfg_kw,B,Ti,steps", [(MEDIUM, 4, 33, 14), (SMALL, 3, 9, 12)])

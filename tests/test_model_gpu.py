@@ -10,11 +10,11 @@ from common import MEDIUM, SMALL, make_params, oracle_run, rel_err, small_batch
 pytestmark = pytest.mark.gpu
 
 
-def run_engine(cfg, P, batch, seed, prec, dalign=None, clusters=True):
+def run_engine(cfg, P, batch, seed, prec, dalign=None, clusters=True, loss_type="l1"):
     from satt_amd import ops
     from satt_amd.engine import Engine
     ops.set_precision(prec)
-    eng = Engine(cfg, "cuda", params=P, rng_seed=seed)
+    eng = Engine(cfg, "cuda", params=P, rng_seed=seed, loss_type=loss_type)
     eng.use_clusters = clusters
     b = eng.to_device_batch(batch)
     eng.zero_grad()
@@ -242,6 +242,35 @@ def test_f32_parity_postnet_v2():
     eng, out, grads = run_engine(cfg, P, batch, 7, "f32", clusters=True)
     errs = report(out, {**ref, "dec_out": col["dec_out"]}, grads, gref,
                   ["mel", "mel_postnet", "postnet_mel_loss", "loss", "stop"])
+    bad = {k: e for k, e in errs.items() if not (e < 2e-4)}
+    assert not bad, bad
+
+
+POSTNET_V2_KW = dict(SMALL, use_postnet_v2=True, num_postnet_v2_layers=3, postnet_v2_kernel_size=5,
+                     postnet_v2_out_channels=16, postnet_v2_drop_rate=0.5)      # the configuration of test_f32_parity_postnet_v2
+
+
+@pytest.mark.parametrize("model,B,Ti,Tm", [("dual", 5, 37, 46), ("baseline", 5, 37, 46), ("postnet_v2", 3, 9, 12)])
+def test_f32_parity_mse_loss(model, B, Ti, Tm):
+    """spec_loss_type="mse" (reference hparams "l1 or mse"; Engine.loss_l2) end to end: the squared-error branches of the
+    fused training loss and of the PostNetV2 loss (d*d in the sums, 2*d in the gradients) against the float64 oracle run
+    with the same loss type: outputs, the three losses (+ postnet_mel_loss) and every parameter gradient."""
+    kw = {"dual": MEDIUM, "baseline": baseline_kw(MEDIUM), "postnet_v2": POSTNET_V2_KW}[model]
+    cfg, P = make_params(kw, seed=1)
+    batch = small_batch(cfg, B, Ti, Tm, seed=3)
+    ref, col, gref = oracle_run(kw, P, batch, True, seed=7, loss_type="mse")
+    _, _, gl1 = oracle_run(kw, P, batch, True, seed=7)
+    # an engine that silently ran L1 would miss the gradients by far more than the bar, not only the loss value
+    differ = rel_err(gl1["dec.out.W"], gref["dec.out.W"])
+    print("oracle dec.out.W gradient, L1 against MSE: rel diff %.3e" % differ)
+    assert differ > 1e-2, differ
+    eng, out, grads = run_engine(cfg, P, batch, 7, "f32", clusters=True, loss_type="mse")
+    assert eng.loss_l2
+    keys = ["alignment1", "dec_out", "mel", "stop", "loss", "mel_loss", "done_loss"]
+    if model == "postnet_v2":
+        keys += ["mel_postnet", "postnet_mel_loss"]
+    errs = report(out, {**ref, "dec_out": col["dec_out"]}, grads, gref, keys)
+    assert set(grads) == set(gref)
     bad = {k: e for k, e in errs.items() if not (e < 2e-4)}
     assert not bad, bad
 

@@ -53,6 +53,33 @@ def test_numpy_and_torch_restatements_agree_eval_mode(kw):
         assert abs(c1["loss"] - c["loss"]) > 1e-6
 
 
+def test_numpy_and_torch_restatements_agree_mse_loss():
+    """spec_loss_type="mse" (reference hparams "l1 or mse"): the two restatements agree on the squared-error spec loss, it
+    is the hand-computed masked mean of squares, it differs from the L1 value, and the default stays L1."""
+    cfg, P = make_params(SMALL, seed=5)
+    batch = small_batch(cfg, 2, 7, 10, seed=9)
+    Pt, bt = torch_ref.to_torch(P), torch_ref.batch_to_torch(batch)
+    a = numpy_ref.forward(P, batch, oracle_cfg(SMALL), True, seed=3, loss_type="mse")
+    b = torch_ref.forward(Pt, bt, oracle_cfg(SMALL), True, 3, loss_type="mse")
+    l1 = numpy_ref.forward(P, batch, oracle_cfg(SMALL), True, seed=3)
+    for k in ("mel_loss", "done_loss", "loss"):
+        assert abs(float(b[k]) - a[k]) < 1e-12, k
+    w = batch["spec_loss_mask"][:, :, None]
+    ml = ((a["mel"] - batch["mel"]) ** 2 * w).sum() / (cfg.num_mels * batch["spec_loss_mask"].sum())
+    assert abs(ml - a["mel_loss"]) < 1e-12
+    assert abs(a["mel_loss"] - l1["mel_loss"]) > 1e-3 and a["done_loss"] == l1["done_loss"]
+    assert l1["loss"] == numpy_ref.forward(P, batch, oracle_cfg(SMALL), True, seed=3, loss_type="l1")["loss"]
+    assert float(torch_ref.forward(Pt, bt, oracle_cfg(SMALL), True, 3)["loss"]) == \
+        float(torch_ref.forward(Pt, bt, oracle_cfg(SMALL), True, 3, loss_type="l1")["loss"])
+    # the PostNetV2 spec loss follows the same type
+    kw = dict(SMALL, use_postnet_v2=True)
+    cfg2, P2 = make_params(kw, seed=5)
+    c = torch_ref.forward(torch_ref.to_torch(P2), bt, oracle_cfg(kw), True, 3, loss_type="mse")
+    wt = bt["spec_loss_mask"][:, :, None]
+    pl = ((c["mel_postnet"] - bt["mel"]) ** 2 * wt).sum() / (cfg2.num_mels * bt["spec_loss_mask"].sum())
+    assert abs(float(pl) - float(c["postnet_mel_loss"])) < 1e-12
+
+
 def test_torch_gradients_match_numpy_finite_differences():
     cfg, P = make_params(SMALL, seed=2)
     batch = small_batch(cfg, 2, 6, 8, seed=4)
