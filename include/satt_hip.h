@@ -923,6 +923,39 @@ int satt_dec_stop_scan(const float* yout, int B, int rows, int NO, int t0, int n
 int satt_dec_self_attn(const float* kvq, float* out, const int* step, int B, int Td, int D, int heads, float scale,
                        void* stream);
 
+/* ---- log-mel spectrograms of a batch of utterances in one launch (csrc/melspec.hip; the reference's Audio.melspectrogram,
+ * utils/audio.py:51-73 = librosa.stft defaults).  Utterance u is signal[sample_offsets[u] .. sample_offsets[u + 1]) (n samples, fp32)
+ * and owns the output rows frame_offsets[u] .. frame_offsets[u + 1]; the caller sets frame_offsets[u + 1] - frame_offsets[u] =
+ * 1 + n / hop and passes only utterances of n >= n_fft / 2 + 1 samples (rows of anything else are left unwritten; nothing is read
+ * or written out of bounds whatever the offsets hold).  Frame t covers positions [t hop, t hop + n_fft) of the signal padded by
+ * n_fft / 2 reflected samples on either side (the edge sample not repeated; the index is reflected in the kernel).
+ *   mag[row, k] = |rfft(window * frame)[k]|, k < n_fft / 2 + 1                       (optional: NULL keeps it on chip)
+ *   mel[row, m] = 20 log10(max(1e-5, sum_j band_weight[band_offset[m] + j] * mag[row, band_start[m] + j])) - ref_level_db
+ * Tables (device memory, built by the caller in float64 and rounded once):
+ *   window [n_fft]: the periodic Hann window of `win` points behind (n_fft - win) / 2 zeros, zeros behind it;
+ *   twiddle [n_fft][2]: (cos, -sin)(2 pi k / n_fft);
+ *   band_start [num_mels], band_offset [num_mels + 1], band_weight [n_band_weights = band_offset[num_mels]]: the non-zero run of
+ *   every row of the mel basis (Slaney), ascending bins.
+ * satt_melspec_supported (no GPU needed) == 1: n_fft in {512, 1024, 2048, 4096}, 16 <= win <= n_fft, 1 <= hop <= n_fft,
+ * 1 <= num_mels <= 128; anything else SATT_E_UNSUPPORTED.  fp32, an FFT held in LDS, four frames per workgroup, no atomics and no
+ * cross-workgroup exchange: two launches on the same input are bit-identical, and an utterance's rows do not depend on its batch. */
+typedef struct {
+  int n_fft, win, hop, num_mels, n_utts, n_band_weights;
+  int64_t total_samples, total_frames;
+  const float* signal;
+  const int64_t* sample_offsets; /* [n_utts + 1] */
+  const int64_t* frame_offsets;  /* [n_utts + 1] */
+  const float* window;
+  const float* twiddle;
+  const int* band_start;
+  const int* band_offset;
+  const float* band_weight;
+  float ref_level_db;
+  float* mel; /* [total_frames, num_mels] */
+  float* mag; /* [total_frames, n_fft / 2 + 1] or NULL */
+} satt_melspec_params;
+int satt_melspec_supported(int n_fft, int win, int hop, int num_mels);
+int satt_melspec(const satt_melspec_params* p, void* stream);
 
 #ifdef __cplusplus
 }

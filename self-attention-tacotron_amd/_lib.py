@@ -144,6 +144,15 @@ class DecMegaGroup(C.Structure):
     _fields_ = [("p", DecMegaParams), ("o", DecMegaOptParams), ("has_opt", C.c_int), ("b0", C.c_int)]
 
 
+class MelspecParams(C.Structure):
+    """satt_melspec_params (include/satt_hip.h): log-mel spectrograms of a batch of utterances"""
+    _fields_ = ([(n, C.c_int) for n in ("n_fft", "win", "hop", "num_mels", "n_utts", "n_band_weights")] +
+                [("total_samples", c_i64), ("total_frames", c_i64)] +
+                [(n, C.c_void_p) for n in ("signal", "sample_offsets", "frame_offsets", "window", "twiddle", "band_start",
+                                           "band_offset", "band_weight")] +
+                [("ref_level_db", C.c_float), ("mel", C.c_void_p), ("mag", C.c_void_p)])
+
+
 # name -> (restype, argtypes); must list EVERY symbol declared in include/satt_hip.h
 _P = C.c_void_p
 _I = C.c_int
@@ -272,6 +281,8 @@ SIGNATURES = {
     "satt_dec_mega_groups_forced": (_I, [C.POINTER(DecMegaGroup), _P, _I, C.POINTER(DecMegaForcedParams), _P]),
     "satt_dec_stop_scan": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _P, _P]),
     "satt_dec_self_attn": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "satt_melspec_supported": (_I, [_I, _I, _I, _I]),
+    "satt_melspec": (_I, [C.POINTER(MelspecParams), _P]),
     "satt_l2_reg": (_I, [_P, _P, _P, _I, _F, _P, _P, _P]),
     "satt_sumsq": (_I, [_P, c_i64, _P, _P]),
     "satt_sumsq_state_floats": (_I, []),

@@ -433,6 +433,34 @@ def rows_time_sum(dy, lengths, dv, B, T, t0=0):
     _lib.check(_lib.lib().satt_rows_time_sum(_p(dy), _ld(dy), _p(lengths), _p(dv), _ld(dv), B, T, N, t0, _s()), "rows_time_sum")
 
 
+def melspec_supported(n_fft, win, hop, num_mels):
+    """True when satt_melspec takes these STFT parameters (host-only: needs the library, not a GPU)"""
+    return bool(_lib.lib().satt_melspec_supported(int(n_fft), int(win), int(hop), int(num_mels)))
+
+
+def melspec(signal, sample_offsets, frame_offsets, n_fft, win, hop, window, twiddle, band_start, band_offset, band_weight,
+            ref_level_db, mel, mag=None):
+    """log-mel spectrograms of a batch of utterances in one launch (csrc/melspec.hip).  signal: fp32 [total samples], utterance u
+    at sample_offsets[u] .. sample_offsets[u + 1] (int64 [U + 1]), its rows of mel [total frames, num_mels] (and of the optional
+    mag [total frames, n_fft / 2 + 1]) at frame_offsets[u] .. frame_offsets[u + 1] (int64 [U + 1], 1 + n // hop rows each).  The
+    tables are those of utils/audio.py MelspecTables.  Parameters outside satt_melspec_supported raise."""
+    assert signal.dtype == torch.float32 and signal.dim() == 1 and signal.is_contiguous()
+    assert sample_offsets.dtype == torch.int64 and frame_offsets.dtype == torch.int64
+    assert sample_offsets.numel() == frame_offsets.numel() >= 2
+    assert window.dtype == torch.float32 and window.numel() == n_fft and twiddle.dtype == torch.float32 and twiddle.numel() == 2 * n_fft
+    assert band_start.dtype == torch.int32 and band_offset.dtype == torch.int32 and band_weight.dtype == torch.float32
+    num_mels = band_start.numel()
+    assert band_offset.numel() == num_mels + 1
+    assert mel.dtype == torch.float32 and mel.dim() == 2 and mel.is_contiguous() and mel.shape[1] == num_mels
+    assert mag is None or (mag.dtype == torch.float32 and mag.is_contiguous() and mag.shape == (mel.shape[0], n_fft // 2 + 1))
+    p = _lib.MelspecParams(
+        n_fft=n_fft, win=win, hop=hop, num_mels=num_mels, n_utts=sample_offsets.numel() - 1, n_band_weights=band_weight.numel(),
+        total_samples=signal.numel(), total_frames=mel.shape[0], signal=_p(signal), sample_offsets=_p(sample_offsets),
+        frame_offsets=_p(frame_offsets), window=_p(window), twiddle=_p(twiddle), band_start=_p(band_start),
+        band_offset=_p(band_offset), band_weight=_p(band_weight), ref_level_db=float(ref_level_db), mel=_p(mel), mag=_p(mag))
+    _lib.check(_lib.lib().satt_melspec(C.byref(p), _s()), "melspec")
+
+
 def act_bwd(dy, y, dx, act, scale=1.0):
     rows, cols = y.shape
     _lib.check(_lib.lib().satt_act_bwd(_p(dy), _ld(dy), _p(y), _ld(y), _p(dx), _ld(dx), rows, cols, act, scale, _s()))
