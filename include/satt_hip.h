@@ -957,6 +957,45 @@ typedef struct {
 int satt_melspec_supported(int n_fft, int win, int hop, int num_mels);
 int satt_melspec(const satt_melspec_params* p, void* stream);
 
+/* ---- Griffin-Lim phase reconstruction of a batch of utterances in one call (csrc/griffin_lim.hip): the inverse of satt_melspec's
+ * framing.  Utterance u owns the rows frame_offsets[u] .. frame_offsets[u + 1] (T frames) of mag / ang / c_prev / spec_out and the
+ * samples sample_offsets[u] .. sample_offsets[u + 1] of signal; the caller sets their number to (T - 1) hop (torch.istft's centred
+ * length: 1 + n / hop == T) and passes only utterances of (T - 1) hop >= n_fft / 2 + 1.  Anything else is left untouched: nothing
+ * is read or written out of bounds whatever the offsets hold.  One iteration on the unit-complex state ang:
+ *   y = istft(mag * ang)   per frame irfft (imaginary parts of bins 0 and n_fft / 2 ignored), x window, overlap-add, / sum_t window^2
+ *   c = stft(y)            satt_melspec's framing (reflect-centred, windowed, rfft)
+ *   u = c + alpha (c - c_prev);   ang' = u / max(|u|, 1e-30);   c_prev' = c
+ * The call runs `iters` iterations and writes signal = istft(mag * ang) behind them (iters == 0: a plain inverse STFT).  ang and
+ * c_prev are in/out, so iters = a followed by iters = b equals iters = a + b bit for bit; c_prev may be NULL when alpha == 0 (it
+ * is then neither read nor written; with a buffer it is written only).  spec_out (optional) receives the last c.
+ * Tables (device memory): window and twiddle as for satt_melspec; envelope: float64 [hop + 2 n_fft] = F | H | G with
+ *   F[j] = sum over all t of w^2[j + t hop],  H[p] = sum_{t >= 1} w^2[p + t hop],  G[r] = sum_{t >= 0} w^2[r - t hop]
+ * (w the float64 window), from which the kernel forms sum_{0 <= t < T} w^2[p - t hop] for any T.
+ * workspace: satt_griffin_lim_workspace_bytes(n_fft, total_frames) = total_frames * n_fft * 4 bytes (the windowed frames).
+ * satt_griffin_lim_supported (no GPU needed) == 1: n_fft in {512, 1024, 2048, 4096}, 16 <= win <= n_fft, 1 <= hop <= win / 2;
+ * anything else SATT_E_UNSUPPORTED.  2 iters + 2 launches, fp32, four frames per workgroup, the overlap-add is a gather in
+ * ascending frame order: no atomics, nothing crosses workgroups inside a launch, two calls on the same input are bit-identical
+ * and an utterance's result does not depend on its batch. */
+typedef struct {
+  int n_fft, win, hop, n_utts, iters;
+  float alpha;
+  int64_t total_samples, total_frames;
+  const int64_t* sample_offsets; /* [n_utts + 1] */
+  const int64_t* frame_offsets;  /* [n_utts + 1] */
+  const float* window;
+  const float* twiddle;
+  const double* envelope;
+  const float* mag; /* [total_frames, n_fft / 2 + 1] */
+  float* ang;       /* [total_frames, n_fft / 2 + 1][2], in/out */
+  float* c_prev;    /* the same shape, in/out, or NULL when alpha == 0 */
+  float* signal;    /* [total_samples] */
+  float* workspace;
+  float* spec_out;  /* [total_frames, n_fft / 2 + 1][2] or NULL */
+} satt_griffin_lim_params;
+int satt_griffin_lim_supported(int n_fft, int win, int hop);
+int64_t satt_griffin_lim_workspace_bytes(int n_fft, int64_t total_frames);
+int satt_griffin_lim(const satt_griffin_lim_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

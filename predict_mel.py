@@ -4,6 +4,7 @@
 Usage: predict_mel.py --source-data-root=<dir> --target-data-root=<dir> --checkpoint-dir=<dir> --output-dir=<dir>
                       --selected-list-dir=<dir> [--checkpoint=<file>] [--selected-list-filename=<name>]
                       [--hparams=<a=b>] [--hparam-json-file=<path>] [--batch-size=<N>]
+                      [--wav] [--griffin-lim-iters=<N>] [--griffin-lim-power=<P>]
 
 For every key of the list: free-running decode (batch size 1) from `model-<step>.pt`, output `<key>.mfbsp` (raw
 little-endian float32 [T, num_mels]; the PostNetV2 output when `use_postnet_v2`, models/models.py:440-462), `<key>.alignment.npz` + `<key>.png` (the
@@ -11,7 +12,7 @@ two alignment histories laid out [T_memory, T_query] as in the reference's predi
 reference's prediction record, utils/tfrecord.py:135-152).  `use_forced_alignment_mode=True` (models/models.py:387-428):
 pass 1 is the validation decode fed with the GROUND-TRUTH mel (needs --target-data-root), pass 2 feeds its own outputs
 back while both attention mechanisms return pass 1's alignments.  `--batch-size N` (forced-alignment mode only) decodes N
-utterances per pass.
+utterances per pass.  `--wav` adds `<key>.wav`: Griffin-Lim phase reconstruction of the de-normalised mel (csrc/griffin_lim.hip).
 Usage: see --help"""
 import argparse
 import glob
@@ -37,9 +38,17 @@ def main(argv=None):
                          "passes then decode N utterances at once and every prediction is cut to its own utterance's lengths.  The "
                          "values are those of the model AT THAT BATCH: the padding symbols of the shorter utterances reach the "
                          "encoder's convolutions exactly as in training, so they are not bit-equal to a batch-size-1 run")
+    ap.add_argument("--wav", action="store_true",
+                    help="write <key>.wav next to every <key>.mfbsp: Griffin-Lim phase reconstruction of the de-normalised mel (16-bit "
+                         "PCM at hparams.sample_rate, peak 0.95) - a quick listen, not a vocoder; mel_to_wav.py does the same afterwards")
+    ap.add_argument("--griffin-lim-iters", type=int, default=60, metavar="N", help="Griffin-Lim iterations of --wav (default 60)")
+    ap.add_argument("--griffin-lim-power", type=float, default=1.0, metavar="P",
+                    help="exponent on the linear magnitudes of --wav (default 1.0)")
     a = ap.parse_args(argv)
     if not 1 <= a.batch_size <= 16:
         raise SystemExit("--batch-size: 1 .. 16")
+    if a.griffin_lim_iters < 0:
+        raise SystemExit("--griffin-lim-iters: >= 0")
 
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import satt_amd  # noqa: F401
@@ -61,6 +70,13 @@ def main(argv=None):
         raise SystemExit("--batch-size > 1 needs use_forced_alignment_mode=True: a free-running batch has no per-utterance end")
     # reference predict_mel.py:40-57: estimator = tacotron_model_factory(hparams, checkpoint_dir, run_config);
     # estimator.predict(input_fn, checkpoint_path=...)
+    audio = None
+    if a.wav:
+        if not np.any(np.asarray(hparams.stddev_mel_level_db, np.float64)):
+            raise SystemExit("--wav de-normalises the prediction: average_mel_level_db / stddev_mel_level_db are unset, pass the "
+                             "hparams.json that the preprocessing run wrote")
+        from satt_amd.utils.audio import Audio
+        audio = Audio(hparams, backend="hip")
     model = tacotron_model_factory(hparams, None, device="cuda")
     ck = a.checkpoint or max(glob.glob(os.path.join(a.checkpoint_dir, "model-*.pt")),
                              key=lambda p: int(p.rsplit("-", 1)[1][:-3]))
@@ -98,6 +114,9 @@ def main(argv=None):
         mel = (p["mel_postnet"] if "mel_postnet" in p else p["mel"]).astype("<f4")
         assert mel.shape[1] == hparams.num_mels
         mel.tofile(os.path.join(a.output_dir, "%s.%s" % (key, hparams.predicted_mel_extension)))
+        if audio is not None:
+            audio.save_wav_pcm16(audio.inv_melspectrogram(audio.denormalize_mel(mel).T, iters=a.griffin_lim_iters,
+                                                          power=a.griffin_lim_power), os.path.join(a.output_dir, "%s.wav" % key))
         # [T_memory, T_query]; the single-source baseline model has one history (reference models/models.py:196-212)
         aligns = [p[k] for k in ("alignment", "alignment2") if k in p]
         np.savez(os.path.join(a.output_dir, "%s.alignment.npz" % key), **{k: p[k] for k in ("alignment", "alignment2") if k in p})

@@ -153,6 +153,14 @@ class MelspecParams(C.Structure):
                 [("ref_level_db", C.c_float), ("mel", C.c_void_p), ("mag", C.c_void_p)])
 
 
+class GriffinLimParams(C.Structure):
+    """satt_griffin_lim_params (include/satt_hip.h): Griffin-Lim phase reconstruction of a batch of utterances"""
+    _fields_ = ([(n, C.c_int) for n in ("n_fft", "win", "hop", "n_utts", "iters")] + [("alpha", C.c_float)] +
+                [("total_samples", c_i64), ("total_frames", c_i64)] +
+                [(n, C.c_void_p) for n in ("sample_offsets", "frame_offsets", "window", "twiddle", "envelope", "mag", "ang", "c_prev",
+                                           "signal", "workspace", "spec_out")])
+
+
 # name -> (restype, argtypes); must list EVERY symbol declared in include/satt_hip.h
 _P = C.c_void_p
 _I = C.c_int
@@ -283,6 +291,9 @@ SIGNATURES = {
     "satt_dec_self_attn": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "satt_melspec_supported": (_I, [_I, _I, _I, _I]),
     "satt_melspec": (_I, [C.POINTER(MelspecParams), _P]),
+    "satt_griffin_lim_supported": (_I, [_I, _I, _I]),
+    "satt_griffin_lim_workspace_bytes": (c_i64, [_I, c_i64]),
+    "satt_griffin_lim": (_I, [C.POINTER(GriffinLimParams), _P]),
     "satt_l2_reg": (_I, [_P, _P, _P, _I, _F, _P, _P, _P]),
     "satt_sumsq": (_I, [_P, c_i64, _P, _P]),
     "satt_sumsq_state_floats": (_I, []),

@@ -461,6 +461,45 @@ def melspec(signal, sample_offsets, frame_offsets, n_fft, win, hop, window, twid
     _lib.check(_lib.lib().satt_melspec(C.byref(p), _s()), "melspec")
 
 
+def griffin_lim_supported(n_fft, win, hop):
+    """True when satt_griffin_lim takes these STFT parameters (host-only: needs the library, not a GPU)"""
+    return bool(_lib.lib().satt_griffin_lim_supported(int(n_fft), int(win), int(hop)))
+
+
+def griffin_lim_workspace_bytes(n_fft, total_frames):
+    return int(_lib.lib().satt_griffin_lim_workspace_bytes(int(n_fft), int(total_frames)))
+
+
+def griffin_lim(mag, ang, c_prev, signal, sample_offsets, frame_offsets, n_fft, win, hop, iters, alpha, window, twiddle, envelope,
+                workspace, spec_out=None):
+    """`iters` Griffin-Lim iterations and the inverse STFT behind them for a batch of utterances in one call (csrc/griffin_lim.hip).
+    mag: fp32 [total frames, n_fft / 2 + 1]; ang: fp32 [total frames, n_fft / 2 + 1, 2] unit complex, in/out; c_prev: the same shape,
+    in/out, or None with alpha == 0; signal: fp32 [total samples], out.  Utterance u owns rows frame_offsets[u] .. frame_offsets[u +
+    1] (T frames) and samples sample_offsets[u] .. sample_offsets[u + 1] ((T - 1) hop of them; int64 [U + 1] each).  window / twiddle
+    are those of utils/audio.py MelspecTables, envelope is overlap_envelope_tables (fp64 [hop + 2 n_fft]); spec_out (optional, ang's
+    shape) receives the last re-analysis.  Parameters outside satt_griffin_lim_supported raise."""
+    NF = n_fft // 2 + 1
+    assert mag.dtype == torch.float32 and mag.dim() == 2 and mag.shape[1] == NF and mag.is_contiguous()
+    for x in (ang, c_prev, spec_out):
+        assert x is None or (x.dtype == torch.float32 and x.shape == (mag.shape[0], NF, 2) and x.is_contiguous())
+    assert ang is not None and (c_prev is not None or alpha == 0)
+    assert signal.dtype == torch.float32 and signal.dim() == 1 and signal.is_contiguous()
+    assert sample_offsets.dtype == torch.int64 and frame_offsets.dtype == torch.int64
+    assert sample_offsets.numel() == frame_offsets.numel() >= 2
+    assert window.dtype == torch.float32 and window.numel() == n_fft and twiddle.dtype == torch.float32 and twiddle.numel() == 2 * n_fft
+    assert envelope.dtype == torch.float64 and envelope.numel() == hop + 2 * n_fft
+    assert workspace.dtype == torch.float32 and workspace.numel() * 4 >= griffin_lim_workspace_bytes(n_fft, mag.shape[0])
+    if not griffin_lim_supported(n_fft, win, hop):
+        raise ValueError("griffin_lim does not take n_fft=%d win=%d hop=%d (n_fft in 512 / 1024 / 2048 / 4096, 16 <= win <= n_fft, "
+                         "1 <= hop <= win / 2)" % (n_fft, win, hop))
+    p = _lib.GriffinLimParams(
+        n_fft=n_fft, win=win, hop=hop, n_utts=sample_offsets.numel() - 1, iters=int(iters), alpha=float(alpha),
+        total_samples=signal.numel(), total_frames=mag.shape[0], sample_offsets=_p(sample_offsets), frame_offsets=_p(frame_offsets),
+        window=_p(window), twiddle=_p(twiddle), envelope=_p(envelope), mag=_p(mag), ang=_p(ang), c_prev=_p(c_prev), signal=_p(signal),
+        workspace=_p(workspace), spec_out=_p(spec_out))
+    _lib.check(_lib.lib().satt_griffin_lim(C.byref(p), _s()), "griffin_lim")
+
+
 def act_bwd(dy, y, dx, act, scale=1.0):
     rows, cols = y.shape
     _lib.check(_lib.lib().satt_act_bwd(_p(dy), _ld(dy), _p(y), _ld(y), _p(dx), _ld(dx), rows, cols, act, scale, _s()))

@@ -2,7 +2,9 @@
 librosa.  The log-mel spectrogram runs in csrc/melspec.hip (backend "hip") or as a float32 scipy.fft restatement (backend
 "numpy", for machines without a GPU); both follow librosa.stft's defaults: frames centred by reflect padding, a periodic Hann
 window of `win` points zero-padded to n_fft, T = 1 + n // hop frames, Slaney's mel basis.  `trim` is O(n) host code (DESIGN.md
-records the semantics chosen for it).  Resampling is not built: a wav whose rate differs from hparams.sample_rate is refused."""
+records the semantics chosen for it).  Resampling is not built: a wav whose rate differs from hparams.sample_rate is refused.
+The way back - `inv_melspectrogram`: the pseudo-inverse of the mel basis and Griffin-Lim phase reconstruction - runs in
+csrc/griffin_lim.hip or as the same kind of restatement; it is a quick listen, not a vocoder."""
 import numpy as np
 
 MAX_LAUNCH_SAMPLES = 1 << 23          # samples per kernel launch of melspectrogram_batch (32 MB of signal; one longer utterance
@@ -81,6 +83,7 @@ class MelspecTables:
         self.band_start, self.band_offset, self.band_weight = banded(self.basis)
         self.twiddle = twiddles(n_fft)
         self._dev = {}
+        self._basis_pinv = None              # mel_to_linear's, computed on first use
 
     def device(self, device):
         import torch
@@ -89,6 +92,14 @@ class MelspecTables:
             self._dev[key] = {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(device)
                               for k in ("window", "twiddle", "band_start", "band_offset", "band_weight")}
         return self._dev[key]
+
+    def griffin_lim_device(self, device):
+        """device() plus "envelope", the float64 overlap-add tables that only Griffin-Lim reads (made on first use)"""
+        import torch
+        d = self.device(device)
+        if "envelope" not in d:
+            d["envelope"] = torch.from_numpy(overlap_envelope_tables(padded_window(self.n_fft, self.win), self.hop)).to(device)
+        return d
 
 
 def melspec_hip(tables, signals, ref_level_db, device="cuda", want_mag=False):
@@ -131,6 +142,143 @@ def melspec_numpy(tables, y, ref_level_db, want_mag=False):
     return (db, mag) if want_mag else db
 
 
+# ---- mel -> audio: Griffin-Lim phase reconstruction (csrc/griffin_lim.hip, or float32 scipy.fft) ------------------------------------
+#
+# One utterance of T frames gives n = (T - 1) hop samples (torch.istft's / librosa's centred length; 1 + n // hop == T).  Padded
+# position p = sample + n_fft / 2 lies in frame t at in-frame index p - t hop.  One iteration on the unit-complex `ang`:
+#   y = istft(mag ang);  c = stft(y);  u = c + alpha (c - c_prev);  ang' = u / max(|u|, 1e-30);  c_prev' = c
+# (alpha = 0: classic Griffin-Lim; 0.99: the "fast" variant).  The result is istft(mag ang) behind `iters` iterations.
+
+def overlap_envelope_tables(window64, hop):
+    """float64 [hop + 2 n_fft] = F | H | G, the pieces of the overlap-add envelope of ANY frame count T:
+        sum_{0 <= t < T} w^2[p - t hop] = F[p mod hop] - (H[p] if p < n_fft) - (G[p - T hop] if p >= T hop)
+    F[j] = sum over every integer t of w^2[j + t hop] (the value away from the ends), H[p] = sum_{t >= 1} w^2[p + t hop] (frames
+    in front of the first), G[r] = sum_{t >= 0} w^2[r - t hop] (frames behind the last)."""
+    w2 = np.asarray(window64, np.float64) ** 2
+    N = len(w2)
+    H, G = np.zeros(N), w2.copy()
+    for m in range(1, -(-N // hop)):
+        H[:N - m * hop] += w2[m * hop:]
+        G[m * hop:] += w2[:N - m * hop]
+    F = (H + w2)[:hop].copy() if hop <= N else np.concatenate([w2, np.zeros(hop - N)])
+    return np.concatenate([F, H, G])
+
+
+def overlap_envelope(window64, hop, T):
+    """float64 [n_fft + hop (T - 1)]: sum_t w^2[p - t hop] by direct summation"""
+    N = len(window64)
+    env = np.zeros(N + hop * (T - 1))
+    w2 = np.asarray(window64, np.float64) ** 2
+    for t in range(T):
+        env[t * hop:t * hop + N] += w2
+    return env
+
+
+def griffin_lim_check(tables, frames):
+    """raises ValueError naming what csrc/griffin_lim.hip (and the NumPy restatement) does not take"""
+    t = tables
+    if t.n_fft not in (512, 1024, 2048, 4096):
+        raise ValueError("Griffin-Lim: n_fft=%d is not one of 512 / 1024 / 2048 / 4096" % t.n_fft)
+    if not 16 <= t.win <= t.n_fft:
+        raise ValueError("Griffin-Lim: win=%d is outside 16 .. n_fft=%d" % (t.win, t.n_fft))
+    if not 1 <= t.hop <= t.win // 2:
+        raise ValueError("Griffin-Lim: hop=%d is outside 1 .. win / 2 = %d (the squared Hann windows must overlap)" % (t.hop, t.win // 2))
+    for T in frames:
+        if (T - 1) * t.hop < t.n_fft // 2 + 1:
+            raise ValueError("Griffin-Lim: frames=%d gives (frames - 1) * hop = %d samples, fewer than n_fft / 2 + 1 = %d: the "
+                             "re-analysis cannot reflect-pad" % (T, (T - 1) * t.hop, t.n_fft // 2 + 1))
+
+
+def griffin_lim_numpy(tables, mag, ang0, iters, alpha, c_prev=None, want_state=False):
+    """float32 scipy.fft restatement of csrc/griffin_lim.hip for one utterance.  mag float32 [T, n_fft / 2 + 1], ang0 complex64
+    unit phases of the same shape, c_prev complex64 or None (zeros).  Returns the signal float32 [(T - 1) hop], or with want_state
+    (signal, ang, c_prev, c): the state behind `iters` iterations and the last re-analysis (None when iters == 0)."""
+    try:
+        from scipy.fft import irfft, rfft
+    except ImportError:                  # numpy's transforms compute in float64; the results are rounded to float32 behind them
+        irfft, rfft = np.fft.irfft, np.fft.rfft
+    t = tables
+    mag = np.ascontiguousarray(mag, np.float32)
+    T, M = mag.shape[0], t.n_fft // 2
+    griffin_lim_check(t, [T])
+    n = (T - 1) * t.hop
+    w64 = padded_window(t.n_fft, t.win)
+    w = w64.astype(np.float32)
+    inv_env = (1.0 / overlap_envelope(w64, t.hop, T)[M:M + n].astype(np.float32)).astype(np.float32)
+    ang = np.ascontiguousarray(ang0, np.complex64)
+    prev = np.zeros_like(ang) if c_prev is None else np.ascontiguousarray(c_prev, np.complex64)
+    alpha = np.float32(alpha)
+
+    def synth(a):
+        frames = irfft(mag * a, n=t.n_fft, axis=1).astype(np.float32) * w[None, :]
+        y = np.zeros(t.n_fft + t.hop * (T - 1), np.float32)
+        for i in range(T):                                   # ascending frame order, as the kernel's gather
+            y[i * t.hop:i * t.hop + t.n_fft] += frames[i]
+        return y[M:M + n] * inv_env
+
+    c = None
+    for _ in range(iters):
+        yp = np.pad(synth(ang), M, mode="reflect")
+        fr = np.lib.stride_tricks.as_strided(yp, (T, t.n_fft), (yp.strides[0] * t.hop, yp.strides[0]), writeable=False)
+        c = rfft(fr * w[None, :], axis=1).astype(np.complex64)
+        u = c + alpha * (c - prev) if alpha != 0 else c
+        ang = (u / np.maximum(np.abs(u), np.float32(1e-30))).astype(np.complex64)
+        prev = c
+    y = synth(ang)
+    return (y, ang, prev, c) if want_state else y
+
+
+def griffin_lim_hip(tables, mags, ang0s, iters, alpha, device="cuda", c_prevs=None, want_state=False):
+    """one entry call of csrc/griffin_lim.hip over a list of utterances (mags float32 [T_u, n_fft / 2 + 1], ang0s complex64): the
+    list of signals float32 [(T_u - 1) hop]; with want_state (signals, angs, c_prevs, cs)."""
+    import torch
+    from .. import ops
+    t = tables
+    NF = t.n_fft // 2 + 1
+    Ts = np.asarray([m.shape[0] for m in mags], np.int64)
+    griffin_lim_check(t, Ts)
+    fo = np.concatenate([[0], np.cumsum(Ts)]).astype(np.int64)
+    so = np.concatenate([[0], np.cumsum((Ts - 1) * t.hop)]).astype(np.int64)
+    d = t.griffin_lim_device(device)
+
+    def up(xs, dtype):
+        return torch.from_numpy(np.concatenate([np.ascontiguousarray(x, dtype).reshape(-1, NF) for x in xs])).to(device)
+    mag = up(mags, np.float32)
+    ang = torch.view_as_real(up(ang0s, np.complex64)).contiguous()
+    keep_prev = alpha != 0 or c_prevs is not None or want_state
+    prev = None
+    if keep_prev:
+        prev = torch.view_as_real(up(c_prevs, np.complex64)).contiguous() if c_prevs is not None else torch.zeros_like(ang)
+    spec = torch.zeros_like(ang) if want_state and iters > 0 else None
+    signal = torch.empty(int(so[-1]), dtype=torch.float32, device=device)
+    ws = torch.empty(ops.griffin_lim_workspace_bytes(t.n_fft, int(fo[-1])) // 4, dtype=torch.float32, device=device)
+    ops.griffin_lim(mag, ang, prev, signal, torch.from_numpy(so).to(device), torch.from_numpy(fo).to(device), t.n_fft, t.win, t.hop,
+                    iters, alpha, d["window"], d["twiddle"], d["envelope"], ws, spec)
+    y = signal.cpu().numpy()
+    ys = [y[so[u]:so[u + 1]] for u in range(len(mags))]
+    if not want_state:
+        return ys
+
+    def down(x):
+        if x is None:
+            return [None] * len(mags)
+        z = torch.view_as_complex(x).cpu().numpy()
+        return [z[fo[u]:fo[u + 1]] for u in range(len(mags))]
+    return ys, down(ang), down(prev), down(spec)
+
+
+def mel_to_linear(tables, S_db, ref_level_db, power=1.0):
+    """float64 [T, n_fft / 2 + 1] linear magnitudes of a dB mel spectrogram [T, num_mels] (Audio.melspectrogram's scale):
+        amp = 10 ** ((S + ref_level_db) / 20);   mag = max(1e-10, amp @ pinv(basis).T) ** power
+    The mel basis maps n_fft / 2 + 1 bins onto num_mels bands and is NOT invertible: the Moore-Penrose pseudo-inverse picks, among
+    the spectra with these band amplitudes, the one of least norm (the least-squares choice, librosa's mel_to_stft without its
+    non-negative solver) and the floor removes what it leaves negative.  The pseudo-inverse is computed once per table, in float64."""
+    if tables._basis_pinv is None:
+        tables._basis_pinv = np.linalg.pinv(tables.basis)
+    amp = 10.0 ** ((np.asarray(S_db, np.float64) + ref_level_db) / 20.0)
+    return np.maximum(1e-10, amp @ tables._basis_pinv.T) ** power
+
+
 class Audio:
     def __init__(self, hparams, backend=None, device="cuda"):
         self.hparams = hparams
@@ -170,6 +318,13 @@ class Audio:
     def save_wav(self, wav, path):
         from scipy.io import wavfile
         wavfile.write(path, self.hparams.sample_rate, wav)
+
+    def save_wav_pcm16(self, signal, path, peak=0.95):
+        """16-bit PCM at hparams.sample_rate, the largest |sample| scaled to `peak` of full scale (a silent signal stays silent)"""
+        signal = np.asarray(signal, np.float64)
+        top = float(np.abs(signal).max()) if signal.size else 0.0
+        pcm = np.round(signal * (peak * 32767.0 / top if top > 0.0 else 0.0)).astype(np.int16)
+        self.save_wav(pcm, path)
 
     def trim(self, wav):
         """the signal without its leading and trailing silence, widened by num_silent_frames frame shifts on either side.  A frame
@@ -220,6 +375,36 @@ class Audio:
 
     def normalize_mel(self, S):
         return (S - self.average_mel_level_db) / self.stddev_mel_level_db
+
+    def denormalize_mel(self, S):
+        """the inverse of normalize_mel: dB values from what the model predicts"""
+        return S * self.stddev_mel_level_db + self.average_mel_level_db
+
+    def inv_melspectrogram_batch(self, Ss, iters=60, alpha=0.99, power=1.0, seed=0):
+        """list of float32 signals of (T - 1) hop samples, one per dB mel spectrogram [T, num_mels] (melspectrogram_batch's layout):
+        mel_to_linear, then `iters` Griffin-Lim iterations from a phase drawn uniformly on the host by np.random.default_rng(seed)
+        - for every utterance afresh, so that neither the backend nor the batch changes the numbers it starts from."""
+        t = self.tables
+        griffin_lim_check(t, [len(S) for S in Ss])
+        mags = [mel_to_linear(t, S, self.hparams.ref_level_db, power).astype(np.float32) for S in Ss]
+        angs = [np.exp(2j * np.pi * np.random.default_rng(seed).random(m.shape)).astype(np.complex64) for m in mags]
+        if self.backend == "numpy":
+            return [griffin_lim_numpy(t, m, a, iters, alpha) for m, a in zip(mags, angs)]
+        out, group, count = [], [], 0
+        for m, a in zip(mags, angs):
+            n = (len(m) - 1) * t.hop
+            if group and count + n > MAX_LAUNCH_SAMPLES:
+                out += griffin_lim_hip(t, [g[0] for g in group], [g[1] for g in group], iters, alpha, self.device)
+                group, count = [], 0
+            group.append((m, a))
+            count += n
+        if group:
+            out += griffin_lim_hip(t, [g[0] for g in group], [g[1] for g in group], iters, alpha, self.device)
+        return out
+
+    def inv_melspectrogram(self, S, iters=60, alpha=0.99, power=1.0, seed=0):
+        """float32 [(T - 1) hop] from one dB mel spectrogram [num_mels, T], the layout melspectrogram returns"""
+        return self.inv_melspectrogram_batch([np.asarray(S).T], iters, alpha, power, seed)[0]
 
 
 def _gpu_bound():
