@@ -17,10 +17,9 @@
 // a sample's value has one fixed summation order whatever shares its launch, so two launches are bit-identical and an utterance's
 // result does not depend on its batch (the property melspec_k has).
 //
-// The Stockham stage loop and the LDS layout ([4][M] x, [4][M] y, [M] twiddles: 144 KiB at 4096) are a COPY of melspec.hip's, not a
-// shared header: melspec_k's code object stays what it was.  The recombination of gl_synth_k reads global memory and writes LDS
-// with unit stride (one float2 a lane: conflict-free); gl_analysis_k's reads Z[k] ascending and Z[M - k] descending, both unit
-// stride.
+// The Stockham stage loop, the LDS layout and the forward recombination live in stft_lds.h, shared with melspec.hip.  The
+// recombination of gl_synth_k reads global memory and writes LDS with unit stride (one float2 a lane: conflict-free);
+// gl_analysis_k's reads Z[k] ascending and Z[M - k] descending, both unit stride.
 //
 // Envelope: sum_{0 <= t < T} w^2[p - t hop] = F[p mod hop] - (p < n_fft ? H[p] : 0) - (p >= T hop ? G[p - T hop] : 0) from the
 // float64 tables F [hop], H [n_fft], G [n_fft] of the host (utils/audio.py overlap_envelope_tables); the difference is taken in
@@ -30,14 +29,9 @@
 // [0, total_frames), its samples inside [0, total_samples), its sample count is (T - 1) hop and n_fft / 2 + 1 <= (T - 1) hop <
 // 2^30; anything else is left untouched.  Frames gathered are rows of the utterance itself, in-frame indices lie inside the
 // window's support.  Every LDS word read was written by the same launch.
-#include "common.h"
+#include "stft_lds.h"
 
 namespace {
-
-constexpr int GL_FR = 4;                // frames per workgroup
-
-constexpr int gl_nt(int N) { return N >= 4096 ? 1024 : (N >= 2048 ? 512 : 256); }
-inline size_t gl_lds(int N) { return (size_t)(2 * GL_FR + 1) * (N / 2) * sizeof(float2) + 4 * GL_FR * sizeof(long long); }
 
 struct GlArgs {
   int hop, win, lead, lead_mod, n_utts;
@@ -57,11 +51,7 @@ template <int N>
 __device__ __forceinline__ GlSlot gl_find(const GlArgs& a, long long gf) {
   GlSlot r{-1, 0, 0, 0};
   if (gf >= a.total_frames) return r;
-  int lo = 0, hi = a.n_utts;                              // the last utterance whose first frame is <= gf
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (a.frame_offsets[mid] <= gf) lo = mid; else hi = mid;
-  }
+  const int lo = stft_utt(a.frame_offsets, a.n_utts, gf);
   const long long f0 = a.frame_offsets[lo], f1 = a.frame_offsets[lo + 1];
   const long long s0 = a.sample_offsets[lo], s1 = a.sample_offsets[lo + 1];
   if (f0 < 0 || f1 <= f0 || f1 > a.total_frames || gf < f0 || gf >= f1) return r;
@@ -70,49 +60,6 @@ __device__ __forceinline__ GlSlot gl_find(const GlArgs& a, long long gf) {
   if (n != s1 - s0 || n < N / 2 + 1 || n >= (1LL << 30)) return r;
   r.f0 = f0; r.T = (int)(f1 - f0); r.t = (int)(gf - f0); r.s0 = s0;
   return r;
-}
-
-__device__ __forceinline__ float2 gl_cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ float2 gl_add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 gl_sub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-
-// M-point complex transform of GL_FR frames held in x (melspec_k's stage loop): radix-4 Stockham, decimation in frequency, one
-// radix-2 stage behind it when log2 M is odd.  Returns the buffer that holds the result; the other one is free.
-template <int N>
-__device__ __forceinline__ float2* gl_fft(float2* x, float2* y, const float2* tw, int tid) {
-  constexpr int M = N / 2, NT = gl_nt(N), NB = M / 4;
-#pragma unroll
-  for (int n = M, s = 1; n >= 4; n >>= 2, s <<= 2) {
-    const int n1 = n >> 2;
-    for (int e = tid; e < GL_FR * NB; e += NT) {
-      const int f = e / NB, t = e - f * NB, p = t / s, q = t - p * s;
-      const float2* xf = x + f * M;
-      float2* yf = y + f * M;
-      const float2 A = xf[q + s * p], B = xf[q + s * (p + n1)], C = xf[q + s * (p + 2 * n1)], D = xf[q + s * (p + 3 * n1)];
-      const float2 apc = gl_add(A, C), amc = gl_sub(A, C), bpd = gl_add(B, D), bmd = gl_sub(B, D);
-      const float2 jbmd = make_float2(-bmd.y, bmd.x);
-      const float2 w1 = tw[p * s], w2 = tw[2 * p * s], w3 = tw[3 * p * s];
-      yf[q + s * (4 * p)] = gl_add(apc, bpd);
-      yf[q + s * (4 * p + 1)] = gl_cmul(w1, gl_sub(amc, jbmd));
-      yf[q + s * (4 * p + 2)] = gl_cmul(w2, gl_sub(apc, bpd));
-      yf[q + s * (4 * p + 3)] = gl_cmul(w3, gl_add(amc, jbmd));
-    }
-    __syncthreads();
-    float2* tmp = x; x = y; y = tmp;
-  }
-  constexpr bool ODD = M == 512 || M == 2048;
-  if (ODD) {
-    constexpr int s = M / 2;
-    for (int e = tid; e < GL_FR * s; e += NT) {
-      const int f = e / s, q = e - f * s;
-      const float2 A = x[f * M + q], B = x[f * M + q + s];
-      y[f * M + q] = gl_add(A, B);
-      y[f * M + q + s] = gl_sub(A, B);
-    }
-    __syncthreads();
-    float2* tmp = x; x = y; y = tmp;
-  }
-  return x;
 }
 
 // sample at padded position p (n_fft / 2 <= p < n_fft / 2 + (T - 1) hop) of an utterance whose windowed frames are the rows wsu:
@@ -136,22 +83,20 @@ __device__ __forceinline__ float gl_sample(const GlArgs& a, const float* wsu, in
 }
 
 template <int N>
-__global__ __launch_bounds__(gl_nt(N)) void gl_synth_k(GlArgs a) {
-  constexpr int M = N / 2, NT = gl_nt(N), NF = M + 1;
+__global__ __launch_bounds__(stft_nt(N)) void gl_synth_k(GlArgs a) {
+  constexpr int M = N / 2, NT = stft_nt(N), NF = M + 1;
   extern __shared__ __attribute__((aligned(16))) char gl_smem[];
-  float2* x = reinterpret_cast<float2*>(gl_smem);          // [GL_FR][M]
-  float2* y = x + GL_FR * M;                                // [GL_FR][M]
-  float2* tw = y + GL_FR * M;                               // [M]: exp(-2 pi i j / M)
-  long long* s_f0 = reinterpret_cast<long long*>(tw + M);   // [GL_FR]
   const int tid = threadIdx.x;
-  const long long gf0 = (long long)blockIdx.x * GL_FR;
+  const StftLds l = stft_carve<N>(gl_smem, a.twiddle, tid);
+  float2 *x = l.x, *y = l.y;
+  long long* s_f0 = l.slot;                                 // [STFT_FR]
+  const long long gf0 = (long long)blockIdx.x * STFT_FR;
 
-  if (tid < GL_FR) s_f0[tid] = gl_find<N>(a, gf0 + tid).f0;
-  for (int j = tid; j < M; j += NT) tw[j] = a.twiddle[2 * j];
+  if (tid < STFT_FR) s_f0[tid] = gl_find<N>(a, gf0 + tid).f0;
   __syncthreads();
 
   // conj(Z[k]), k < M, of every frame (zeros for an empty slot)
-  for (int e = tid; e < GL_FR * M; e += NT) {
+  for (int e = tid; e < STFT_FR * M; e += NT) {
     const int f = e / M, k = e - f * M;
     float2 z = make_float2(0.f, 0.f);
     if (s_f0[f] >= 0) {
@@ -164,76 +109,66 @@ __global__ __launch_bounds__(gl_nt(N)) void gl_synth_k(GlArgs a) {
       const float2 D = make_float2(0.5f * (xk.x - xm.x), 0.5f * (xk.y - xm.y));
       float2 w = a.twiddle[k];
       w.y = -w.y;                                          // conj(w^k) = exp(+2 pi i k / n_fft)
-      const float2 O = gl_cmul(w, D);
+      const float2 O = stft_cmul(w, D);
       z = make_float2(E.x - O.y, -(E.y + O.x));            // conj(E + i O)
     }
     x[e] = z;
   }
   __syncthreads();
 
-  const float2* res = gl_fft<N>(x, y, tw, tid);
+  stft_fft<N>(x, y, l.tw, tid);
 
-  // z[j] = conj(res[j]) / M: samples 2 j and 2 j + 1 of the frame, windowed
+  // z[j] = conj(x[j]) / M: samples 2 j and 2 j + 1 of the frame, windowed
   constexpr float inv_m = 1.0f / (float)M;
-  for (int e = tid; e < GL_FR * M; e += NT) {
+  for (int e = tid; e < STFT_FR * M; e += NT) {
     const int f = e / M, j = e - f * M;
     if (s_f0[f] < 0) continue;
     const float2 w = *reinterpret_cast<const float2*>(a.window + 2 * j);
-    const float2 v = res[e];
+    const float2 v = x[e];
     *reinterpret_cast<float2*>(a.ws + (gf0 + f) * N + 2 * j) = make_float2(v.x * inv_m * w.x, -(v.y * inv_m) * w.y);
   }
 }
 
 template <int N>
-__global__ __launch_bounds__(gl_nt(N)) void gl_analysis_k(GlArgs a) {
-  constexpr int M = N / 2, NT = gl_nt(N), NF = M + 1;
+__global__ __launch_bounds__(stft_nt(N)) void gl_analysis_k(GlArgs a) {
+  constexpr int M = N / 2, NT = stft_nt(N), NF = M + 1;
   extern __shared__ __attribute__((aligned(16))) char gl_smem[];
-  float2* x = reinterpret_cast<float2*>(gl_smem);
-  float2* y = x + GL_FR * M;
-  float2* tw = y + GL_FR * M;
-  long long* s_f0 = reinterpret_cast<long long*>(tw + M);   // [GL_FR]
-  int* s_T = reinterpret_cast<int*>(s_f0 + GL_FR);          // [GL_FR]
-  int* s_t = s_T + GL_FR;                                   // [GL_FR]
   const int tid = threadIdx.x;
-  const long long gf0 = (long long)blockIdx.x * GL_FR;
+  const StftLds l = stft_carve<N>(gl_smem, a.twiddle, tid);
+  float2 *x = l.x, *y = l.y;
+  long long* s_f0 = l.slot;                                 // [STFT_FR]
+  int* s_T = reinterpret_cast<int*>(s_f0 + STFT_FR);        // [STFT_FR]
+  int* s_t = s_T + STFT_FR;                                 // [STFT_FR]
+  const long long gf0 = (long long)blockIdx.x * STFT_FR;
 
-  if (tid < GL_FR) {
+  if (tid < STFT_FR) {
     const GlSlot s = gl_find<N>(a, gf0 + tid);
     s_f0[tid] = s.f0; s_T[tid] = s.T; s_t[tid] = s.t;
   }
-  for (int j = tid; j < M; j += NT) tw[j] = a.twiddle[2 * j];
   __syncthreads();
 
-  // windowed frames of the re-synthesised signal, two real samples a complex point; signal index i of padded position q is q - M,
-  // reflected once at either end (n >= M + 1 and t hop <= n keep the reflected index inside [0, n))
-  for (int e = tid; e < GL_FR * M; e += NT) {
+  // windowed frames of the re-synthesised signal, two real samples a complex point
+  for (int e = tid; e < STFT_FR * M; e += NT) {
     const int f = e / M, j = e - f * M;
     float2 z = make_float2(0.f, 0.f);
     if (s_f0[f] >= 0) {
       const int T = s_T[f], n = (T - 1) * a.hop;
       const float2 w = *reinterpret_cast<const float2*>(a.window + 2 * j);
-      int i0 = s_t[f] * a.hop + 2 * j - M, i1 = i0 + 1;
-      i0 = i0 < 0 ? -i0 : (i0 >= n ? 2 * (n - 1) - i0 : i0);
-      i1 = i1 < 0 ? -i1 : (i1 >= n ? 2 * (n - 1) - i1 : i1);
+      const int i = s_t[f] * a.hop + 2 * j - M, i0 = stft_reflect(i, n), i1 = stft_reflect(i + 1, n);
       const float* wsu = a.ws + s_f0[f] * N;
       // (where the padded window is zero - (n_fft - win) / 2 points at either end - nothing is gathered)
-      z =make_float2(w.x != 0.f ? gl_sample<N>(a, wsu, T, i0 + M) * w.x : 0.f, w.y != 0.f ? gl_sample<N>(a, wsu, T, i1 + M) * w.y : 0.f);
+      z = make_float2(w.x != 0.f ? gl_sample<N>(a, wsu, T, i0 + M) * w.x : 0.f, w.y != 0.f ? gl_sample<N>(a, wsu, T, i1 + M) * w.y : 0.f);
     }
     x[e] = z;
   }
   __syncthreads();
 
-  const float2* Z = gl_fft<N>(x, y, tw, tid);
+  stft_fft<N>(x, y, l.tw, tid);
 
-  for (int e = tid; e < GL_FR * NF; e += NT) {
+  for (int e = tid; e < STFT_FR * NF; e += NT) {
     const int f = e / NF, k = e - f * NF;
     if (s_f0[f] < 0) continue;
-    const float2 zk = Z[f * M + (k & (M - 1))];
-    float2 zm = Z[f * M + ((M - k) & (M - 1))];
-    zm.y = -zm.y;
-    const float2 E = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y + zm.y));
-    const float2 O = make_float2(0.5f * (zk.y - zm.y), -0.5f * (zk.x - zm.x));
-    const float2 c = gl_add(E, gl_cmul(a.twiddle[k], O));
+    const float2 c = stft_bin<N>(x + f * M, a.twiddle, k);
     const long long o = (gf0 + f) * NF + k;
     float2 u = c;
     if (a.alpha != 0.f) {
@@ -261,20 +196,15 @@ __global__ __launch_bounds__(256) void gl_signal_k(GlArgs a) {
 }
 
 inline bool gl_supported(int n_fft, int win, int hop) {
-  if (n_fft != 512 && n_fft != 1024 && n_fft != 2048 && n_fft != 4096) return false;
-  if (win < 16 || win > n_fft) return false;
-  return hop >= 1 && hop <= win / 2;
+  return stft_supported(n_fft, win) && hop >= 1 && hop <= win / 2;
 }
 
 template <int N>
 int gl_run(GlArgs a, int iters, float2* spec_out, hipStream_t st) {
-  const size_t lds = gl_lds(N);
-  static const hipError_t attr_s = hipFuncSetAttribute(reinterpret_cast<const void*>(gl_synth_k<N>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)gl_lds(N));
-  static const hipError_t attr_a = hipFuncSetAttribute(reinterpret_cast<const void*>(gl_analysis_k<N>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)gl_lds(N));
-  if (attr_s != hipSuccess || attr_a != hipSuccess) return SATT_E_LAUNCH;
-  const dim3 grid((unsigned)((a.total_frames + GL_FR - 1) / GL_FR)), block(gl_nt(N));
+  const size_t lds = stft_lds(N);
+  const bool limit_s = stft_lds_limit<gl_synth_k<N>, N>(), limit_a = stft_lds_limit<gl_analysis_k<N>, N>();
+  if (!limit_s || !limit_a) return SATT_E_LAUNCH;
+  const dim3 grid((unsigned)((a.total_frames + STFT_FR - 1) / STFT_FR)), block(stft_nt(N));
   for (int it = 0; it < iters; ++it) {
     a.spec_out = it == iters - 1 ? spec_out : nullptr;
     hipLaunchKernelGGL(gl_synth_k<N>, grid, block, lds, st, a);
@@ -312,10 +242,5 @@ extern "C" int satt_griffin_lim(const satt_griffin_lim_params* p, void* stream) 
            p->mag, reinterpret_cast<float2*>(p->ang), reinterpret_cast<float2*>(p->c_prev), nullptr, p->signal, p->workspace};
   float2* spec = reinterpret_cast<float2*>(p->spec_out);
   hipStream_t st = (hipStream_t)stream;
-  switch (p->n_fft) {
-    case 512: return gl_run<512>(a, p->iters, spec, st);
-    case 1024: return gl_run<1024>(a, p->iters, spec, st);
-    case 2048: return gl_run<2048>(a, p->iters, spec, st);
-    default: return gl_run<4096>(a, p->iters, spec, st);
-  }
+  return stft_dispatch(p->n_fft, [&](auto n) { return gl_run<decltype(n)::value>(a, p->iters, spec, st); });
 }

@@ -125,18 +125,28 @@ def melspec_hip(tables, signals, ref_level_db, device="cuda", want_mag=False):
     return mels, [mag[fo[u]:fo[u + 1]] for u in range(len(signals))]
 
 
+def _fft():
+    """the module whose rfft / irfft the NumPy backend uses: scipy.fft, which transforms float32 in float32, or numpy.fft, which
+    computes in float64 (the results are rounded to float32 behind it)"""
+    try:
+        import scipy.fft
+        return scipy.fft
+    except ImportError:
+        return np.fft
+
+
+def centred_frames(y, n_fft, hop, T):
+    """read-only view [T, n_fft] of y reflect-padded by n_fft // 2 at either end: frame t starts at padded position t hop"""
+    yp = np.pad(y, n_fft // 2, mode="reflect")
+    return np.lib.stride_tricks.as_strided(yp, (T, n_fft), (yp.strides[0] * hop, yp.strides[0]), writeable=False)
+
+
 def melspec_numpy(tables, y, ref_level_db, want_mag=False):
     """the same in float32 NumPy / scipy.fft: [T, num_mels] of one signal"""
-    try:
-        from scipy.fft import rfft
-    except ImportError:                  # numpy's transform computes in float64; the result is rounded to float32 behind it
-        rfft = np.fft.rfft
     t = tables
     y = np.ascontiguousarray(y, np.float32)
-    T = frame_count(len(y), t.hop)
-    yp = np.pad(y, t.n_fft // 2, mode="reflect")
-    frames = np.lib.stride_tricks.as_strided(yp, (T, t.n_fft), (yp.strides[0] * t.hop, yp.strides[0]), writeable=False)
-    mag = np.abs(rfft(frames * t.window[None, :], axis=1)).astype(np.float32)
+    frames = centred_frames(y, t.n_fft, t.hop, frame_count(len(y), t.hop))
+    mag = np.abs(_fft().rfft(frames * t.window[None, :], axis=1)).astype(np.float32)
     mel = mag @ t.basis.astype(np.float32).T
     db = (20.0 * np.log10(np.maximum(np.float32(1e-5), mel)) - np.float32(ref_level_db)).astype(np.float32)
     return (db, mag) if want_mag else db
@@ -193,10 +203,7 @@ def griffin_lim_numpy(tables, mag, ang0, iters, alpha, c_prev=None, want_state=F
     """float32 scipy.fft restatement of csrc/griffin_lim.hip for one utterance.  mag float32 [T, n_fft / 2 + 1], ang0 complex64
     unit phases of the same shape, c_prev complex64 or None (zeros).  Returns the signal float32 [(T - 1) hop], or with want_state
     (signal, ang, c_prev, c): the state behind `iters` iterations and the last re-analysis (None when iters == 0)."""
-    try:
-        from scipy.fft import irfft, rfft
-    except ImportError:                  # numpy's transforms compute in float64; the results are rounded to float32 behind them
-        irfft, rfft = np.fft.irfft, np.fft.rfft
+    fft = _fft()
     t = tables
     mag = np.ascontiguousarray(mag, np.float32)
     T, M = mag.shape[0], t.n_fft // 2
@@ -210,7 +217,7 @@ def griffin_lim_numpy(tables, mag, ang0, iters, alpha, c_prev=None, want_state=F
     alpha = np.float32(alpha)
 
     def synth(a):
-        frames = irfft(mag * a, n=t.n_fft, axis=1).astype(np.float32) * w[None, :]
+        frames = fft.irfft(mag * a, n=t.n_fft, axis=1).astype(np.float32) * w[None, :]
         y = np.zeros(t.n_fft + t.hop * (T - 1), np.float32)
         for i in range(T):                                   # ascending frame order, as the kernel's gather
             y[i * t.hop:i * t.hop + t.n_fft] += frames[i]
@@ -218,9 +225,7 @@ def griffin_lim_numpy(tables, mag, ang0, iters, alpha, c_prev=None, want_state=F
 
     c = None
     for _ in range(iters):
-        yp = np.pad(synth(ang), M, mode="reflect")
-        fr = np.lib.stride_tricks.as_strided(yp, (T, t.n_fft), (yp.strides[0] * t.hop, yp.strides[0]), writeable=False)
-        c = rfft(fr * w[None, :], axis=1).astype(np.complex64)
+        c = fft.rfft(centred_frames(synth(ang), t.n_fft, t.hop, T) * w[None, :], axis=1).astype(np.complex64)
         u = c + alpha * (c - prev) if alpha != 0 else c
         ang = (u / np.maximum(np.abs(u), np.float32(1e-30))).astype(np.complex64)
         prev = c
