@@ -996,6 +996,36 @@ int satt_griffin_lim_supported(int n_fft, int win, int hop);
 int64_t satt_griffin_lim_workspace_bytes(int n_fft, int64_t total_frames);
 int satt_griffin_lim(const satt_griffin_lim_params* p, void* stream);
 
+/* ---- sample-rate conversion of a batch of utterances in one launch (csrc/resample.hip): a Kaiser-windowed sinc on the rational
+ * grid up / down = target rate / source rate in lowest terms.  Utterance u is signal_in[in_offsets[u] .. in_offsets[u + 1]) (n >= 1
+ * samples) and owns signal_out[out_offsets[u] .. out_offsets[u + 1]); the caller sets out_offsets[u + 1] - out_offsets[u] =
+ * ceil(n up / down) = (n up + down - 1) / down.  An utterance with another count, with n < 1 or with offsets outside the buffers
+ * is left untouched; nothing is read or written out of bounds whatever the offsets hold.  Output m sits at input time m down / up:
+ *   k0 = (m down) / up,  phase = (m down) % up                                       (64-bit products)
+ *   signal_out[m] = sum_{jj = 0 .. taps - 1} table[phase][jj] * x[k0 - taps / 2 + 1 + jj],     x = 0 outside [0, n)
+ * table (device memory, 8-byte aligned, built by the caller in float64 and rounded once): [up][taps],
+ *   table[phase][jj] = h(phase / up - (jj - taps / 2 + 1)),   h(tau) = s sinc(s tau) I0(beta sqrt(1 - (s tau / Z)^2)) / I0(beta) for
+ *   |s tau| < Z, else 0;   s = rolloff min(1, up / down), taps = 2 ceil(Z / s);   satt_amd/utils/audio.py ResampleTables holds the
+ *   constants (Z = 64 zero crossings).  The kernel itself takes any table of this shape.
+ * satt_resample_supported (no GPU needed) == 1: up and down coprime and not both 1, 1 <= up <= 1024, 1 <= down <= 4096, taps even
+ * and 2 <= taps <= 4096; anything else SATT_E_UNSUPPORTED.  satt_resample_run_length: the outputs a workgroup takes (seams of the
+ * launch fall at its multiples, counted through the batch).  fp32, taps ascending in one chain per output (acc = acc + w x, product and
+ * sum each rounded, no fused multiply-add: the bits of the float32 NumPy backend), no atomics and no
+ * cross-workgroup exchange: two launches on the same input are bit-identical, and an utterance's result does not depend on its
+ * batch. */
+typedef struct {
+  int up, down, taps, n_utts;
+  int64_t total_in, total_out;
+  const float* signal_in;     /* [total_in] */
+  const int64_t* in_offsets;  /* [n_utts + 1] */
+  const int64_t* out_offsets; /* [n_utts + 1] */
+  const float* table;         /* [up][taps] */
+  float* signal_out;          /* [total_out] */
+} satt_resample_params;
+int satt_resample_supported(int up, int down, int taps);
+int satt_resample_run_length(void);
+int satt_resample(const satt_resample_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

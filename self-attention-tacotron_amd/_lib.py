@@ -161,6 +161,12 @@ class GriffinLimParams(C.Structure):
                                            "signal", "workspace", "spec_out")])
 
 
+class ResampleParams(C.Structure):
+    """satt_resample_params (include/satt_hip.h): sample-rate conversion of a batch of utterances"""
+    _fields_ = ([(n, C.c_int) for n in ("up", "down", "taps", "n_utts")] + [("total_in", c_i64), ("total_out", c_i64)] +
+                [(n, C.c_void_p) for n in ("signal_in", "in_offsets", "out_offsets", "table", "signal_out")])
+
+
 # name -> (restype, argtypes); must list EVERY symbol declared in include/satt_hip.h
 _P = C.c_void_p
 _I = C.c_int
@@ -294,6 +300,9 @@ SIGNATURES = {
     "satt_griffin_lim_supported": (_I, [_I, _I, _I]),
     "satt_griffin_lim_workspace_bytes": (c_i64, [_I, c_i64]),
     "satt_griffin_lim": (_I, [C.POINTER(GriffinLimParams), _P]),
+    "satt_resample_supported": (_I, [_I, _I, _I]),
+    "satt_resample_run_length": (_I, []),
+    "satt_resample": (_I, [C.POINTER(ResampleParams), _P]),
     "satt_l2_reg": (_I, [_P, _P, _P, _I, _F, _P, _P, _P]),
     "satt_sumsq": (_I, [_P, c_i64, _P, _P]),
     "satt_sumsq_state_floats": (_I, []),

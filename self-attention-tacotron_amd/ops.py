@@ -461,6 +461,35 @@ def melspec(signal, sample_offsets, frame_offsets, n_fft, win, hop, window, twid
     _lib.check(_lib.lib().satt_melspec(C.byref(p), _s()), "melspec")
 
 
+def resample_supported(up, down, taps):
+    """True when satt_resample takes this ratio and filter length (host-only: needs the library, not a GPU)"""
+    return bool(_lib.lib().satt_resample_supported(int(up), int(down), int(taps)))
+
+
+def resample_run_length():
+    """the outputs one workgroup of csrc/resample.hip takes: the launch's seams fall at its multiples, counted through the batch"""
+    return int(_lib.lib().satt_resample_run_length())
+
+
+def resample(signal_in, in_offsets, out_offsets, up, down, table, signal_out):
+    """sample-rate conversion of a batch of utterances in one launch (csrc/resample.hip).  signal_in: fp32 [total in], utterance u
+    at in_offsets[u] .. in_offsets[u + 1] (int64 [U + 1], n >= 1 samples), its ceil(n up / down) results in signal_out (fp32
+    [total out]) at out_offsets[u] .. out_offsets[u + 1].  table: fp32 [up, taps], utils/audio.py ResampleTables.  Parameters outside
+    satt_resample_supported raise."""
+    assert signal_in.dtype == torch.float32 and signal_in.dim() == 1 and signal_in.is_contiguous()
+    assert signal_out.dtype == torch.float32 and signal_out.dim() == 1 and signal_out.is_contiguous()
+    assert in_offsets.dtype == torch.int64 and out_offsets.dtype == torch.int64 and in_offsets.numel() == out_offsets.numel() >= 2
+    assert table.dtype == torch.float32 and table.dim() == 2 and table.is_contiguous() and table.shape[0] == up
+    taps = table.shape[1]
+    if not resample_supported(up, down, taps):
+        raise ValueError("resample does not take up=%d down=%d taps=%d (coprime and not both 1, up <= 1024, down <= 4096, taps even "
+                         "and <= 4096)" % (up, down, taps))
+    p = _lib.ResampleParams(up=up, down=down, taps=taps, n_utts=in_offsets.numel() - 1, total_in=signal_in.numel(),
+                            total_out=signal_out.numel(), signal_in=_p(signal_in), in_offsets=_p(in_offsets),
+                            out_offsets=_p(out_offsets), table=_p(table), signal_out=_p(signal_out))
+    _lib.check(_lib.lib().satt_resample(C.byref(p), _s()), "resample")
+
+
 def griffin_lim_supported(n_fft, win, hop):
     """True when satt_griffin_lim takes these STFT parameters (host-only: needs the library, not a GPU)"""
     return bool(_lib.lib().satt_griffin_lim_supported(int(n_fft), int(win), int(hop)))

@@ -1,6 +1,7 @@
 """What the two corpus drivers share: record writers, the per-bin mel statistics, the batched target pass and the command line.
 The reference maps utterances over Spark workers; here file I/O runs on a thread pool of at most 16 workers and the mel
-spectrograms of a chunk of utterances go through Audio.melspectrogram_batch - one GPU stream, a few launches per chunk."""
+spectrograms of a chunk of utterances go through Audio.melspectrogram_batch - one GPU stream, a few launches per chunk.  With
+--resample the chunk's wavs are read at their own rates and go through Audio.resample_batch in front of that."""
 import argparse
 import csv
 import json
@@ -56,22 +57,32 @@ def workers():
     return max(1, min(MAX_WORKERS, os.cpu_count() or 1))
 
 
-def process_targets(records, audio, out_dir, load):
-    """records: objects with .id and .key; load(record) -> float32 signal.  Writes every target record and returns
-    (keys, MelStatistics)."""
-    stats = MelStatistics(audio.hparams.num_mels)
+def load_chunk(pool, chunk, audio, post=None):
+    """the signals of a chunk of records (objects with .key and .wav_path) at hparams.sample_rate, behind `post` (a per-signal step
+    such as Audio.trim, or None).  Without audio.resample every file goes through Audio.load_wav on the pool.  With it the files
+    are read at their own rates on the pool, Audio.resample_batch converts the chunk in one call, and `post` runs on the pool on
+    the converted signals.  A signal too short for one frame is refused by its record's key."""
+    post = post or (lambda wav: wav)
+    if not audio.resample:
+        wavs = list(pool.map(lambda rec: post(audio.load_wav(rec.wav_path)), chunk))
+    else:
+        read = list(pool.map(lambda rec: audio.read_wav(rec.wav_path), chunk))
+        wavs = list(pool.map(post, audio.resample_batch([y for _, y in read], [rate for rate, _ in read])))
     need = audio.tables.n_fft // 2 + 1
-
-    def checked(rec):
-        wav = load(rec)
+    for rec, wav in zip(chunk, wavs):
         if len(wav) < need:
             raise ValueError("%s: %d samples, fewer than the %d a frame of n_fft = %d needs" % (rec.key, len(wav), need, audio.tables.n_fft))
-        return wav
+    return wavs
 
+
+def process_targets(records, audio, out_dir, post=None):
+    """records: objects with .id, .key and .wav_path; post: a per-signal step between loading and the mel (see load_chunk).  Writes
+    every target record and returns (keys, MelStatistics)."""
+    stats = MelStatistics(audio.hparams.num_mels)
     with ThreadPoolExecutor(max_workers=workers()) as pool:
         for i in range(0, len(records), CHUNK):
             chunk = records[i:i + CHUNK]
-            mels = audio.melspectrogram_batch(list(pool.map(checked, chunk)))
+            mels = audio.melspectrogram_batch(load_chunk(pool, chunk, audio, post))
             for mel in mels:
                 stats.add(mel)
             list(pool.map(lambda rm: write_target_record(rm[0].id, rm[0].key, rm[1],
@@ -119,6 +130,8 @@ def parse_args(doc, argv=None, version=False):
     ap.add_argument("--target-only", action="store_true")
     ap.add_argument("--backend", choices=("hip", "numpy"), default=None,
                     help="mel extraction: the HIP kernel (default when a GPU is bound) or the float32 NumPy restatement")
+    ap.add_argument("--resample", action="store_true",
+                    help="convert wavs whose rate differs from hparams.sample_rate (Kaiser-windowed sinc; without it they are refused)")
     if version:
         ap.add_argument("--version", default="0.8", help="VCTK release; only the 0.8 layout (wav48/, txt/, speaker-info.txt) is built")
     return ap.parse_args(argv)

@@ -14,9 +14,9 @@ TextAndPath = namedtuple("TextAndPath", ["id", "key", "wav_path", "text"])
 
 
 class LJSpeech:
-    def __init__(self, in_dir, out_dir, hparams, backend=None):
+    def __init__(self, in_dir, out_dir, hparams, backend=None, resample=False):
         self.in_dir, self.out_dir = in_dir, out_dir
-        self.audio = Audio(hparams, backend=backend)
+        self.audio = Audio(hparams, backend=backend, resample=resample)
 
     def list_records(self):
         out = []
@@ -37,4 +37,4 @@ class LJSpeech:
         return corpus.process_sources(records, write)
 
     def process_targets(self, records):
-        return corpus.process_targets(records, self.audio, self.out_dir, lambda rec: self.audio.load_wav(rec.wav_path))
+        return corpus.process_targets(records, self.audio, self.out_dir)

@@ -17,9 +17,9 @@ TxtWavRecord = namedtuple("TxtWavRecord", ["id", "key", "txt_path", "wav_path", 
 
 
 class VCTK:
-    def __init__(self, in_dir, out_dir, hparams, speaker_info_filename="speaker-info.txt", backend=None):
+    def __init__(self, in_dir, out_dir, hparams, speaker_info_filename="speaker-info.txt", backend=None, resample=False):
         self.in_dir, self.out_dir, self.speaker_info_filename = in_dir, out_dir, speaker_info_filename
-        self.audio = Audio(hparams, backend=backend)
+        self.audio = Audio(hparams, backend=backend, resample=resample)
 
     def load_speaker_info(self):
         with open(os.path.join(self.in_dir, self.speaker_info_filename), mode="r", encoding="utf8") as f:
@@ -56,5 +56,4 @@ class VCTK:
         return corpus.process_sources(records, write)
 
     def process_targets(self, records):
-        return corpus.process_targets(records, self.audio, self.out_dir,
-                                      lambda rec: self.audio.trim(self.audio.load_wav(rec.wav_path)))
+        return corpus.process_targets(records, self.audio, self.out_dir, self.audio.trim)      # with --resample: trim after it

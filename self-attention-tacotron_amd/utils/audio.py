@@ -2,13 +2,18 @@
 librosa.  The log-mel spectrogram runs in csrc/melspec.hip (backend "hip") or as a float32 scipy.fft restatement (backend
 "numpy", for machines without a GPU); both follow librosa.stft's defaults: frames centred by reflect padding, a periodic Hann
 window of `win` points zero-padded to n_fft, T = 1 + n // hop frames, Slaney's mel basis.  `trim` is O(n) host code (DESIGN.md
-records the semantics chosen for it).  Resampling is not built: a wav whose rate differs from hparams.sample_rate is refused.
+records the semantics chosen for it).  Resampling is opt-in (`Audio(..., resample=True)`): a Kaiser-windowed sinc on the rational grid
+of the two rates, in csrc/resample.hip or as a float32 NumPy restatement on the same float32 table, operation for operation (the two
+backends agree bit for bit; DESIGN.md 3.6 holds the definition; it is not librosa's bits).  Without it a wav whose rate differs
+from hparams.sample_rate is refused.
 The way back - `inv_melspectrogram`: the pseudo-inverse of the mel basis and Griffin-Lim phase reconstruction - runs in
 csrc/griffin_lim.hip or as the same kind of restatement; it is a quick listen, not a vocoder."""
+import math
+
 import numpy as np
 
-MAX_LAUNCH_SAMPLES = 1 << 23          # samples per kernel launch of melspectrogram_batch (32 MB of signal; one longer utterance
-                                      # still goes out as a launch of its own)
+MAX_LAUNCH_SAMPLES = 1 << 23          # samples per kernel launch of melspectrogram_batch / resample_batch (32 MB of signal; one
+                                      # longer utterance still goes out as a launch of its own)
 
 
 def stft_parameters(hparams):
@@ -284,9 +289,146 @@ def mel_to_linear(tables, S_db, ref_level_db, power=1.0):
     return np.maximum(1e-10, amp @ tables._basis_pinv.T) ** power
 
 
+# ---- sample-rate conversion (csrc/resample.hip, or float32 NumPy on the same table) -------------------------------------------------
+#
+# Source rate a, target rate b: g = gcd(a, b), up = b / g, down = a / g.  n samples give n_out = ceil(n up / down); output m sits at
+# input time m down / up:  k0 = (m down) // up, phase = (m down) % up,
+#   y[m] = sum_{j = -half + 1 .. half} h(phase / up - j) x[k0 + j]        (x = 0 outside [0, n))
+#   h(tau) = s sinc(s tau) I0(beta sqrt(1 - (s tau / Z)^2)) / I0(beta) for |s tau| < Z, else 0;   s = rolloff min(1, up / down)
+# half = ceil(Z / s), taps = 2 half.  The constants are those of a "kaiser best" design; the bits are this definition's, not those
+# of any resampling library.
+
+RESAMPLE_ZEROS = 64
+RESAMPLE_ROLLOFF = 0.9475937167399596
+RESAMPLE_BETA = 14.769656459379492
+RESAMPLE_MAX_UP, RESAMPLE_MAX_DOWN, RESAMPLE_MAX_TAPS = 1024, 4096, 4096          # satt_resample_supported's bounds
+
+
+def resample_ratio(src_rate, dst_rate):
+    """(up, down) = (dst_rate, src_rate) in lowest terms"""
+    src_rate, dst_rate = int(src_rate), int(dst_rate)
+    if src_rate < 1 or dst_rate < 1:
+        raise ValueError("resample: rates must be positive, got %d Hz -> %d Hz" % (src_rate, dst_rate))
+    g = math.gcd(src_rate, dst_rate)
+    return dst_rate // g, src_rate // g
+
+
+def resample_length(n, up, down):
+    return (int(n) * up + down - 1) // down
+
+
+def resample_filter_half(up, down):
+    """half = ceil(Z / s), s = rolloff min(1, up / down)"""
+    return int(math.ceil(RESAMPLE_ZEROS / (RESAMPLE_ROLLOFF * min(1.0, up / down))))
+
+
+def resample_check(src_rate, dst_rate):
+    """raises ValueError naming both rates when csrc/resample.hip (and the NumPy restatement) does not take the pair: the predicate
+    of satt_resample_supported, evaluated here so that both backends refuse the same pairs"""
+    up, down = resample_ratio(src_rate, dst_rate)
+    taps = 2 * resample_filter_half(up, down)
+    if (up == 1 and down == 1) or up > RESAMPLE_MAX_UP or down > RESAMPLE_MAX_DOWN or taps > RESAMPLE_MAX_TAPS:
+        raise ValueError("resample: %d Hz -> %d Hz is up / down = %d / %d with %d taps; supported are ratios other than 1 / 1 with "
+                         "up <= %d, down <= %d and at most %d taps" % (src_rate, dst_rate, up, down, taps, RESAMPLE_MAX_UP,
+                                                                        RESAMPLE_MAX_DOWN, RESAMPLE_MAX_TAPS))
+    return up, down, taps
+
+
+class ResampleTables:
+    """the filter of one (source rate, target rate) pair: up, down, half, taps and table float32 [up, taps] with
+    table[phase][j + half - 1] = h(phase / up - j), evaluated in float64 and rounded once; device copies are made on first use.
+    The argument of h is formed as the exact rational |phase - j up| / up, so that table[p][jj] == table[up - p][taps - 1 - jj]
+    bit for bit."""
+
+    def __init__(self, src_rate, dst_rate):
+        self.src_rate, self.dst_rate = int(src_rate), int(dst_rate)
+        self.up, self.down, self.taps = resample_check(src_rate, dst_rate)
+        self.half = self.taps // 2
+        self.scale = RESAMPLE_ROLLOFF * min(1.0, self.up / self.down)
+        j = np.arange(self.taps, dtype=np.int64) - (self.half - 1)
+        q = np.abs(np.arange(self.up, dtype=np.int64)[:, None] - j[None, :] * self.up)            # |phase - j up|, exact
+        u = self.scale * (q.astype(np.float64) / self.up)
+        inside = u < RESAMPLE_ZEROS
+        kaiser = np.i0(RESAMPLE_BETA * np.sqrt(np.where(inside, 1.0 - (u / RESAMPLE_ZEROS) ** 2, 0.0))) / np.i0(RESAMPLE_BETA)
+        self.table = np.where(inside, self.scale * np.sinc(u) * kaiser, 0.0).astype(np.float32)
+        self._dev, self._columns = {}, None
+
+    def device(self, device):
+        import torch
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = torch.from_numpy(self.table).to(device)
+        return self._dev[key]
+
+    def columns(self):
+        """the table transposed, float32 [taps, up] contiguous (made on first use): what resample_numpy gathers from"""
+        if self._columns is None:
+            self._columns = np.ascontiguousarray(self.table.T)
+        return self._columns
+
+    def length(self, n):
+        return resample_length(n, self.up, self.down)
+
+
+_RESAMPLE_TABLES = {}
+
+
+def resample_tables(src_rate, dst_rate):
+    """the ResampleTables of the pair, built once per process"""
+    key = (int(src_rate), int(dst_rate))
+    if key not in _RESAMPLE_TABLES:
+        _RESAMPLE_TABLES[key] = ResampleTables(*key)
+    return _RESAMPLE_TABLES[key]
+
+
+RESAMPLE_NUMPY_BLOCK = 16384          # outputs summed at a time by resample_numpy (the temporaries stay in cache)
+
+
+def resample_numpy(tables, y):
+    """float32 [ceil(n up / down)] of one signal (n >= 1), with the kernel's operations in the kernel's order: for every output
+    acc = acc + table[phase][jj] * x[k0 - half + 1 + jj], jj ascending, the product and the sum each rounded to float32 - the bits of
+    csrc/resample.hip.  Vectorised over the outputs, a loop over the taps; the blocks only bound the temporaries."""
+    t = tables
+    y = np.ascontiguousarray(y, np.float32)
+    if y.ndim != 1 or len(y) < 1:
+        raise ValueError("resample: need a one-dimensional signal of at least one sample, got shape %r" % (y.shape,))
+    n_out = t.length(len(y))
+    padded = np.concatenate([np.zeros(t.half - 1, np.float32), y, np.zeros(t.half, np.float32)])     # x[k] at k + half - 1
+    columns = t.columns()
+    out = np.empty(n_out, np.float32)
+    for m0 in range(0, n_out, RESAMPLE_NUMPY_BLOCK):
+        pos = np.arange(m0, min(n_out, m0 + RESAMPLE_NUMPY_BLOCK), dtype=np.int64) * t.down
+        k0 = pos // t.up
+        phase = pos - k0 * t.up
+        acc = np.zeros(len(pos), np.float32)
+        for jj in range(t.taps):
+            acc += columns[jj][phase] * padded[k0 + jj]
+        out[m0:m0 + len(pos)] = acc
+    return out
+
+
+def resample_hip(tables, signals, device="cuda"):
+    """one launch of csrc/resample.hip over `signals` (float32 arrays of >= 1 sample, all at tables.src_rate): the list of their
+    float32 conversions"""
+    import torch
+    from .. import ops
+    t = tables
+    lens = np.asarray([len(s) for s in signals], np.int64)
+    if lens.min() < 1:
+        raise ValueError("resample: a signal of no samples")
+    io = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    oo = np.concatenate([[0], np.cumsum((lens * t.up + t.down - 1) // t.down)]).astype(np.int64)
+    x = torch.from_numpy(np.concatenate([np.ascontiguousarray(s, np.float32) for s in signals])).to(device)
+    y = torch.empty(int(oo[-1]), dtype=torch.float32, device=device)
+    ops.resample(x, torch.from_numpy(io).to(device), torch.from_numpy(oo).to(device), t.up, t.down, t.device(device), y)
+    y = y.cpu().numpy()
+    return [y[oo[u]:oo[u + 1]] for u in range(len(signals))]
+
+
 class Audio:
-    def __init__(self, hparams, backend=None, device="cuda"):
+    def __init__(self, hparams, backend=None, device="cuda", resample=False):
         self.hparams = hparams
+        self.resample = bool(resample)
         if backend is None:
             backend = "hip" if _gpu_bound() else "numpy"
         if backend not in ("hip", "numpy"):
@@ -302,23 +444,60 @@ class Audio:
         self.average_mel_level_db = np.array(hparams.average_mel_level_db, dtype=np.float32)
         self.stddev_mel_level_db = np.array(hparams.stddev_mel_level_db, dtype=np.float32)
 
-    def load_wav(self, path):
-        """float32 mono samples in [-1, 1) (int16 / 32768).  No resampling: the file's rate must be hparams.sample_rate."""
+    def read_wav(self, path):
+        """(rate, float32 mono samples in [-1, 1) (int16 / 32768)) of a file, at the file's own rate"""
         from scipy.io import wavfile
         rate, data = wavfile.read(path)
         if data.ndim != 1:
             raise ValueError("%s: %d channels, need a mono file (rate %d Hz, hparams.sample_rate %d Hz)"
                              % (path, data.shape[1], rate, self.hparams.sample_rate))
-        if rate != self.hparams.sample_rate:
+        if data.dtype == np.int16:
+            return rate, data.astype(np.float32) / np.float32(32768.0)
+        if data.dtype == np.int32:
+            return rate, (data.astype(np.float64) / 2147483648.0).astype(np.float32)
+        if data.dtype == np.uint8:
+            return rate, (data.astype(np.float32) - np.float32(128.0)) / np.float32(128.0)
+        return rate, data.astype(np.float32)
+
+    def check_rate(self, path, rate):
+        """without `resample`, a file whose rate is not hparams.sample_rate is refused by name"""
+        if rate != self.hparams.sample_rate and not self.resample:
             raise ValueError("%s: sample rate %d Hz differs from hparams.sample_rate %d Hz and resampling is not built"
                              % (path, rate, self.hparams.sample_rate))
-        if data.dtype == np.int16:
-            return data.astype(np.float32) / np.float32(32768.0)
-        if data.dtype == np.int32:
-            return (data.astype(np.float64) / 2147483648.0).astype(np.float32)
-        if data.dtype == np.uint8:
-            return (data.astype(np.float32) - np.float32(128.0)) / np.float32(128.0)
-        return data.astype(np.float32)
+
+    def load_wav(self, path):
+        """float32 mono samples at hparams.sample_rate.  A file at another rate is refused, or with `resample` converted."""
+        rate, y = self.read_wav(path)
+        self.check_rate(path, rate)
+        return self.resample_batch([y], [rate])[0] if self.resample else y
+
+    def resample_batch(self, ys, rates):
+        """the signals at hparams.sample_rate, in input order.  One already at that rate passes through as the same array; the rest
+        are grouped by source rate and each group goes out in launches of at most MAX_LAUNCH_SAMPLES input samples (backend "numpy":
+        one signal at a time).  A signal's result does not depend on what shares its batch."""
+        if len(ys) != len(rates):
+            raise ValueError("resample_batch: %d signals, %d rates" % (len(ys), len(rates)))
+        target = self.hparams.sample_rate
+        out, by_rate = list(ys), {}
+        for i, rate in enumerate(rates):
+            if int(rate) != target:
+                by_rate.setdefault(int(rate), []).append(i)
+        for rate, members in by_rate.items():
+            tables = resample_tables(rate, target)
+            if self.backend == "numpy":
+                for i in members:
+                    out[i] = resample_numpy(tables, ys[i])
+                continue
+            group, count = [], 0
+            for i in members + [None]:
+                if group and (i is None or count + len(ys[i]) > MAX_LAUNCH_SAMPLES):
+                    for k, y in zip(group, resample_hip(tables, [ys[k] for k in group], self.device)):
+                        out[k] = y
+                    group, count = [], 0
+                if i is not None:
+                    group.append(i)
+                    count += len(ys[i])
+        return out
 
     def save_wav(self, wav, path):
         from scipy.io import wavfile
