@@ -93,21 +93,9 @@ def main(argv=None):
             # batch size 1 unless --batch-size, targets merged into the source side (reference predict_mel.py:46-50)
             return dataset_factory(src, tgt, hparams).prepare_and_zip().group_by_batch(batch_size=a.batch_size) \
                 .merge_target_to_source()
-        from satt_amd.datasets.ljspeech import decode_source_record, resolve_accent_types
-
-        def gen():
-            for f in src:
-                s = decode_source_record(next(tfrecord.read_records(f)))
-                b = dict(source=s.source[None, :], source_length=np.array([s.source_length], np.int64),
-                         id=np.array([s.id], np.int64), key=[s.key], text=[s.text])
-                if s.speaker_id >= 0:
-                    b["speaker_id"] = np.array([s.speaker_id], np.int64)
-                if hparams.use_accent_type:       # same unknown-id mapping and missing-field error as the batched reader
-                    acc = np.full((1, len(s.source)), hparams.accent_type_offset, np.int64)
-                    acc[0, :s.source_length] = resolve_accent_types(s, hparams)
-                    b["accent_type"] = acc
-                yield b
-        return gen()
+        # no targets: the dataset's own source padding (the pad values, unknown-id mapping and missing-field error of group_by_batch)
+        from satt_amd.datasets.ljspeech import source_batches
+        return source_batches(src, hparams, a.batch_size)
 
     for p in model.predict(input_fn):
         key = p["key"]

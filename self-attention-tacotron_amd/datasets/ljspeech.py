@@ -236,12 +236,48 @@ def resolve_accent_types(s, hparams):
     return acc
 
 
+def pad_sources(sources, hparams, new=None):
+    """list of SourceData -> the source side of the engine's batch dict, padded to the longest: `source` with 0, `accent_type`
+    (use_accent_type) with accent_type_offset (table row 0).  The one statement of the source padding: pad_batch builds its source
+    side here, and so does a batch that has no targets (source_batches)."""
+    if new is None:
+        new = lambda name, shape, dtype: np.empty(shape, dtype)
+    B, Ti = len(sources), max(len(s.source) for s in sources)
+    source = new("source", (B, Ti), np.int64); source.fill(0)
+    accent = None
+    if getattr(hparams, "use_accent_type", False):       # padded with accent_type_offset (table row 0) where source pads with 0
+        accent = new("accent_type", (B, Ti), np.int64); accent.fill(hparams.accent_type_offset)
+    for b, s in enumerate(sources):
+        source[b, :len(s.source)] = s.source
+        if accent is not None:
+            accent[b, :s.source_length] = resolve_accent_types(s, hparams)
+    batch = dict(source=source, source_length=np.array([s.source_length for s in sources], np.int64),
+                 id=np.array([s.id for s in sources], np.int64), key=[s.key for s in sources], text=[s.text for s in sources])
+    if accent is not None:
+        batch["accent_type"] = accent
+    if sources[0].speaker_id >= 0:
+        batch["speaker_id"] = np.array([s.speaker_id for s in sources], np.int64)
+    return batch
+
+
+def source_batches(source_files, hparams, batch_size=1):
+    """batches of `batch_size` utterances that have no targets (free-running synthesis from text): one source record per file, in
+    the order given, padded by pad_sources"""
+    buf = []
+    for f in source_files:
+        buf.append(decode_source_record(next(tfrecord.read_records(f))))
+        if len(buf) == batch_size:
+            yield pad_sources(buf, hparams)
+            buf = []
+    if buf:
+        yield pad_sources(buf, hparams)
+
+
 def pad_batch(pairs, hparams, ring=None):
     """list of (SourceData, MelData | RawTarget) -> the engine's batch dict (padding values of group_by_batch, :264-281).
     RawTarget elements are normalised and silence-padded straight into their row of the batch tensor (satt_prepare_mel);
     ring (PinnedRing): the arrays live in page-locked memory (torch.as_tensor(a).is_pinned(): asynchronous H2D copies)."""
     B = len(pairs)
-    Ti = max(len(s.source) for s, _ in pairs)
     Tm = max(m.target_length for _, m in pairs)
     r = hparams.outputs_per_step
     W = pairs[0][1].raw_mel.shape[1] if isinstance(pairs[0][1], RawTarget) else pairs[0][1].mel.shape[1]
@@ -251,19 +287,13 @@ def pad_batch(pairs, hparams, ring=None):
         new = lambda name, shape, dtype: ring.array(slot, name, shape, dtype)
     else:
         new = lambda name, shape, dtype: np.empty(shape, dtype)
-    source = new("source", (B, Ti), np.int64); source.fill(0)
-    accent = None
-    if getattr(hparams, "use_accent_type", False):       # padded with accent_type_offset (table row 0) where source pads with 0
-        accent = new("accent_type", (B, Ti), np.int64); accent.fill(hparams.accent_type_offset)
+    src = pad_sources([s for s, _ in pairs], hparams, new)
     mel = new("mel", (B, Tm, W), np.float32)
     done = new("done", (B, Tm // r), np.float32); done.fill(1.0)
     smask = new("spec_loss_mask", (B, Tm), np.float32); smask.fill(0.0)
     bmask = new("binary_loss_mask", (B, Tm // r), np.float32); bmask.fill(0.0)
     tables = None
     for b, (s, m) in enumerate(pairs):
-        source[b, :len(s.source)] = s.source
-        if accent is not None:
-            accent[b, :s.source_length] = resolve_accent_types(s, hparams)
         L = m.target_length
         if isinstance(m, RawTarget):
             if tables is None:
@@ -282,15 +312,8 @@ def pad_batch(pairs, hparams, ring=None):
             done[b, :len(m.done)] = m.done
             smask[b, :L] = m.spec_loss_mask
             bmask[b, :len(m.binary_loss_mask)] = m.binary_loss_mask
-    batch = dict(source=source, source_length=np.array([s.source_length for s, _ in pairs], np.int64), mel=mel,
-                 target_length=np.array([m.target_length for _, m in pairs], np.int64), done=done,
-                 spec_loss_mask=smask, binary_loss_mask=bmask,
-                 id=np.array([s.id for s, _ in pairs], np.int64), key=[s.key for s, _ in pairs],
-                 text=[s.text for s, _ in pairs])
-    if accent is not None:
-        batch["accent_type"] = accent
-    if pairs[0][0].speaker_id >= 0:
-        batch["speaker_id"] = np.array([s.speaker_id for s, _ in pairs], np.int64)
+    batch = dict(src, mel=mel, target_length=np.array([m.target_length for _, m in pairs], np.int64), done=done,
+                 spec_loss_mask=smask, binary_loss_mask=bmask)
     if ring is not None:
         batch = PinnedBatch(batch)
         batch.pinned = (ring, slot)          # lease of the page-locked slot: Engine.to_device_batch fences its asynchronous upload
