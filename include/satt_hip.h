@@ -918,6 +918,15 @@ int satt_dec_mega_groups_forced(const satt_dec_mega_group* host_blocks, const vo
  * that is already non-zero is left as it is. */
 int satt_dec_stop_scan(const float* yout, int B, int rows, int NO, int t0, int nsteps, int min_steps, float stop_threshold,
                        int* flag, void* stream);
+/* per-utterance stop of a free-running batch (csrc/decode_ends.hip), behind a launch that evaluated no stop rule.  yout, rows, NO,
+ * t0, nsteps and the argument checks are those of satt_dec_stop_scan; ends [B] must be non-NULL as well.  ends[b] is sticky: 0
+ * while sample b has not ended, otherwise t_b + 1 for the FIRST step t_b > min_steps with 1 / (1 + exp(-stop logit)) >
+ * stop_threshold (the same expression, so the same bits); a sample whose ends[b] is non-zero is not looked at again.  *flag
+ * stays 0 until every ends[b] is non-zero and then becomes max_b ends[b], the number of steps the batch needed; a call with
+ * *flag != 0 changes nothing.  One workgroup, any B >= 1, no atomics: two runs give the same integers.  The caller zeroes ends
+ * and flag before the first window and passes windows in ascending order. */
+int satt_dec_ends_scan(const float* yout, int B, int rows, int NO, int t0, int nsteps, int min_steps, float stop_threshold,
+                       int* ends, int* flag, void* stream);
 /* new query row of the causal self-attention over the K|V|Q cache kvq [B,Td,3D] (row *step must hold K|V|Q of the step):
  * out [B,D] = softmax(q K^T * scale over rows 0..*step) V, heads side by side (modules/self_attention.py:45-65) */
 int satt_dec_self_attn(const float* kvq, float* out, const int* step, int B, int Td, int D, int heads, float scale,

@@ -3,7 +3,7 @@
 
 Usage: predict_mel.py --source-data-root=<dir> --target-data-root=<dir> --checkpoint-dir=<dir> --output-dir=<dir>
                       --selected-list-dir=<dir> [--checkpoint=<file>] [--selected-list-filename=<name>]
-                      [--hparams=<a=b>] [--hparam-json-file=<path>] [--batch-size=<N>]
+                      [--hparams=<a=b>] [--hparam-json-file=<path>] [--batch-size=<N>] [--stop-per-utterance]
                       [--wav] [--griffin-lim-iters=<N>] [--griffin-lim-power=<P>]
 
 For every key of the list: free-running decode (batch size 1) from `model-<step>.pt`, output `<key>.mfbsp` (raw
@@ -12,7 +12,8 @@ two alignment histories laid out [T_memory, T_query] as in the reference's predi
 reference's prediction record, utils/tfrecord.py:135-152).  `use_forced_alignment_mode=True` (models/models.py:387-428):
 pass 1 is the validation decode fed with the GROUND-TRUTH mel (needs --target-data-root), pass 2 feeds its own outputs
 back while both attention mechanisms return pass 1's alignments.  `--batch-size N` (forced-alignment mode only) decodes N
-utterances per pass.  `--wav` adds `<key>.wav`: Griffin-Lim phase reconstruction of the de-normalised mel (csrc/griffin_lim.hip).
+utterances per pass; `--batch-size N --stop-per-utterance` decodes N free-running utterances at once, each ending at its own stop
+token.  `--wav` adds `<key>.wav`: Griffin-Lim phase reconstruction of the de-normalised mel (csrc/griffin_lim.hip).
 Usage: see --help"""
 import argparse
 import glob
@@ -38,6 +39,11 @@ def main(argv=None):
                          "passes then decode N utterances at once and every prediction is cut to its own utterance's lengths.  The "
                          "values are those of the model AT THAT BATCH: the padding symbols of the shorter utterances reach the "
                          "encoder's convolutions exactly as in training, so they are not bit-equal to a batch-size-1 run")
+    ap.add_argument("--stop-per-utterance", action="store_true",
+                    help="free-running synthesis of --batch-size 2 .. 16 utterances per decode: every utterance ends at its own stop "
+                         "token and its prediction is cut there (the decode runs until the last one has ended, at most max_iters "
+                         "steps).  As with the forced batches, the values are those of the model at that batch.  Not with "
+                         "use_forced_alignment_mode=True, whose passes run the target's number of steps")
     ap.add_argument("--wav", action="store_true",
                     help="write <key>.wav next to every <key>.mfbsp: Griffin-Lim phase reconstruction of the de-normalised mel (16-bit "
                          "PCM at hparams.sample_rate, peak 0.95) - a quick listen, not a vocoder; mel_to_wav.py does the same afterwards")
@@ -64,10 +70,14 @@ def main(argv=None):
     hparams.parse(a.hparams)
     if hparams.use_forced_alignment_mode and not a.target_data_root:
         raise SystemExit("use_forced_alignment_mode aligns to the reference audio: --target-data-root is required")
-    if a.batch_size > 1 and not hparams.use_forced_alignment_mode:
+    if a.stop_per_utterance and hparams.use_forced_alignment_mode:
+        raise SystemExit("--stop-per-utterance is the stop rule of free-running synthesis: use_forced_alignment_mode=True decodes the "
+                         "target's number of steps")
+    if a.batch_size > 1 and not hparams.use_forced_alignment_mode and not a.stop_per_utterance:
         # (the reference's stop rule of a batch fires only when EVERY sample is above the threshold at the same step; where to cut
-        #  each sample of a free-running batch is a decision this driver does not take)
-        raise SystemExit("--batch-size > 1 needs use_forced_alignment_mode=True: a free-running batch has no per-utterance end")
+        #  each sample of a free-running batch is decided by --stop-per-utterance alone)
+        raise SystemExit("--batch-size > 1 needs use_forced_alignment_mode=True: a free-running batch has no per-utterance end "
+                         "(or --stop-per-utterance, which gives it one)")
     # reference predict_mel.py:40-57: estimator = tacotron_model_factory(hparams, checkpoint_dir, run_config);
     # estimator.predict(input_fn, checkpoint_path=...)
     audio = None
@@ -97,7 +107,7 @@ def main(argv=None):
         from satt_amd.datasets.ljspeech import source_batches
         return source_batches(src, hparams, a.batch_size)
 
-    for p in model.predict(input_fn):
+    for p in model.predict(input_fn, stop_each=a.stop_per_utterance):
         key = p["key"]
         mel = (p["mel_postnet"] if "mel_postnet" in p else p["mel"]).astype("<f4")
         assert mel.shape[1] == hparams.num_mels

@@ -294,6 +294,7 @@ SIGNATURES = {
     "satt_dec_mega_groups_forced_variant": (_I, [C.POINTER(DecMegaGroup), _I, C.POINTER(DecMegaForcedParams)]),
     "satt_dec_mega_groups_forced": (_I, [C.POINTER(DecMegaGroup), _P, _I, C.POINTER(DecMegaForcedParams), _P]),
     "satt_dec_stop_scan": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _P, _P]),
+    "satt_dec_ends_scan": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "satt_dec_self_attn": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "satt_melspec_supported": (_I, [_I, _I, _I, _I]),
     "satt_melspec": (_I, [C.POINTER(MelspecParams), _P]),

@@ -17,6 +17,7 @@ dropout is off, BatchNorm uses the moving statistics.
 """
 import math
 
+import numpy as np
 import torch
 
 from . import ops
@@ -29,8 +30,16 @@ class DecodeSession:
     (B, Ti, Td, feeding mode, forced alignments, stop rule).  Kept on the engine and reused by later calls of the same
     shape: a new utterance only refills the memories and resets the recurrent state."""
 
-    def __init__(self, eng, B, Ti, Td, teacher, forced, min_steps, stop_threshold, steps_per_graph, use_graph):
+    def __init__(self, eng, B, Ti, Td, teacher, forced, min_steps, stop_threshold, steps_per_graph, use_graph, stop_each=False):
         c, P, dev = eng.cfg, eng.P, eng.dev
+        # stop_each (free running, B >= 2: infer(stop="each")): every utterance ends on its own.  No launch evaluates a stop rule - the
+        # session is built like a teacher-fed one in that respect, but keeps feeding its own outputs - and satt_dec_ends_scan runs
+        # behind every launch or replay (replay(), scan_ends()); `ends` [B] holds the samples' step counts, 0 = not ended yet
+        self.stop_each = bool(stop_each)
+        assert not (self.stop_each and (teacher or forced or B < 2))
+        self.ends = torch.zeros(B, dtype=torch.int32, device=dev) if self.stop_each else None
+        self._stop_args = (int(min_steps), float(stop_threshold))
+        self._t0 = 0
         self.eng, self.B, self.Ti, self.K = eng, B, Ti, max(1, int(steps_per_graph))
         self.Td = Td
         # The persistent kernel (csrc/decode_mega2.hip) is decided FIRST, by the library itself (satt_dec_mega_supported on the
@@ -81,7 +90,8 @@ class DecodeSession:
                 self._mega_shape = shape
                 self._mega_single = not dual_form
                 self._groups = (B + 1) // 2 if groups else 0
-                self.K = max(self.K, self.MEGA_GROUPS_STEPS if groups else self.MEGA_STEPS)
+                # (stop_each at B = 2: no stop rule inside the launch either, so the group launch length bounds the overshoot)
+                self.K = max(self.K, self.MEGA_GROUPS_STEPS if (groups or self.stop_each) else self.MEGA_STEPS)
         Ba = self.Ba = 2 * self._groups if self._groups else B
         Tdp = self.Tdp = (Td + self.K - 1) // self.K * self.K          # whole graphs: rows past Td are scratch
         f32 = dict(dtype=torch.float32, device=dev)
@@ -130,7 +140,7 @@ class DecodeSession:
             if graph:
                 L.append((ops.dec_linear, prm))
         # stop logit of step t = last column of output row t + 1 (evaluated on the device, one step later)
-        stop_rule = None if teacher else (self.yout.view(-1)[NO + NO - 1:], (Tdp + 1) * NO, NO, self.flag, stop_threshold, min_steps)
+        stop_rule = None if (teacher or self.stop_each) else (self.yout.view(-1)[NO + NO - 1:], (Tdp + 1) * NO, NO, self.flag, stop_threshold, min_steps)
         # ---- pre-net of the fed-back frame (MultiSpeakerPreNet: modules/multi_speaker_modules.py:27-32).  Dropout is off unless
         #      apply_dropout_on_inference keeps it on in the plain PreNet layers (modules/module.py:564-577): mask of row
         #      (b, step) of a [B, Td, units] activation, seeded by the engine's device seed word
@@ -250,7 +260,7 @@ class DecodeSession:
                 locF=P["dec.att1.F"], locFb=P["dec.att1.bF"], locU=P["dec.att1.U"], v1=P["dec.att1.v"], b1=P["dec.att1.b"],
                 lengths=self.lengths, keys1=self.keys1, values1=self.values1, ca=ca, ha=ha, c1=c1, h1=h1, c2=c2, h2=h2, a_state=self.a_state,
                 alpha_state=self.alpha_state, ctx=self.ctx, yout=self.yout, tin=self.tin, align1=self.al1, **second,
-                part=self._mega_part, ctab=self.ctab, step=self.steps2, flag=None if (teacher or self._groups) else self.flag,
+                part=self._mega_part, ctab=self.ctab, step=self.steps2, flag=None if (teacher or self._groups or self.stop_each) else self.flag,
                 err=self._mega_err, **spk, **({} if self._fb is None else dict(Wfh=self._fb["hi"], Wfl=self._fb["lo"], bfb=self._fb["bias"])))
             assert ops.dec_mega_supported(mega)
             # options of the kernel (a block of their own; None: ops.dec_mega as ever).  Transition agent: the kernel forms no
@@ -341,7 +351,6 @@ class DecodeSession:
         self._gproto, self._gblocks = blocks, {}
         self.mega_groups = self._group_blocks(self.K)[0]
         assert ops.dec_mega_groups_supported(self.mega_groups)
-        self._t0 = 0
 
     def _group_blocks(self, nsteps):
         """(host array, device copy) of the group blocks for launches of `nsteps` steps (the blocks carry nsteps: a ragged last
@@ -520,6 +529,9 @@ class DecodeSession:
                 ops.dec_mega_groups_forced(*self._group_blocks(n), self.mega_forced)
             else:
                 ops.dec_mega_groups(*self._group_blocks(n))
+            if self.stop_each:      # (the B real samples: the padding sample of an odd batch is not one of them)
+                self.scan_ends(n)
+                return
             if self.tin is None:
                 ops.dec_stop_scan(self.yout, self.B, self.Tdp + 1, self.yout.shape[-1], self._t0, n, self._mega_shape["min_steps"],
                                   self._mega_shape["stop_threshold"], self.flag)
@@ -532,8 +544,18 @@ class DecodeSession:
                 ops.dec_mega_opt(self.mega, self.mega_opt, n)
             else:
                 ops.dec_mega(self.mega, n)
+            if self.stop_each:
+                self.scan_ends(n)
         else:
             self.graph.replay()
+            if self.stop_each:      # outside the captured graph, with the host's t0; the graph always runs its K steps
+                self.scan_ends(self.K if nsteps is None else max(1, min(self.K, int(nsteps))))
+
+    def scan_ends(self, n):
+        """stop_each: the per-utterance stop over the n steps behind the host's step count `_t0` (satt_dec_ends_scan), which advances"""
+        ops.dec_ends_scan(self.yout, self.B, self.Tdp + 1, self.yout.shape[-1], self._t0, n, self._stop_args[0], self._stop_args[1],
+                          self.ends, self.flag)
+        self._t0 += n
 
     def check(self):
         """host-synchronous: raise if an exchange of the persistent kernel timed out (sticky word)"""
@@ -543,10 +565,13 @@ class DecodeSession:
     def reset(self):
         """recurrent state of a new utterance (zeros; alpha_0 = onehot(0): modules/forward_attention.py:128-136)"""
         self.steps2.zero_(); self.flag.zero_()
+        self._t0 = 0
+        if getattr(self, "ends", None) is not None:
+            self.ends.zero_()
         if self.mega is not None or self.mega_groups is not None:
             self._mega_part.zero_()        # exchange granules carry step + 1 as their tag: a new utterance starts from untagged ones
         if self.mega_groups is not None:      # the groups' own step words and state ([G][parity][2][...])
-            self._gsteps.zero_(); self._t0 = 0
+            self._gsteps.zero_()
             for t in self._gstates + [self._ga_state, self._gctx, self._galpha_state]:
                 t.zero_()
             self._galpha_state[:, 0, :, 0] = 1.0
@@ -560,7 +585,8 @@ class DecodeSession:
 
 
 def infer(eng, source, source_length, max_steps=None, teacher=None, speaker_id=None, min_steps=10, stop_threshold=0.5,
-          check_every=8, teacher_alignments=None, use_graph=True, dropout_seed=None, encoder_outputs=None, speaker_embed=None, accent_type=None):
+          check_every=8, teacher_alignments=None, use_graph=True, dropout_seed=None, encoder_outputs=None, speaker_embed=None, accent_type=None,
+          stop="all"):
     """eng: Engine.  source int64 [B,Ti], source_length int64 [B] (device tensors or array-likes).
     accent_type int64 [B,Ti]: required by a model with accent types (use_accent_type=True), ignored otherwise.
     speaker_id int64 [B] (multi-speaker model).  With the hparam speaker_for_synthesis > -1 EVERY row is synthesised with that
@@ -574,6 +600,13 @@ def infer(eng, source, source_length, max_steps=None, teacher=None, speaker_id=N
     teacher_alignments=(a1, a2), each [B,T,Ti] with T >= the number of steps (a2 = None for the single-source model):
     forced-alignment mode (use_forced_alignment_mode: modules/teacher_forcing_attention.py:13-78, models/models.py:411-428)
     - the mechanisms return the given alignment of the step; contexts and alignment histories follow them.
+    stop="all": the reference's rule, above.  stop="each" (free running only): every utterance ends on its own - sample b at its first
+    step t > min_steps with sigmoid(stop) > stop_threshold - and the decode ends when the last one has.  No launch evaluates a rule;
+    satt_dec_ends_scan runs behind each launch or replay (launches of MEGA_GROUPS_STEPS steps on the persistent kernel, so the
+    overshoot is bounded by one launch plus the one the host polls behind).  The result gains steps_each (int64 numpy [B]: the
+    samples' step counts, Td where one never ended), steps = max of them, and every returned tensor has `steps` rows - cutting
+    sample b to steps_each[b] is the caller's job (Model.predict(stop_each=True) does it).  At B = 1 it IS the rule of "all"
+    and takes that path.
     use_graph=False issues the same kernels step by step without capturing them (debugging).
     dropout_seed (apply_dropout_on_inference only): seed of this call's pre-net dropout masks.  None: the engine's seed word
     plus a per-call increment, so repeated synthesis of one utterance draws different masks (as the reference's stateful TF
@@ -581,12 +614,18 @@ def infer(eng, source, source_length, max_steps=None, teacher=None, speaker_id=N
     Returns dict(mel [B,T*r,num_mels], stop [B,T,1], alignment1 [B,T,Ti], alignment2 [B,T,Ti], steps=T,
     lstm_out, sa_out)."""
     c, P, dev = eng.cfg, eng.P, eng.dev
+    if stop not in ("all", "each"):
+        raise ValueError("infer: stop must be 'all' or 'each' (got %r)" % (stop,))
+    if stop == "each" and (teacher is not None or teacher_alignments is not None):
+        raise ValueError("infer: stop='each' is the stop rule of a free-running decode; a teacher-fed or forced-alignment pass runs "
+                         "its given number of steps")
     f32 = dict(dtype=torch.float32, device=dev)
     batch = {"source": torch.as_tensor(source).to(dev).contiguous(),
              "source_length": torch.as_tensor(source_length).to(dev).contiguous()}
     if c.num_speakers > 0 and speaker_embed is None and (speaker_id is not None or c.speaker_for_synthesis < 0):
         batch["speaker_id"] = torch.as_tensor(speaker_id).to(dev).contiguous()
     B, Ti = batch["source"].shape
+    each = stop == "each" and B > 1
     if c.accent and encoder_outputs is None:
         if accent_type is None:
             raise ValueError("infer: accent_type ([B, Ti] int64) is required by a model with use_accent_type=True")
@@ -622,14 +661,14 @@ def infer(eng, source, source_length, max_steps=None, teacher=None, speaker_id=N
     key = (B, Ti, Td, teacher is not None, forced, int(min_steps), float(stop_threshold), int(check_every), bool(use_graph),
            ops.get_precision(), DecodeSession.FUSE, DecodeSession.MAX_CHAIN, DecodeSession.MEGA, DecodeSession.MEGA_MAX_B,
            DecodeSession.MEGA_STEPS, DecodeSession.MEGA_FOLD_FEEDBACK, DecodeSession.MEGA_GROUPS, DecodeSession.MEGA_GROUPS_MAX_B,
-           DecodeSession.MEGA_GROUPS_STEPS, DecodeSession.MEGA_FORCED)
+           DecodeSession.MEGA_GROUPS_STEPS, DecodeSession.MEGA_FORCED, each)
     cache = eng.__dict__.setdefault("_decode_sessions", {})
     ses = cache.get(key)
     if ses is None:         # (the kernels read the parameters in place: an optimiser step does not invalidate a session)
         if len(cache) >= 8:
             cache.clear()
         ses = cache[key] = DecodeSession(eng, B, Ti, Td, teacher is not None, forced, min_steps, stop_threshold, check_every,
-                                         use_graph)
+                                         use_graph, stop_each=each)
     # ---- memories (same as Engine.forward): values = memory * seq_mask, keys = values W_m
     V1, V2 = c.cbhg_out_units, c.sa_units
     ses.lengths.copy_(slen)
@@ -691,6 +730,14 @@ def infer(eng, source, source_length, max_steps=None, teacher=None, speaker_id=N
     if ses.graph is None and ses.mega is None and ses.mega_groups is None:
         for t in range(Td):
             ses.run_step()
+            if each:                # the scan behind every K steps, read at once (this is the debugging path)
+                if (t + 1) % K == 0 or t == Td - 1:
+                    ses.scan_ends(t + 1 - ses._t0)
+                    f = int(ses.flag.item()) if t > min_steps else 0
+                    if f:
+                        steps = f
+                        break
+                continue
             if teacher is None and t > min_steps and (t % K == 0 or t == Td - 1):
                 f = int(ses.flag.item())
                 if f:
@@ -719,12 +766,17 @@ def infer(eng, source, source_length, max_steps=None, teacher=None, speaker_id=N
             steps = min(f, Td)
         ses.check()
     ev_b.record(); ev_b.synchronize()
+    each_kw = {}
+    if stop == "each":
+        e = ses.ends.cpu().numpy().astype(np.int64) if each else np.full((B,), steps, dtype=np.int64)
+        each_kw["steps_each"] = np.where(e > 0, e, Td)
     y = ses.yout[:, 1:steps + 1]
     yout = y.reshape(B * steps, NO) if steps == Td else None
     return dict(yout=yout, mel=y[:, :, :NO - 1].reshape(B, steps * r, nm), stop=y[:, :, NO - 1:].contiguous(),
                 alignment1=ses.al1[:, :steps].clone(), alignment2=ses.al2[:, :steps].clone() if c.dual else None,
                 steps=steps, decode_ms=ev_a.elapsed_time(ev_b), lstm_out=lstm_out.view(B, Ti, -1), sa_out=sa_out.view(B, Ti, -1) if c.dual else None,
-                enc_alignment=ctx["enc_align"].view(B, c.sa_heads, Ti, Ti) if (c.dual and ctx.get("enc_align") is not None) else None)
+                enc_alignment=ctx["enc_align"].view(B, c.sa_heads, Ti, Ti) if (c.dual and ctx.get("enc_align") is not None) else None,
+                **each_kw)
 
 
 def postnet_infer(eng, mel):

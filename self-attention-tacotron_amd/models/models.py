@@ -475,8 +475,11 @@ class DualSourceSelfAttentionTacotronModel:
         return out
 
     # ------------------------------------------------------------------ predict (models/models.py:566-588)
-    def predict(self, input_fn):
-        """yields ONE prediction dict per utterance, keys and layouts of the reference's EstimatorSpec predictions"""
+    def predict(self, input_fn, stop_each=False):
+        """yields ONE prediction dict per utterance, keys and layouts of the reference's EstimatorSpec predictions.
+        stop_each=True (free running, batches of several utterances): every utterance ends at its OWN stop token
+        (infer(stop="each")) and its prediction is cut there - the decode runs until the last one has ended.  The values are those of
+        the model at that batch (padding symbols reach the encoder convolutions), not asserted equal to a batch-1 run."""
         from ..inference import infer, postnet_infer
         eng, hp = self.engine, self.params
         r = hp.outputs_per_step
@@ -495,13 +498,17 @@ class DualSourceSelfAttentionTacotronModel:
                             min_steps=1 << 30, teacher_alignments=(first["alignment1"], first["alignment2"] if eng.cfg.dual else None),
                             **acc)
             else:
-                out = infer(eng, b["source"], b["source_length"], max_steps=hp.max_iters, speaker_id=spk, **acc)
-            mel_post = postnet_infer(eng, out["mel"]) if eng.cfg.use_postnet_v2 else None
+                out = infer(eng, b["source"], b["source_length"], max_steps=hp.max_iters, speaker_id=spk, **acc,
+                            **(dict(stop="each") if (stop_each and B > 1) else {}))
+            each = out.get("steps_each")
+            # (per-utterance stop: the post-net runs per utterance on its cut mel below - the zero padding its `same` convolutions see
+            #  past the end is then that of the batch-1 run, not the frames decoded after the utterance's stop token)
+            mel_post = postnet_infer(eng, out["mel"]) if (eng.cfg.use_postnet_v2 and each is None) else None
             enc_al = out.get("enc_alignment")
             # forced-alignment mode over a batch of several utterances: the batch is padded to its longest target and memory, so each
             # prediction is cut to its own utterance - mel rows to ceil(target_length / r) * r, the query axis of the alignments
             # likewise, the memory axis and `source` to source_length: the shapes of the utterance's batch-1 run
-            cut = hp.use_forced_alignment_mode and B > 1
+            cut = (hp.use_forced_alignment_mode and B > 1) or each is not None
             for i in range(B):
                 p = {"id": int(batch["id"][i]) if "id" in batch else i, "key": batch["key"][i] if "key" in batch else str(i),
                      "mel": out["mel"][i].float().cpu().numpy()}
@@ -519,8 +526,11 @@ class DualSourceSelfAttentionTacotronModel:
                 if eng.cfg.accent:                                              # models/models.py:585
                     p["accent_type"] = np.asarray(batch["accent_type"][i])
                 p["text"] = batch["text"][i] if "text" in batch else ""
+                if each is not None and eng.cfg.use_postnet_v2:
+                    p["mel_postnet"] = postnet_infer(eng, out["mel"][i:i + 1, :int(each[i]) * r])[0].float().cpu().numpy()
                 if cut:
-                    nq, ns = -(-int(batch["target_length"][i]) // r), int(batch["source_length"][i])
+                    nq = int(each[i]) if each is not None else -(-int(batch["target_length"][i]) // r)
+                    ns = int(batch["source_length"][i])
                     for k in ("mel", "mel_postnet", "ground_truth_mel"):
                         if k in p:
                             p[k] = p[k][:nq * r]

@@ -1375,6 +1375,13 @@ def dec_stop_scan(yout, B, rows, NO, t0, nsteps, min_steps, stop_threshold, flag
                                              float(stop_threshold), _p(flag), _s()), "dec_stop_scan")
 
 
+def dec_ends_scan(yout, B, rows, NO, t0, nsteps, min_steps, stop_threshold, ends, flag):
+    """per-utterance stop over the steps t0 .. t0 + nsteps - 1 of yout [B][rows][NO]: ends[b] = t_b + 1 at sample b's first
+    qualifying step (sticky, int32 [B]); *flag = max(ends) once every sample has ended"""
+    _lib.check(_lib.lib().satt_dec_ends_scan(_p(yout), int(B), int(rows), int(NO), int(t0), int(nsteps), int(min_steps),
+                                             float(stop_threshold), _p(ends), _p(flag), _s()), "dec_ends_scan")
+
+
 def dec_self_attn(kvq, out, step, B, Td, D, heads, scale):
     _lib.check(_lib.lib().satt_dec_self_attn(_p(kvq), _p(out), _p(step), B, Td, D, heads, float(scale), _s()), "dec_self_attn")
 

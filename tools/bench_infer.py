@@ -9,7 +9,9 @@ steps such batches ran on before.
 use_forced_alignment_mode): one free-running utterance produces the alignments, the timed utterances replay them.
 --forced --batch 3 .. 16: the forced instantiations in group mode (path "persistent, groups, forced"); --no-groups returns it to the
 hipGraph path as well.
-usage: python tools/bench_infer.py [--steps 200] [--batch 1] [--no-groups] [--forced] [--hparams-json FILE] [--hparams "k=v,..."] [--repeat N]"""
+--stop-each: the per-utterance stop rule (infer(..., stop="each"): satt_dec_ends_scan behind every launch; B = 2 takes launches of
+MEGA_GROUPS_STEPS steps) with min_steps out of reach like every run here, so both rules decode the same number of steps.
+usage: python tools/bench_infer.py [--steps 200] [--batch 1] [--no-groups] [--forced] [--stop-each] [--hparams-json FILE] [--hparams "k=v,..."] [--repeat N]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -29,6 +31,7 @@ ap.add_argument("--no-graph", action="store_true")
 ap.add_argument("--mega-max-b", type=int, default=None, help="largest batch that takes the persistent step kernel (default: the session's)")
 ap.add_argument("--no-groups", action="store_true", help="DecodeSession.MEGA_GROUPS = False: batches of 3 .. 16 on the launch-per-layer path")
 ap.add_argument("--forced", action="store_true", help="time forced-alignment utterances fed the alignments of one free-running utterance")
+ap.add_argument("--stop-each", action="store_true", help='time infer(..., stop="each"), the per-utterance stop rule of free-running batches')
 ap.add_argument("--hparams-json", default=None, help="hparams file of the model (default: the LJSpeech dimensions)")
 ap.add_argument("--hparams", default=None, help='comma-separated name=value overrides of the model\'s hparams')
 ap.add_argument("--repeat", type=int, default=1, help="timed utterances (one JSON line each)")
@@ -39,6 +42,8 @@ if a.mega_max_b is not None:
     DecodeSession.MEGA_MAX_B = a.mega_max_b
 if a.batch < 1 or a.batch > 16:
     ap.error("--batch: 1 .. 16")
+if a.stop_each and a.forced:
+    ap.error("--stop-each is the stop rule of a free-running decode")
 if a.no_groups:
     from satt_amd.inference import DecodeSession
     DecodeSession.MEGA_GROUPS = False
@@ -57,6 +62,8 @@ B, Ti = a.batch, 100
 src = g.integers(1, 68, (B, Ti)); src[:, 0] = 0; src[:, -1] = 0
 sl = np.full((B,), Ti, dtype=np.int64)
 ap_kw = dict(max_steps=a.steps, min_steps=10 ** 6, check_every=a.steps_per_graph, use_graph=not a.no_graph)
+if a.stop_each:
+    ap_kw["stop"] = "each"
 if cfg.num_speakers > 0:
     ap_kw["speaker_id"] = (np.arange(B) % cfg.num_speakers + cfg.speaker_offset).astype(np.int64)
 if a.forced:                            # the alignments of one free-running utterance; the forced session is built by the warm-up below
@@ -76,7 +83,7 @@ for _ in range(a.repeat):
         "persistent, forced" if getattr(ses, "mega_forced", None) is not None else "persistent" if getattr(ses, "mega", None) is not None else \
         ("persistent, groups" if getattr(ses, "mega_groups", None) is not None else "launch-per-layer")
     frames = a.steps * cfg.r * B
-    print(json.dumps({"metric": "forced-alignment decode" if a.forced else "free-running decode (config 5)", "model": (a.hparams_json or "ljspeech") + (" + " + a.hparams if a.hparams else ""), "path": path, "batch": B, "Ti": Ti, "decoder_steps": out["steps"],
+    print(json.dumps({"metric": "forced-alignment decode" if a.forced else "free-running decode (config 5)", "model": (a.hparams_json or "ljspeech") + (" + " + a.hparams if a.hparams else ""), "path": path, "stop": "each" if a.stop_each else "all", "batch": B, "Ti": Ti, "decoder_steps": out["steps"],
                       "ms_per_step": 1e3 * dt / a.steps, "utterance_ms_incl_encoder": 1e3 * dt_all,
                       "steps_per_graph": a.steps_per_graph, "graph": not a.no_graph,
                       "mel_frames_per_sec": frames / dt,
