@@ -1035,6 +1035,44 @@ int satt_resample_supported(int up, int down, int taps);
 int satt_resample_run_length(void);
 int satt_resample(const satt_resample_params* p, void* stream);
 
+/* ---- dynamic time warping of a batch of feature-sequence pairs in one launch (csrc/dtw.hip).  Pair u is
+ * a[a_offsets[u] .. a_offsets[u + 1]) (Ta rows of K floats) against b[b_offsets[u] .. b_offsets[u + 1]) (Tb rows):
+ *   c(i, j) = sqrt(sum_k (a[i, k] - b[j, k])^2)   fp32, k ascending in one chain; difference, product and sum each rounded (no
+ *                                                 fused multiply-add), the square root correctly rounded
+ *   D(0, 0) = c(0, 0);  D(i, j) = best + c(i, j)  best = the smallest of the predecessors that exist, taken in the order diagonal
+ *                                                 (i-1, j-1), up (i-1, j), left (i, j-1); a later candidate replaces an earlier
+ *                                                 one only when it is strictly smaller
+ *   L(0, 0) = 1;        L(i, j) = L(chosen predecessor) + 1
+ * cost[u] = D(Ta-1, Tb-1), steps[u] = L(Ta-1, Tb-1).  With dirs, dir_offsets, path and path_offsets (all four or none) the chosen
+ * predecessor of every cell is kept as a byte in dirs[dir_offsets[u] .. dir_offsets[u + 1]) (at least Ta * Tb bytes; the layout
+ * inside is the kernel's own) and path[2 path_offsets[u] ..] receives steps[u] pairs (i, j), ascending from (0, 0) to
+ * (Ta-1, Tb-1); path_offsets count PAIRS and pair u needs room for Ta + Tb - 1.  total_dirs (bytes) and total_path (pairs) are the
+ * sizes of the two buffers.  A pair whose ranges do not lie inside the totals, with Ta or Tb outside 1 .. satt_dtw_max_frames() or
+ * with too little workspace or path room is left untouched; nothing is read or written out of bounds whatever the tables hold.
+ * max_ta / max_tb: the caller's statement of the longest Ta and Tb of the batch; max_ta picks the rows a lane owns, and a pair
+ * with more rows than max_ta rounded up to 512, 1024 or 2048 is left untouched as well.  satt_dtw_supported (no GPU needed) == 1:
+ * 1 <= Ta, Tb <= 2048, 1 <= K <= 128; a launch whose max_ta, max_tb, K lie outside returns SATT_E_UNSUPPORTED; null pointers, a
+ * partial set of path pointers, counts or totals < 1, max_ta > total_a or max_tb > total_b return SATT_E_BADARG; both before
+ * anything is launched.  One workgroup per pair, no atomics, nothing crosses workgroups: two launches are bit-identical and a
+ * pair's result does not depend on its batch or its place in it. */
+typedef struct {
+  int n_pairs, K, max_ta, max_tb;
+  int64_t total_a, total_b, total_dirs, total_path;
+  const float* a;              /* [total_a, K] */
+  const float* b;              /* [total_b, K] */
+  const int64_t* a_offsets;    /* [n_pairs + 1] */
+  const int64_t* b_offsets;    /* [n_pairs + 1] */
+  float* cost;                 /* [n_pairs] */
+  int32_t* steps;              /* [n_pairs] */
+  uint8_t* dirs;               /* [total_dirs] or NULL */
+  const int64_t* dir_offsets;  /* [n_pairs + 1] or NULL */
+  int32_t* path;               /* [total_path][2] or NULL */
+  const int64_t* path_offsets; /* [n_pairs + 1] or NULL */
+} satt_dtw_params;
+int satt_dtw_supported(int Ta, int Tb, int K);
+int satt_dtw_max_frames(void);
+int satt_dtw(const satt_dtw_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -167,6 +167,14 @@ class ResampleParams(C.Structure):
                 [(n, C.c_void_p) for n in ("signal_in", "in_offsets", "out_offsets", "table", "signal_out")])
 
 
+class DtwParams(C.Structure):
+    """satt_dtw_params (include/satt_hip.h): dynamic time warping of a batch of feature-sequence pairs"""
+    _fields_ = ([(n, C.c_int) for n in ("n_pairs", "K", "max_ta", "max_tb")] +
+                [(n, c_i64) for n in ("total_a", "total_b", "total_dirs", "total_path")] +
+                [(n, C.c_void_p) for n in ("a", "b", "a_offsets", "b_offsets", "cost", "steps", "dirs", "dir_offsets", "path",
+                                           "path_offsets")])
+
+
 # name -> (restype, argtypes); must list EVERY symbol declared in include/satt_hip.h
 _P = C.c_void_p
 _I = C.c_int
@@ -304,6 +312,9 @@ SIGNATURES = {
     "satt_resample_supported": (_I, [_I, _I, _I]),
     "satt_resample_run_length": (_I, []),
     "satt_resample": (_I, [C.POINTER(ResampleParams), _P]),
+    "satt_dtw_supported": (_I, [_I, _I, _I]),
+    "satt_dtw_max_frames": (_I, []),
+    "satt_dtw": (_I, [C.POINTER(DtwParams), _P]),
     "satt_l2_reg": (_I, [_P, _P, _P, _I, _F, _P, _P, _P]),
     "satt_sumsq": (_I, [_P, c_i64, _P, _P]),
     "satt_sumsq_state_floats": (_I, []),

@@ -490,6 +490,45 @@ def resample(signal_in, in_offsets, out_offsets, up, down, table, signal_out):
     _lib.check(_lib.lib().satt_resample(C.byref(p), _s()), "resample")
 
 
+def dtw_supported(Ta, Tb, K):
+    """True when satt_dtw takes pairs of these lengths and this feature width (host-only: needs the library, not a GPU)"""
+    return bool(_lib.lib().satt_dtw_supported(int(Ta), int(Tb), int(K)))
+
+
+def dtw_max_frames():
+    """the longest sequence csrc/dtw.hip takes: three diagonals of D and L in 48 KiB of LDS"""
+    return int(_lib.lib().satt_dtw_max_frames())
+
+
+def dtw(a, b, a_offsets, b_offsets, max_ta, max_tb, cost, steps, dirs=None, dir_offsets=None, path=None, path_offsets=None):
+    """dynamic time warping of a batch of pairs in one launch (csrc/dtw.hip).  a: fp32 [total a, K], b: fp32 [total b, K]; pair u is
+    a[a_offsets[u] .. a_offsets[u + 1]) against b[b_offsets[u] .. b_offsets[u + 1]) (int64 [U + 1]); max_ta / max_tb: the longest
+    of each side.  cost fp32 [U] and steps int32 [U] receive D and L of the corner.  With dirs (uint8, Ta * Tb bytes per pair at
+    dir_offsets) and path (int32 [total, 2], Ta + Tb - 1 pairs of room per pair at path_offsets) the warping path is written too.
+    Shapes outside satt_dtw_supported raise."""
+    assert a.dtype == torch.float32 and a.dim() == 2 and a.is_contiguous()
+    assert b.dtype == torch.float32 and b.dim() == 2 and b.is_contiguous() and b.shape[1] == a.shape[1]
+    assert a_offsets.dtype == torch.int64 and b_offsets.dtype == torch.int64 and a_offsets.numel() == b_offsets.numel() >= 2
+    n = a_offsets.numel() - 1
+    assert cost.dtype == torch.float32 and cost.is_contiguous() and cost.numel() >= n
+    assert steps.dtype == torch.int32 and steps.is_contiguous() and steps.numel() >= n
+    want_path = dirs is not None
+    if want_path:
+        assert dirs.dtype == torch.uint8 and dirs.dim() == 1 and dirs.is_contiguous()
+        assert path.dtype == torch.int32 and path.dim() == 2 and path.shape[1] == 2 and path.is_contiguous()
+        assert dir_offsets.dtype == torch.int64 and path_offsets.dtype == torch.int64 and dir_offsets.numel() == path_offsets.numel() == n + 1
+    else:
+        assert dir_offsets is None and path is None and path_offsets is None
+    K = a.shape[1]
+    if not dtw_supported(max_ta, max_tb, K):
+        raise ValueError("dtw does not take Ta=%d Tb=%d K=%d (1 <= Ta, Tb <= %d, 1 <= K <= 128)" % (max_ta, max_tb, K, dtw_max_frames()))
+    p = _lib.DtwParams(n_pairs=n, K=K, max_ta=max_ta, max_tb=max_tb, total_a=a.shape[0], total_b=b.shape[0],
+                       total_dirs=dirs.numel() if want_path else 0, total_path=path.shape[0] if want_path else 0, a=_p(a), b=_p(b),
+                       a_offsets=_p(a_offsets), b_offsets=_p(b_offsets), cost=_p(cost), steps=_p(steps), dirs=_p(dirs),
+                       dir_offsets=_p(dir_offsets), path=_p(path), path_offsets=_p(path_offsets))
+    _lib.check(_lib.lib().satt_dtw(C.byref(p), _s()), "dtw")
+
+
 def griffin_lim_supported(n_fft, win, hop):
     """True when satt_griffin_lim takes these STFT parameters (host-only: needs the library, not a GPU)"""
     return bool(_lib.lib().satt_griffin_lim_supported(int(n_fft), int(win), int(hop)))

@@ -586,6 +586,47 @@ class Audio:
             out += griffin_lim_hip(t, [g[0] for g in group], [g[1] for g in group], iters, alpha, self.device)
         return out
 
+    def mel_distance_batch(self, preds, refs, feature="mcep", order=13, want_paths=False, keys=None):
+        """DTW distance of every (predicted, ground-truth) pair of NORMALISED mels [T, num_mels] (what .mfbsp files and the prediction
+        records hold): a list of dicts frames_pred, frames_ref, steps, cost, value (and path int32 [steps, 2] of (pred frame, ref
+        frame) with want_paths).  feature "mcep": mel_cepstrum of the de-normalised dB mel, value = MCD in dB =
+        (10 sqrt(2) / ln 10) cost / steps; "mel": the dB rows themselves, value = cost / steps / sqrt(num_mels), an RMS log-spectral
+        distance in dB.  Both backends align the same float32 features (utils/mel_distance.py; on "hip" all pairs in one launch) and
+        agree bit for bit.  `keys` name the pairs in error messages (default: their index)."""
+        from . import mel_distance as md
+        if feature not in ("mcep", "mel"):
+            raise ValueError("feature must be 'mcep' or 'mel', got %r" % (feature,))
+        if len(preds) != len(refs):
+            raise ValueError("mel_distance_batch: %d predictions, %d references" % (len(preds), len(refs)))
+        M = self.hparams.num_mels
+        pairs = []
+        for u, (pred, ref) in enumerate(zip(preds, refs)):
+            name = keys[u] if keys is not None else "pair %d" % u
+            feats = []
+            for what, S in (("prediction", pred), ("reference", ref)):
+                S = np.asarray(S)
+                if S.ndim != 2 or S.shape[1] != M:
+                    raise ValueError("%s: the %s has shape %r, need [T, num_mels=%d]" % (name, what, S.shape, M))
+                if not 1 <= S.shape[0] <= md.DTW_MAX_FRAMES:
+                    raise ValueError("%s: the %s has %d frames, need 1 .. %d" % (name, what, S.shape[0], md.DTW_MAX_FRAMES))
+                if not np.isfinite(S).all():
+                    raise ValueError("%s: the %s holds non-finite values" % (name, what))
+                S_db = self.denormalize_mel(S.astype(np.float64))
+                feats.append(md.mel_cepstrum(S_db, order) if feature == "mcep" else S_db.astype(np.float32))
+            pairs.append(tuple(feats))
+        if self.backend == "numpy":
+            res = [md.dtw_numpy(a, b, want_paths) for a, b in pairs]
+        else:
+            res = md.dtw_hip(pairs, want_paths, self.device)
+        scale = md.MCD_SCALE if feature == "mcep" else 1.0 / math.sqrt(M)
+        out = []
+        for (a, b), r in zip(pairs, res):
+            o = dict(frames_pred=len(a), frames_ref=len(b), steps=int(r[1]), cost=float(r[0]), value=scale * float(r[0]) / int(r[1]))
+            if want_paths:
+                o["path"] = r[2]
+            out.append(o)
+        return out
+
     def inv_melspectrogram(self, S, iters=60, alpha=0.99, power=1.0, seed=0):
         """float32 [(T - 1) hop] from one dB mel spectrogram [num_mels, T], the layout melspectrogram returns"""
         return self.inv_melspectrogram_batch([np.asarray(S).T], iters, alpha, power, seed)[0]
