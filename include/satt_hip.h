@@ -1073,6 +1073,45 @@ int satt_dtw_supported(int Ta, int Tb, int K);
 int satt_dtw_max_frames(void);
 int satt_dtw(const satt_dtw_params* p, void* stream);
 
+/* ---- YIN pitch tracking of a batch of utterances on the mel frame grid in one launch (csrc/yin.hip).  Utterance u
+ * is signal[in_offsets[u] .. in_offsets[u + 1]) (n >= 1 samples) and owns index frame_offsets[u] .. frame_offsets[u + 1] of f0,
+ * aperiodicity and power; the caller sets frame_offsets[u + 1] - frame_offsets[u] = 1 + n / hop.  An utterance with another count,
+ * with n < 1 or with offsets outside the totals is left untouched; nothing is read or written out of bounds whatever the tables
+ * hold.  With W = window, s = t hop - (W + tau_max) / 2 for frame t and x = 0 outside [0, n):
+ *   d(tau)  = sum_{j = 0 .. W - 1} (x[s + j] - x[s + j + tau])^2   tau = 0 .. tau_max; fp32, j ascending in one chain; difference,
+ *                                                                 product and sum each rounded (no fused multiply-add)
+ *   power   = (sum_j x[s + j]^2) / W                               the same way; the division correctly rounded
+ *   c(tau)  = c(tau - 1) + d(tau), c(0) = 0                        one ascending chain
+ *   d'(0)   = 1;  d'(tau) = (d(tau) * tau) / c(tau) if c(tau) > 0, else 1        product rounded, division correctly rounded
+ *   tau0    = the smallest tau in [tau_min, tau_max - 1] with d'(tau) < threshold.  None: f0 = 0, aperiodicity = the minimum of d'
+ *             over [tau_min, tau_max] (a NaN entry is passed over; +inf when all are NaN).  Otherwise tau* walks up from tau0 while
+ *             tau* + 1 <= tau_max - 1 and d'(tau* + 1) < d'(tau*); aperiodicity = d'(tau*); with a, b, c = d' at tau* - 1, tau*,
+ *             tau* + 1: num = a - c, den = (a - b) + (c - b), off = den > 0 ? (0.5 num) / den : 0, cut to [-1, 1];
+ *             f0 = sample_rate / ((float)tau* + off).
+ * Digital silence and a constant signal give d = 0, d' = 1, f0 = 0.  satt_yin_supported (no GPU needed) == 1:
+ * 1 <= window <= satt_yin_max_window() = 1536, 3 <= tau_max <= satt_yin_max_lag() = 1023, 1 <= hop <= 2^20 (the defaults of
+ * utils/pitch.py at 8 kHz .. 61 kHz); anything else SATT_E_UNSUPPORTED.  Null pointers, counts or totals < 1, tau_min outside
+ * [2, tau_max - 1], sample_rate not > 0 or a NaN threshold return SATT_E_BADARG; both before anything is launched.
+ * satt_yin_run_length: the frames a workgroup takes (seams of the launch fall at its multiples, counted through the batch).  No
+ * atomics, nothing crosses workgroups: two launches are bit-identical and an utterance's result does not depend on its batch or
+ * its place in it; the float32 NumPy backend (utils/pitch.py yin_numpy) gives the same bits. */
+typedef struct {
+  int window, tau_min, tau_max, hop, n_utts;
+  float sample_rate, threshold;
+  int64_t total_in, total_frames;
+  const float* signal;          /* [total_in] */
+  const int64_t* in_offsets;    /* [n_utts + 1] */
+  const int64_t* frame_offsets; /* [n_utts + 1] */
+  float* f0;                    /* [total_frames] */
+  float* aperiodicity;          /* [total_frames] */
+  float* power;                 /* [total_frames] */
+} satt_yin_params;
+int satt_yin_supported(int window, int tau_max, int hop);
+int satt_yin_max_window(void);
+int satt_yin_max_lag(void);
+int satt_yin_run_length(void);
+int satt_yin(const satt_yin_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

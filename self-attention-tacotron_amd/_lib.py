@@ -175,6 +175,13 @@ class DtwParams(C.Structure):
                                            "path_offsets")])
 
 
+class YinParams(C.Structure):
+    """satt_yin_params (include/satt_hip.h): YIN pitch tracking of a batch of utterances"""
+    _fields_ = ([(n, C.c_int) for n in ("window", "tau_min", "tau_max", "hop", "n_utts")] +
+                [("sample_rate", C.c_float), ("threshold", C.c_float), ("total_in", c_i64), ("total_frames", c_i64)] +
+                [(n, C.c_void_p) for n in ("signal", "in_offsets", "frame_offsets", "f0", "aperiodicity", "power")])
+
+
 # name -> (restype, argtypes); must list EVERY symbol declared in include/satt_hip.h
 _P = C.c_void_p
 _I = C.c_int
@@ -315,6 +322,11 @@ SIGNATURES = {
     "satt_dtw_supported": (_I, [_I, _I, _I]),
     "satt_dtw_max_frames": (_I, []),
     "satt_dtw": (_I, [C.POINTER(DtwParams), _P]),
+    "satt_yin_supported": (_I, [_I, _I, _I]),
+    "satt_yin_max_window": (_I, []),
+    "satt_yin_max_lag": (_I, []),
+    "satt_yin_run_length": (_I, []),
+    "satt_yin": (_I, [C.POINTER(YinParams), _P]),
     "satt_l2_reg": (_I, [_P, _P, _P, _I, _F, _P, _P, _P]),
     "satt_sumsq": (_I, [_P, c_i64, _P, _P]),
     "satt_sumsq_state_floats": (_I, []),

@@ -529,6 +529,35 @@ def dtw(a, b, a_offsets, b_offsets, max_ta, max_tb, cost, steps, dirs=None, dir_
     _lib.check(_lib.lib().satt_dtw(C.byref(p), _s()), "dtw")
 
 
+def yin_supported(window, tau_max, hop):
+    """True when satt_yin takes this window, longest lag and hop (host-only: needs the library, not a GPU)"""
+    return bool(_lib.lib().satt_yin_supported(int(window), int(tau_max), int(hop)))
+
+
+def yin_limits():
+    """(longest window, longest lag, frames a workgroup takes) of csrc/yin.hip"""
+    L = _lib.lib()
+    return int(L.satt_yin_max_window()), int(L.satt_yin_max_lag()), int(L.satt_yin_run_length())
+
+
+def yin(signal, in_offsets, frame_offsets, window, tau_min, tau_max, hop, sample_rate, threshold, f0, aperiodicity, power):
+    """YIN pitch tracking of a batch of utterances in one launch (csrc/yin.hip).  signal: fp32 [total in], utterance u at
+    in_offsets[u] .. in_offsets[u + 1] (int64 [U + 1], n >= 1 samples), its 1 + n // hop frames of f0, aperiodicity and power (fp32
+    [total frames] each) at frame_offsets[u] .. frame_offsets[u + 1].  Parameters outside satt_yin_supported raise."""
+    assert signal.dtype == torch.float32 and signal.dim() == 1 and signal.is_contiguous()
+    assert in_offsets.dtype == torch.int64 and frame_offsets.dtype == torch.int64 and in_offsets.numel() == frame_offsets.numel() >= 2
+    for o in (f0, aperiodicity, power):
+        assert o.dtype == torch.float32 and o.dim() == 1 and o.is_contiguous() and o.numel() == f0.numel()
+    if not yin_supported(window, tau_max, hop):
+        raise ValueError("yin does not take window=%d tau_max=%d hop=%d (1 <= window <= %d, 3 <= tau_max <= %d, 1 <= hop <= 2^20)"
+                         % ((window, tau_max, hop) + yin_limits()[:2]))
+    p = _lib.YinParams(window=window, tau_min=tau_min, tau_max=tau_max, hop=hop, n_utts=in_offsets.numel() - 1,
+                       sample_rate=float(sample_rate), threshold=float(threshold), total_in=signal.numel(), total_frames=f0.numel(),
+                       signal=_p(signal), in_offsets=_p(in_offsets), frame_offsets=_p(frame_offsets), f0=_p(f0),
+                       aperiodicity=_p(aperiodicity), power=_p(power))
+    _lib.check(_lib.lib().satt_yin(C.byref(p), _s()), "yin")
+
+
 def griffin_lim_supported(n_fft, win, hop):
     """True when satt_griffin_lim takes these STFT parameters (host-only: needs the library, not a GPU)"""
     return bool(_lib.lib().satt_griffin_lim_supported(int(n_fft), int(win), int(hop)))

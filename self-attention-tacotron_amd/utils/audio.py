@@ -627,6 +627,24 @@ class Audio:
             out.append(o)
         return out
 
+    def f0_batch(self, ys, fmin=None, fmax=None, window_ms=None, threshold=None, silence_db=None):
+        """YIN pitch tracks of signals at hparams.sample_rate on the mel frame grid (utils/pitch.py): a list of dicts
+        f0 (float32, Hz; 0 where no lag passes the threshold), voiced (bool), aperiodicity and power (float32), each [1 + n // hop].
+        On "hip" the batch is one launch of csrc/yin.hip (cut at MAX_LAUNCH_SAMPLES), on "numpy" its float32 restatement: the same
+        bits.  The defaults are pitch.FMIN / FMAX / WINDOW_MS / THRESHOLD / SILENCE_DB; they are arguments, not hparams."""
+        from . import pitch
+        kw = dict(fmin=pitch.FMIN if fmin is None else fmin, fmax=pitch.FMAX if fmax is None else fmax,
+                  window_ms=pitch.WINDOW_MS if window_ms is None else window_ms,
+                  threshold=pitch.THRESHOLD if threshold is None else threshold)
+        silence_db = pitch.SILENCE_DB if silence_db is None else silence_db
+        sr, hop = self.hparams.sample_rate, self.tables.hop
+        pitch.yin_check(sr, hop, kw["fmin"], kw["fmax"], kw["window_ms"])
+        if self.backend == "numpy":
+            res = [pitch.yin_numpy(y, sr, hop, **kw) for y in ys]
+        else:
+            res = pitch.yin_hip(ys, sr, hop, device=self.device, **kw) if len(ys) else []
+        return [dict(f0=f0, voiced=pitch.voicing(f0, power, silence_db), aperiodicity=ap, power=power) for f0, ap, power in res]
+
     def inv_melspectrogram(self, S, iters=60, alpha=0.99, power=1.0, seed=0):
         """float32 [(T - 1) hop] from one dB mel spectrogram [num_mels, T], the layout melspectrogram returns"""
         return self.inv_melspectrogram_batch([np.asarray(S).T], iters, alpha, power, seed)[0]
