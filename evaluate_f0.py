@@ -4,6 +4,7 @@ compared along the dynamic-time-warping path of their mel spectrograms.
 
 Usage: evaluate_f0.py --hparam-json-file=<hparams.json> [--hparams=<a=b>] [--backend=hip|numpy] [--fmin=<Hz>] [--fmax=<Hz>]
                       [--window-ms=<ms>] [--threshold=<x>] [--silence-db=<dB>] [--iters=<N>] [--seed=<S>]
+                      [--tracker=yin|viterbi] [--jump-cost=<x>] [--switch-cost=<x>] [--unvoiced-cost=<x>] [--lag-bias=<x>]
                       [--pred-wav-dir=<D> --ref-wav-dir=<D>] [--write-tracks] <prediction_dir> [<out_dir>]
 
 Default mode: every `<key>.tfrecord` of <prediction_dir> (predict_mel.py's prediction record) holds the predicted `mel` and, when the
@@ -22,8 +23,16 @@ loudest frame.  These are arguments of this tool, not hparams.  Per key on stdou
 <out_dir>: <prediction_dir>): key, frames_pred, frames_ref, steps, voiced_both, vuv_error, f0_rmse_cents, f0_rmse_hz, log_f0_corr,
 gpe (empty where undefined: no step voiced on both sides; the correlation below 2 such steps or at zero variance);
 <out_dir>/summary.json: count, the means over the keys where defined, the voiced-step-weighted RMSEs, every parameter, and the skipped
-keys.  --write-tracks adds <key>.f0.npz with both tracks and the path.  There is no octave-error smoothing, and this is not WORLD or
-pYIN: values compare between runs of this tool only."""
+keys.  --write-tracks adds <key>.f0.npz with both tracks and the path.
+
+--tracker yin (the default) decides every frame alone and has no octave-error smoothing: on Griffin-Lim audio it reports the octave
+above wherever the fundamental is weak.  --tracker viterbi keeps the 8 deepest dips of d' of every frame and chooses among them and
+an "unvoiced" state along the utterance by dynamic programming (csrc/f0_viterbi.hip, or its NumPy restatement: the same bits):
+an octave between neighbouring frames costs --jump-cost (0.3), entering or leaving "unvoiced" --switch-cost (0.1), an unvoiced frame
+--unvoiced-cost (default: the value of --threshold), and a candidate d' + --lag-bias (0.1) * period / longest lag.  A frame is then
+voiced when the path takes a candidate there; utterances of more than 2048 frames are refused.  summary.json then also holds
+tracker and the four costs (a summary without `tracker` is a yin run), and --write-tracks the state track of both sides.  Neither
+tracker is WORLD or pYIN: values compare between runs of this tool with the same tracker only."""
 import argparse
 import csv
 import glob
@@ -49,6 +58,11 @@ def main(argv=None):
     ap.add_argument("--silence-db", type=float, default=None, metavar="DB")
     ap.add_argument("--iters", type=int, default=60, metavar="N", help="Griffin-Lim iterations of both sides (default mode)")
     ap.add_argument("--seed", type=int, default=0, metavar="S", help="seed of the starting phase of both sides (default mode)")
+    ap.add_argument("--tracker", choices=("yin", "viterbi"), default="yin")
+    ap.add_argument("--jump-cost", type=float, default=None, help="viterbi: the cost of an octave between neighbouring frames")
+    ap.add_argument("--switch-cost", type=float, default=None, help="viterbi: the cost of entering or leaving the unvoiced state")
+    ap.add_argument("--unvoiced-cost", type=float, default=None, help="viterbi: the cost of an unvoiced frame (default: --threshold)")
+    ap.add_argument("--lag-bias", type=float, default=None, help="viterbi: added to a candidate's d', times period / longest lag")
     ap.add_argument("--pred-wav-dir", default=None, metavar="D")
     ap.add_argument("--ref-wav-dir", default=None, metavar="D")
     ap.add_argument("--write-tracks", action="store_true", help="write <key>.f0.npz with both tracks and the path")
@@ -76,6 +90,14 @@ def main(argv=None):
                window_ms=pitch.WINDOW_MS if a.window_ms is None else a.window_ms,
                threshold=pitch.THRESHOLD if a.threshold is None else a.threshold,
                silence_db=pitch.SILENCE_DB if a.silence_db is None else a.silence_db)
+    costs = {}
+    if a.tracker == "viterbi":
+        costs = dict(tracker=a.tracker, jump_cost=pitch.JUMP_COST if a.jump_cost is None else a.jump_cost,
+                     switch_cost=pitch.SWITCH_COST if a.switch_cost is None else a.switch_cost,
+                     unvoiced_cost=par["threshold"] if a.unvoiced_cost is None else a.unvoiced_cost,
+                     lag_bias=pitch.LAG_BIAS if a.lag_bias is None else a.lag_bias)
+    elif not all(v is None for v in (a.jump_cost, a.switch_cost, a.unvoiced_cost, a.lag_bias)):
+        raise SystemExit("--jump-cost, --switch-cost, --unvoiced-cost and --lag-bias belong to --tracker viterbi")
 
     skipped = []
     if a.pred_wav_dir is not None:
@@ -116,7 +138,7 @@ def main(argv=None):
                                               iters=a.iters, seed=a.seed)
         sig_pred, sig_ref = wavs[:len(keys)], wavs[len(keys):]
     dist = audio.mel_distance_batch(preds, refs, want_paths=True, keys=keys)
-    tracks = audio.f0_batch(sig_pred + sig_ref, **par)
+    tracks = audio.f0_batch(sig_pred + sig_ref, **par, **costs)
     tr_pred, tr_ref = tracks[:len(keys)], tracks[len(keys):]
 
     out_dir = a.out_dir or a.prediction_dir
@@ -147,7 +169,7 @@ def main(argv=None):
         return math.sqrt(sum(m["voiced_both"] * m[k] ** 2 for m in rows if m[k] is not None) / nb) if nb else None
     summary = dict(count=len(rows), mode=mode, steps=sum(m["steps"] for m in rows), voiced_both=sum(m["voiced_both"] for m in rows),
                    mean={k: mean(k) for k in METRICS}, weighted_f0_rmse_cents=weighted("f0_rmse_cents"),
-                   weighted_f0_rmse_hz=weighted("f0_rmse_hz"), sample_rate=hparams.sample_rate, hop=audio.tables.hop, **par,
+                   weighted_f0_rmse_hz=weighted("f0_rmse_hz"), sample_rate=hparams.sample_rate, hop=audio.tables.hop, **par, **costs,
                    iters=a.iters if mode == "griffin_lim" else None, seed=a.seed if mode == "griffin_lim" else None, skipped=skipped)
     with open(os.path.join(out_dir, "summary.json"), "w") as f:
         json.dump(summary, f, indent=1)

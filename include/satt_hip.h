@@ -1112,6 +1112,61 @@ int satt_yin_max_lag(void);
 int satt_yin_run_length(void);
 int satt_yin(const satt_yin_params* p, void* stream);
 
+/* ---- the period candidates of every frame, for the Viterbi tracker below (csrc/yin.hip, the d' of satt_yin with another pick;
+ * DESIGN.md 3.6).  Signal, offsets, window, lags, hop, power and what is left untouched are those of satt_yin.  Lag k in
+ * [tau_min, tau_max - 1] is a dip when d'(k) < d'(k - 1) and d'(k) <= d'(k + 1) (a NaN makes both false).  The SATT_F0_CANDIDATES = 8
+ * dips with the smallest d' are kept (ties to the smaller lag) and stored in ascending lag order: slot c of frame g holds
+ * cand_period[8 g + c] = (float)k + off, off the parabola and clamp of satt_yin, and cand_value[8 g + c] = d'(k); unused slots hold
+ * period 0 and value +inf.  A frame of NaN / Inf samples has no dip.  Refusals are those of satt_yin (there is no threshold and no
+ * sample rate).  The float32 NumPy backend (utils/pitch.py yin_candidates_numpy) gives the same bits. */
+#define SATT_F0_CANDIDATES 8
+typedef struct {
+  int window, tau_min, tau_max, hop, n_utts;
+  int64_t total_in, total_frames;
+  const float* signal;          /* [total_in] */
+  const int64_t* in_offsets;    /* [n_utts + 1] */
+  const int64_t* frame_offsets; /* [n_utts + 1] */
+  float* cand_period;           /* [total_frames, 8] */
+  float* cand_value;            /* [total_frames, 8] */
+  float* power;                 /* [total_frames] */
+} satt_yin_candidates_params;
+int satt_yin_candidates(const satt_yin_candidates_params* p, void* stream);
+
+/* ---- the cheapest path through the candidates of every utterance of a batch in one launch (csrc/f0_viterbi.hip).
+ * Utterance u owns frames frame_offsets[u] .. frame_offsets[u + 1] of cand_period, cand_value, gate, f0 and state and entry u of
+ * cost; T = frame_offsets[u + 1] - frame_offsets[u].  States 0 .. 7 of a frame are its slots (used when period > 0), state 8 is
+ * "unvoiced"; gate is a byte per frame, non-zero where the host's silence rule lets the frame be voiced.  All fp32, every
+ * operation rounded on its own, divisions correctly rounded:
+ *   obs(t, j)   = value_j + lag_bias * (period_j / (float)tau_max) for a used slot of a gated-in frame, else +inf;
+ *                 obs(t, 8) = unvoiced_cost
+ *   trans(q, j) = 0 when both are 8, switch_cost when exactly one is 8, else jump_cost * (hi / lo - 1) with hi = the period of q
+ *                 when it is > the period of j, else that of j, and lo the other one
+ *   delta_0     = obs(0, .);  delta_t(j) = (min_q (delta_{t-1}(q) + trans(q, j))) + obs(t, j): best = +inf and predecessor 8 to
+ *                 begin with, q ascending, taken when strictly < best (a tie keeps the smaller q; +inf and NaN are passed over)
+ *   end         = the smallest state with the minimum of delta_{T-1} (found the same way); the path walks the predecessors back
+ *   f0[t]       = sample_rate / period in a candidate state, 0 in state 8;  state[t] = the state;  cost[u] = delta_{T-1}(end)
+ * An utterance whose frame range does not lie in [0, total_frames] or whose T is outside 1 .. satt_f0_viterbi_max_frames() = 2048
+ * is left untouched; nothing is read or written out of bounds whatever the tables hold.  satt_f0_viterbi_supported(max_frames)
+ * (no GPU needed) == 1 for 1 <= max_frames <= 2048; a longer max_frames returns SATT_E_UNSUPPORTED.  Null pointers, n_utts or
+ * total_frames < 1, tau_max < 1, sample_rate not > 0 or a cost that is negative, infinite or NaN return SATT_E_BADARG; both before
+ * anything is launched.  One workgroup per utterance, no atomics, nothing crosses workgroups: two launches are bit-identical and
+ * an utterance's result does not depend on its batch; utils/pitch.py f0_viterbi_numpy gives the same bits. */
+typedef struct {
+  int n_utts, max_frames, tau_max;
+  float sample_rate, jump_cost, switch_cost, unvoiced_cost, lag_bias;
+  int64_t total_frames;
+  const float* cand_period;      /* [total_frames, 8] */
+  const float* cand_value;       /* [total_frames, 8] */
+  const uint8_t* gate;           /* [total_frames] */
+  const int64_t* frame_offsets;  /* [n_utts + 1] */
+  float* f0;                     /* [total_frames] */
+  uint8_t* state;                /* [total_frames] */
+  float* cost;                   /* [n_utts] */
+} satt_f0_viterbi_params;
+int satt_f0_viterbi_supported(int max_frames);
+int satt_f0_viterbi_max_frames(void);
+int satt_f0_viterbi(const satt_f0_viterbi_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,21 @@ class YinParams(C.Structure):
                 [(n, C.c_void_p) for n in ("signal", "in_offsets", "frame_offsets", "f0", "aperiodicity", "power")])
 
 
+class YinCandidatesParams(C.Structure):
+    """satt_yin_candidates_params (include/satt_hip.h): the period candidates of every frame of a batch of utterances"""
+    _fields_ = ([(n, C.c_int) for n in ("window", "tau_min", "tau_max", "hop", "n_utts")] +
+                [("total_in", c_i64), ("total_frames", c_i64)] +
+                [(n, C.c_void_p) for n in ("signal", "in_offsets", "frame_offsets", "cand_period", "cand_value", "power")])
+
+
+class F0ViterbiParams(C.Structure):
+    """satt_f0_viterbi_params (include/satt_hip.h): the cheapest path through the candidates of a batch of utterances"""
+    _fields_ = ([(n, C.c_int) for n in ("n_utts", "max_frames", "tau_max")] +
+                [(n, C.c_float) for n in ("sample_rate", "jump_cost", "switch_cost", "unvoiced_cost", "lag_bias")] +
+                [("total_frames", c_i64)] +
+                [(n, C.c_void_p) for n in ("cand_period", "cand_value", "gate", "frame_offsets", "f0", "state", "cost")])
+
+
 # name -> (restype, argtypes); must list EVERY symbol declared in include/satt_hip.h
 _P = C.c_void_p
 _I = C.c_int
@@ -327,6 +342,10 @@ SIGNATURES = {
     "satt_yin_max_lag": (_I, []),
     "satt_yin_run_length": (_I, []),
     "satt_yin": (_I, [C.POINTER(YinParams), _P]),
+    "satt_yin_candidates": (_I, [C.POINTER(YinCandidatesParams), _P]),
+    "satt_f0_viterbi_supported": (_I, [_I]),
+    "satt_f0_viterbi_max_frames": (_I, []),
+    "satt_f0_viterbi": (_I, [C.POINTER(F0ViterbiParams), _P]),
     "satt_l2_reg": (_I, [_P, _P, _P, _I, _F, _P, _P, _P]),
     "satt_sumsq": (_I, [_P, c_i64, _P, _P]),
     "satt_sumsq_state_floats": (_I, []),

@@ -14,6 +14,11 @@
 //               f0 = sample_rate / ((float)tau* + off)
 // These are the operations of utils/pitch.py yin_numpy in its order, so the two agree bit for bit.
 //
+// satt_yin_candidates is the same kernel with another pick (yin_k<NCH, true>), for the Viterbi tracker of csrc/f0_viterbi.hip: lag k
+// in [tau_min, tau_max - 1] is a dip when d'(k) < d'(k - 1) and d'(k) <= d'(k + 1); the YIN_K = 8 dips with the smallest d' (ties to
+// the smaller lag) are stored in ascending lag order as period = (float)k + off (the parabola above) and value = d'(k), unused slots
+// as period 0 and value +inf: the operations of utils/pitch.py yin_candidates_numpy.
+//
 // A workgroup of 4 waves takes YIN_RUN = 16 consecutive frames of the batch (frames are numbered through the utterances; the
 // utterance of a frame is found by bisection of frame_offsets), a wave one frame at a time.  The wave stages the frame's span
 // xs[e] = x[s + e] in its own LDS region (zeros outside the utterance, and on to the end of the region: every word read below was
@@ -49,7 +54,23 @@ struct YinArgs {
   long long total_in, total_frames;
   const float* x; const int64_t* in_offsets; const int64_t* frame_offsets;
   float* f0; float* ap; float* pw;
+  float* cper; float* cval;               // the candidates kernel's outputs, [total_frames, YIN_K] each
 };
+
+constexpr int YIN_K = SATT_F0_CANDIDATES;
+
+// the parabola through d' at t - 1, t, t + 1 and its clamp: the offset of the minimum from t
+__device__ __forceinline__ float yin_offset(float ya, float yb, float yc) {
+#pragma clang fp contract(off)
+  const float num = ya - yc, den = (ya - yb) + (yc - yb);
+  float off = 0.f;
+  if (den > 0.f) {
+    off = (0.5f * num) / den;
+    if (off > 1.f) off = 1.f;
+    if (off < -1.f) off = -1.f;
+  }
+  return off;
+}
 
 // the last utterance whose first frame is <= g
 __device__ __forceinline__ int yin_utt(const int64_t* frame_offsets, int n_utts, long long g) {
@@ -61,7 +82,8 @@ __device__ __forceinline__ int yin_utt(const int64_t* frame_offsets, int n_utts,
   return lo;
 }
 
-template <int NCH>                       // chunks of 256 lags: the smallest that covers 0 .. tau_max
+// NCH: chunks of 256 lags, the smallest that covers 0 .. tau_max.  CAND: the pick of satt_yin_candidates in place of satt_yin's
+template <int NCH, bool CAND>
 __global__ __launch_bounds__(YIN_NT) void yin_k(YinArgs a) {
 #pragma clang fp contract(off)            // every difference, product and sum below is rounded on its own: NumPy's float32 bits
   extern __shared__ __attribute__((aligned(16))) float yin_smem[];
@@ -171,7 +193,53 @@ __global__ __launch_bounds__(YIN_NT) void yin_k(YinArgs a) {
       }
     }
     __syncthreads();
-    if (ok) {                                                  // the pick: every lane takes the same way through it
+    if constexpr (CAND) {
+      if (ok) {
+        // a lane marks the dips among its lags tau_min + lane + 64 i (at most 16 of them: tau_max <= 1023) in a register, then
+        // YIN_K rounds take the wave-wide minimum of (d', lag) over the marks that are left and its owner drops the mark.  A dip's
+        // d' is below its neighbour's, so it is neither NaN nor +inf: +inf with lag INT_MAX stands for "none"
+        unsigned marks = 0;
+        for (int i = 0, t = a.tau_min + lane; t < tmax; ++i, t += 64) {          // tau_min >= 2: t - 1 >= 1; t + 1 <= tau_max
+          const float v = db[t];
+          if (v < db[t - 1] && v <= db[t + 1]) marks |= 1u << i;
+        }
+        float selv[YIN_K]; int selk[YIN_K];
+#pragma unroll
+        for (int r = 0; r < YIN_K; ++r) {
+          float bv = INFINITY; int bk = 0x7fffffff;
+          for (unsigned m = marks; m; m &= m - 1) {                              // ascending lags: a strict < keeps the smaller one
+            const int t = a.tau_min + lane + 64 * (__ffs((int)m) - 1);
+            const float v = db[t];
+            if (v < bv) { bv = v; bk = t; }
+          }
+#pragma unroll
+          for (int o = 32; o >= 1; o >>= 1) {
+            const float ov = __shfl_xor(bv, o); const int ol = __shfl_xor(bk, o);
+            if (ov < bv || (ov == bv && ol < bk)) { bv = ov; bk = ol; }
+          }
+          selv[r] = bv; selk[r] = bk;
+          if (bk != 0x7fffffff && ((bk - a.tau_min) & 63) == lane) marks &= ~(1u << ((bk - a.tau_min) >> 6));
+        }
+        // lane c < YIN_K stores the slot c: the kept dip with c kept dips at smaller lags (the lags are distinct)
+        if (lane < YIN_K) {
+          float v = INFINITY, per = 0.f;
+#pragma unroll
+          for (int i = 0; i < YIN_K; ++i) {
+            int rank = 0;
+#pragma unroll
+            for (int j = 0; j < YIN_K; ++j) rank += selk[j] < selk[i] ? 1 : 0;
+            if (selk[i] != 0x7fffffff && rank == lane) {
+              const int t = selk[i];                                             // tau_min <= t <= tau_max - 1 by construction
+              v = selv[i];
+              per = (float)t + yin_offset(db[t - 1], db[t], db[t + 1]);
+            }
+          }
+          a.cper[g * YIN_K + lane] = per;
+          a.cval[g * YIN_K + lane] = v;
+        }
+        if (lane == 0) a.pw[g] = pw / (float)W;
+      }
+    } else if (ok) {                                           // the pick: every lane takes the same way through it
       int t0 = -1;
       for (int b = a.tau_min; b < tmax && t0 < 0; b += 64) {
         const int t = b + lane;
@@ -191,14 +259,7 @@ __global__ __launch_bounds__(YIN_NT) void yin_k(YinArgs a) {
         while (t + 1 < tmax && db[t + 1] < db[t]) ++t;         // at most tau_max steps
         const float ya = db[t - 1], yb = db[t], yc = db[t + 1];  // 1 <= t - 1 and t + 1 <= tau_max: tau_min >= 2
         ap = yb;
-        const float num = ya - yc, den = (ya - yb) + (yc - yb);
-        float off = 0.f;
-        if (den > 0.f) {
-          off = (0.5f * num) / den;
-          if (off > 1.f) off = 1.f;
-          if (off < -1.f) off = -1.f;
-        }
-        f0 = a.sr / ((float)t + off);
+        f0 = a.sr / ((float)t + yin_offset(ya, yb, yc));
       }
       if (lane == 0) {
         a.f0[g] = f0;
@@ -223,26 +284,40 @@ extern "C" int satt_yin_max_lag(void) { return YIN_MAX_TAU; }
 
 extern "C" int satt_yin_run_length(void) { return YIN_RUN; }
 
-extern "C" int satt_yin(const satt_yin_params* p, void* stream) {
-  if (!p || !p->signal || !p->in_offsets || !p->frame_offsets || !p->f0 || !p->aperiodicity || !p->power) return SATT_E_BADARG;
-  if (p->n_utts < 1 || p->total_in < 1 || p->total_frames < 1) return SATT_E_BADARG;
-  if (!yin_supported(p->window, p->tau_max, p->hop)) return SATT_E_UNSUPPORTED;
-  if (p->tau_min < 2 || p->tau_min >= p->tau_max) return SATT_E_BADARG;          // [tau_min, tau_max - 1] holds a lag, tau* - 1 >= 1
-  if (!(p->sample_rate > 0.f) || !(p->threshold == p->threshold)) return SATT_E_BADARG;
-  const long long blocks = ((long long)p->total_frames + YIN_RUN - 1) / YIN_RUN;
+// the checks that both entry points share, then the launch: the sizes of the grid and of LDS are the same for both picks
+template <bool CAND>
+int yin_launch(YinArgs a, void* stream) {
+  if (a.n_utts < 1 || a.total_in < 1 || a.total_frames < 1) return SATT_E_BADARG;
+  if (!yin_supported(a.W, a.tau_max, a.hop)) return SATT_E_UNSUPPORTED;
+  if (a.tau_min < 2 || a.tau_min >= a.tau_max) return SATT_E_BADARG;                // [tau_min, tau_max - 1] holds a lag, tau* - 1 >= 1
+  if (!(a.sr > 0.f) || !(a.thr == a.thr)) return SATT_E_BADARG;
+  const long long blocks = (a.total_frames + YIN_RUN - 1) / YIN_RUN;
   if (blocks > 0x7fffffffLL) return SATT_E_UNSUPPORTED;
-  const int nch = (p->tau_max + YIN_CHUNK) / YIN_CHUNK;                           // covers tau = 0 .. tau_max
-  const int lags = nch * YIN_CHUNK;
-  const int span = ((p->window + 3) & ~3) + lags + 4;                             // the last 16-byte read ends at W4 + lags + 3
-  const size_t lds = (size_t)YIN_WAVES * (span + lags) * sizeof(float);           // <= 4 (1536 + 1028 + 1024) 4 = 57 408 bytes
-  YinArgs a{p->window, p->tau_min, p->tau_max, p->hop, p->n_utts, span, lags, p->sample_rate, p->threshold,
-            (long long)p->total_in, (long long)p->total_frames, p->signal, p->in_offsets, p->frame_offsets,
-            p->f0, p->aperiodicity, p->power};
+  const int nch = (a.tau_max + YIN_CHUNK) / YIN_CHUNK;                              // covers tau = 0 .. tau_max
+  a.lags = nch * YIN_CHUNK;
+  a.span = ((a.W + 3) & ~3) + a.lags + 4;                                           // the last 16-byte read ends at W4 + lags + 3
+  const size_t lds = (size_t)YIN_WAVES * (a.span + a.lags) * sizeof(float);         // <= 4 (1536 + 1028 + 1024) 4 = 57 408 bytes
   const dim3 grid((unsigned)blocks), block(YIN_NT);
   hipStream_t st = (hipStream_t)stream;
-  if (nch == 1) hipLaunchKernelGGL(yin_k<1>, grid, block, lds, st, a);
-  else if (nch == 2) hipLaunchKernelGGL(yin_k<2>, grid, block, lds, st, a);
-  else if (nch == 3) hipLaunchKernelGGL(yin_k<3>, grid, block, lds, st, a);
-  else hipLaunchKernelGGL(yin_k<4>, grid, block, lds, st, a);
+  if (nch == 1) hipLaunchKernelGGL((yin_k<1, CAND>), grid, block, lds, st, a);
+  else if (nch == 2) hipLaunchKernelGGL((yin_k<2, CAND>), grid, block, lds, st, a);
+  else if (nch == 3) hipLaunchKernelGGL((yin_k<3, CAND>), grid, block, lds, st, a);
+  else hipLaunchKernelGGL((yin_k<4, CAND>), grid, block, lds, st, a);
   SATT_LAUNCH_CHECK(); return SATT_OK;
+}
+
+extern "C" int satt_yin(const satt_yin_params* p, void* stream) {
+  if (!p || !p->signal || !p->in_offsets || !p->frame_offsets || !p->f0 || !p->aperiodicity || !p->power) return SATT_E_BADARG;
+  YinArgs a{p->window, p->tau_min, p->tau_max, p->hop, p->n_utts, 0, 0, p->sample_rate, p->threshold,
+            (long long)p->total_in, (long long)p->total_frames, p->signal, p->in_offsets, p->frame_offsets,
+            p->f0, p->aperiodicity, p->power, nullptr, nullptr};
+  return yin_launch<false>(a, stream);
+}
+
+extern "C" int satt_yin_candidates(const satt_yin_candidates_params* p, void* stream) {
+  if (!p || !p->signal || !p->in_offsets || !p->frame_offsets || !p->cand_period || !p->cand_value || !p->power) return SATT_E_BADARG;
+  YinArgs a{p->window, p->tau_min, p->tau_max, p->hop, p->n_utts, 0, 0, 1.f, 0.f,   // (neither a sample rate nor a threshold here)
+            (long long)p->total_in, (long long)p->total_frames, p->signal, p->in_offsets, p->frame_offsets,
+            nullptr, nullptr, p->power, p->cand_period, p->cand_value};
+  return yin_launch<true>(a, stream);
 }

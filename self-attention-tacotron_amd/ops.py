@@ -558,6 +558,55 @@ def yin(signal, in_offsets, frame_offsets, window, tau_min, tau_max, hop, sample
     _lib.check(_lib.lib().satt_yin(C.byref(p), _s()), "yin")
 
 
+def yin_candidates(signal, in_offsets, frame_offsets, window, tau_min, tau_max, hop, cand_period, cand_value, power):
+    """the period candidates of every frame of a batch of utterances in one launch (csrc/yin.hip).  Signal and offsets as for `yin`;
+    cand_period and cand_value: fp32 [total frames, 8], power: fp32 [total frames].  Parameters outside satt_yin_supported raise."""
+    assert signal.dtype == torch.float32 and signal.dim() == 1 and signal.is_contiguous()
+    assert in_offsets.dtype == torch.int64 and frame_offsets.dtype == torch.int64 and in_offsets.numel() == frame_offsets.numel() >= 2
+    assert power.dtype == torch.float32 and power.dim() == 1 and power.is_contiguous()
+    for o in (cand_period, cand_value):
+        assert o.dtype == torch.float32 and o.is_contiguous() and tuple(o.shape) == (power.numel(), 8)
+    if not yin_supported(window, tau_max, hop):
+        raise ValueError("yin_candidates does not take window=%d tau_max=%d hop=%d (1 <= window <= %d, 3 <= tau_max <= %d, 1 <= hop <= 2^20)"
+                         % ((window, tau_max, hop) + yin_limits()[:2]))
+    p = _lib.YinCandidatesParams(window=window, tau_min=tau_min, tau_max=tau_max, hop=hop, n_utts=in_offsets.numel() - 1,
+                                 total_in=signal.numel(), total_frames=power.numel(), signal=_p(signal), in_offsets=_p(in_offsets),
+                                 frame_offsets=_p(frame_offsets), cand_period=_p(cand_period), cand_value=_p(cand_value), power=_p(power))
+    _lib.check(_lib.lib().satt_yin_candidates(C.byref(p), _s()), "yin_candidates")
+
+
+def f0_viterbi_supported(max_frames):
+    """True when satt_f0_viterbi takes utterances of up to this many frames (host-only: needs the library, not a GPU)"""
+    return bool(_lib.lib().satt_f0_viterbi_supported(int(max_frames)))
+
+
+def f0_viterbi_max_frames():
+    """the longest utterance csrc/f0_viterbi.hip takes: a predecessor byte per frame and state in 18 KiB of LDS"""
+    return int(_lib.lib().satt_f0_viterbi_max_frames())
+
+
+def f0_viterbi(cand_period, cand_value, gate, frame_offsets, max_frames, tau_max, sample_rate, jump_cost, switch_cost, unvoiced_cost,
+               lag_bias, f0, state, cost):
+    """the cheapest path through the candidates of a batch of utterances in one launch (csrc/f0_viterbi.hip).  cand_period,
+    cand_value: fp32 [total frames, 8]; gate: uint8 [total frames]; utterance u owns frames frame_offsets[u] .. frame_offsets[u + 1]
+    (int64 [U + 1]) of f0 (fp32) and state (uint8) and entry u of cost (fp32 [U]).  max_frames: the longest utterance of the batch;
+    one outside satt_f0_viterbi_supported raises."""
+    n = frame_offsets.numel() - 1
+    assert frame_offsets.dtype == torch.int64 and n >= 1
+    assert gate.dtype == torch.uint8 and state.dtype == torch.uint8 and f0.dtype == torch.float32 and cost.dtype == torch.float32
+    assert gate.dim() == state.dim() == f0.dim() == cost.dim() == 1 and gate.numel() == state.numel() == f0.numel() and cost.numel() == n
+    for o in (cand_period, cand_value):
+        assert o.dtype == torch.float32 and o.is_contiguous() and tuple(o.shape) == (f0.numel(), 8)
+    assert all(o.is_contiguous() for o in (gate, state, f0, cost, frame_offsets))
+    if not f0_viterbi_supported(max_frames):
+        raise ValueError("f0_viterbi does not take an utterance of %d frames (1 <= frames <= %d)" % (max_frames, f0_viterbi_max_frames()))
+    p = _lib.F0ViterbiParams(n_utts=n, max_frames=max_frames, tau_max=tau_max, sample_rate=float(sample_rate), jump_cost=float(jump_cost),
+                             switch_cost=float(switch_cost), unvoiced_cost=float(unvoiced_cost), lag_bias=float(lag_bias),
+                             total_frames=f0.numel(), cand_period=_p(cand_period), cand_value=_p(cand_value), gate=_p(gate),
+                             frame_offsets=_p(frame_offsets), f0=_p(f0), state=_p(state), cost=_p(cost))
+    _lib.check(_lib.lib().satt_f0_viterbi(C.byref(p), _s()), "f0_viterbi")
+
+
 def griffin_lim_supported(n_fft, win, hop):
     """True when satt_griffin_lim takes these STFT parameters (host-only: needs the library, not a GPU)"""
     return bool(_lib.lib().satt_griffin_lim_supported(int(n_fft), int(win), int(hop)))

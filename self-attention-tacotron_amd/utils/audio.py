@@ -627,12 +627,27 @@ class Audio:
             out.append(o)
         return out
 
-    def f0_batch(self, ys, fmin=None, fmax=None, window_ms=None, threshold=None, silence_db=None):
+    def f0_batch(self, ys, fmin=None, fmax=None, window_ms=None, threshold=None, silence_db=None, tracker="yin", jump_cost=None,
+                 switch_cost=None, unvoiced_cost=None, lag_bias=None):
         """YIN pitch tracks of signals at hparams.sample_rate on the mel frame grid (utils/pitch.py): a list of dicts
         f0 (float32, Hz; 0 where no lag passes the threshold), voiced (bool), aperiodicity and power (float32), each [1 + n // hop].
         On "hip" the batch is one launch of csrc/yin.hip (cut at MAX_LAUNCH_SAMPLES), on "numpy" its float32 restatement: the same
-        bits.  The defaults are pitch.FMIN / FMAX / WINDOW_MS / THRESHOLD / SILENCE_DB; they are arguments, not hparams."""
+        bits.  The defaults are pitch.FMIN / FMAX / WINDOW_MS / THRESHOLD / SILENCE_DB; they are arguments, not hparams.
+        tracker="viterbi" (pitch.track_f0) chooses among the 8 deepest dips of every frame along the utterance instead (the costs
+        default to pitch.JUMP_COST / SWITCH_COST / LAG_BIAS and the threshold) and adds `state` (uint8; 8 is unvoiced) to the dicts;
+        utterances of more than pitch.F0_VITERBI_MAX_FRAMES frames are refused."""
         from . import pitch
+        if tracker != "yin":
+            kw = dict(fmin=pitch.FMIN if fmin is None else fmin, fmax=pitch.FMAX if fmax is None else fmax,
+                      window_ms=pitch.WINDOW_MS if window_ms is None else window_ms,
+                      threshold=pitch.THRESHOLD if threshold is None else threshold,
+                      silence_db=pitch.SILENCE_DB if silence_db is None else silence_db,
+                      jump_cost=pitch.JUMP_COST if jump_cost is None else jump_cost,
+                      switch_cost=pitch.SWITCH_COST if switch_cost is None else switch_cost,
+                      unvoiced_cost=unvoiced_cost, lag_bias=pitch.LAG_BIAS if lag_bias is None else lag_bias)
+            res = pitch.track_f0(ys, self.hparams.sample_rate, self.tables.hop, tracker=tracker, backend=self.backend, device=self.device,
+                                 with_state=True, **kw)
+            return [dict(f0=f0, voiced=v, aperiodicity=ap, power=power, state=state) for f0, ap, power, v, state in res]
         kw = dict(fmin=pitch.FMIN if fmin is None else fmin, fmax=pitch.FMAX if fmax is None else fmax,
                   window_ms=pitch.WINDOW_MS if window_ms is None else window_ms,
                   threshold=pitch.THRESHOLD if threshold is None else threshold)

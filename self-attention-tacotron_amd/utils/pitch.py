@@ -3,8 +3,13 @@ path (DESIGN.md 3.6 holds the definition).  The tracker runs in csrc/yin.hip (ba
 in `yin_numpy`, a float32 restatement with the kernel's operations in the kernel's order: both agree bit for bit on f0, aperiodicity
 and power.  The voicing decision and the metrics are host code, the same for both.
 
-This is plain YIN: no octave-error smoothing, no pYIN / Viterbi, not WORLD.  Its values compare between runs of this tool only.
-fmin, fmax, window_ms, threshold and silence_db are arguments, not hparams."""
+`track_f0` is the front of two trackers.  "yin" is plain YIN: every frame is decided alone, by the first dip of d' below the
+threshold, which reports the octave above wherever the fundamental is weak.  "viterbi" keeps the K = 8 deepest dips of d' of every
+frame as period candidates (csrc/yin.hip satt_yin_candidates / `yin_candidates_numpy`) and chooses among them and an "unvoiced"
+state along the utterance by dynamic programming (csrc/f0_viterbi.hip / `f0_viterbi_numpy`): octave jumps between neighbouring
+frames cost jump_cost.  Both stages are float32 without transcendental functions, and the two backends agree bit for bit on them as
+well.  This is neither pYIN (no probabilities, no threshold prior) nor WORLD: values compare between runs of this tool only.
+fmin, fmax, window_ms, threshold, silence_db and the four costs are arguments, not hparams."""
 import math
 
 import numpy as np
@@ -14,6 +19,10 @@ YIN_MAX_WINDOW = 1536                 # satt_yin_max_window(): with the span and
 YIN_MAX_LAG = 1023                    # satt_yin_max_lag(): four chunks of 256 lags, four lags a lane
 YIN_MAX_HOP = 1 << 20
 YIN_RUN = 16                          # satt_yin_run_length(): frames per workgroup, counted through the batch
+F0_CANDIDATES = 8                     # SATT_F0_CANDIDATES: candidate slots of a frame; state 8 of the Viterbi tracker is "unvoiced"
+F0_VITERBI_MAX_FRAMES = 2048          # satt_f0_viterbi_max_frames(): a predecessor byte per frame and state in 18 KiB of LDS
+JUMP_COST, SWITCH_COST, LAG_BIAS = 0.3, 0.1, 0.1     # unvoiced_cost defaults to the threshold (profiles/f0_viterbi_defaults.txt)
+TRACKERS = ("yin", "viterbi")
 
 
 def yin_supported(window, tau_max, hop):
@@ -144,14 +153,231 @@ def yin_hip(signals, sr, hop, fmin=FMIN, fmax=FMAX, window_ms=WINDOW_MS, thresho
     return out
 
 
-def voicing(f0, power, silence_db=SILENCE_DB):
-    """bool [T]: f0 > 0 and power > max_t(power) 10^(-silence_db / 10), in float64.  A signal whose largest power is 0 (or NaN) is
-    all unvoiced; a NaN f0 is unvoiced."""
-    f0, power = np.asarray(f0, np.float64), np.asarray(power, np.float64)
+def silence_gate(power, silence_db=SILENCE_DB):
+    """bool [T]: power > max_t(power) 10^(-silence_db / 10), in float64: the frames that may be voiced.  A signal whose largest
+    power is 0 (or NaN) has none."""
+    power = np.asarray(power, np.float64)
     if len(power) == 0:
         return np.zeros(0, bool)
     with np.errstate(invalid="ignore"):
-        return (f0 > 0) & (power > power.max() * 10.0 ** (-silence_db / 10.0))
+        return power > power.max() * 10.0 ** (-silence_db / 10.0)
+
+
+def voicing(f0, power, silence_db=SILENCE_DB):
+    """bool [T]: f0 > 0 and silence_gate(power).  A signal whose largest power is 0 (or NaN) is all unvoiced; a NaN f0 is
+    unvoiced."""
+    f0 = np.asarray(f0, np.float64)
+    if len(f0) == 0:
+        return np.zeros(0, bool)
+    with np.errstate(invalid="ignore"):
+        return (f0 > 0) & silence_gate(power, silence_db)
+
+
+# ---- the Viterbi tracker: candidates, path, front ----------------------------------------------------------------------------------------
+def yin_candidates_pick_numpy(dp, tau_min, tau_max):
+    """(cand_period, cand_value) float32 [T, 8] from d' [T, tau_max + 1]: the dips of [tau_min, tau_max - 1], the 8 with the smallest
+    d' (ties to the smaller lag) in ascending lag order, each with the parabola and clamp of the YIN pick; unused slots 0 and +inf"""
+    T, K = len(dp), F0_CANDIDATES
+    per, val = np.zeros((T, K), np.float32), np.full((T, K), np.inf, np.float32)
+    with np.errstate(all="ignore"):
+        mid = dp[:, tau_min:tau_max]
+        dips = (mid < dp[:, tau_min - 1:tau_max - 1]) & (mid <= dp[:, tau_min + 1:tau_max + 1])
+        for t in np.nonzero(dips.any(axis=1))[0]:
+            row = dp[t]
+            k = tau_min + np.nonzero(dips[t])[0]
+            k = np.sort(k[np.lexsort((k, row[k]))[:K]])                # by (d', lag), the first 8, then by lag
+            a, b, c = row[k - 1], row[k], row[k + 1]
+            num, den = a - c, (a - b) + (c - b)
+            shift = (np.float32(0.5) * num) / den
+            shift = np.where(shift > 1, np.float32(1.0), shift)
+            shift = np.where(shift < -1, np.float32(-1.0), shift)
+            shift = np.where(den > 0, shift, np.float32(0.0)).astype(np.float32)
+            per[t, :len(k)] = k.astype(np.float32) + shift
+            val[t, :len(k)] = b
+    return per, val
+
+
+def yin_candidates_numpy(y, sr, hop, fmin=FMIN, fmax=FMAX, window_ms=WINDOW_MS):
+    """(cand_period [T, 8], cand_value [T, 8], power [T]), float32, T = 1 + n // hop, of one signal: the bits of csrc/yin.hip
+    satt_yin_candidates"""
+    _, tau_min, tau_max = yin_check(sr, hop, fmin, fmax, window_ms)
+    dp, power = yin_dprime_numpy(y, sr, hop, fmin, fmax, window_ms)
+    per, val = yin_candidates_pick_numpy(dp, tau_min, tau_max)
+    return per, val, power
+
+
+def f0_viterbi_check(frames, jump_cost, switch_cost, unvoiced_cost, lag_bias):
+    """ValueError when neither backend takes an utterance of `frames` frames or these costs"""
+    if not 1 <= frames <= F0_VITERBI_MAX_FRAMES:
+        raise ValueError("f0_viterbi: an utterance of %d frames; supported are 1 <= frames <= %d" % (frames, F0_VITERBI_MAX_FRAMES))
+    for name, c in (("jump_cost", jump_cost), ("switch_cost", switch_cost), ("unvoiced_cost", unvoiced_cost), ("lag_bias", lag_bias)):
+        if not (0.0 <= np.float32(c) < np.inf):
+            raise ValueError("f0_viterbi: %s=%r must be finite and >= 0" % (name, c))
+
+
+def _table(cand_period, cand_value, gate):
+    per, val = np.ascontiguousarray(cand_period, np.float32), np.ascontiguousarray(cand_value, np.float32)
+    gate = np.ascontiguousarray(np.asarray(gate) != 0, np.uint8)
+    if per.ndim != 2 or per.shape[1] != F0_CANDIDATES or val.shape != per.shape or gate.shape != per.shape[:1]:
+        raise ValueError("f0_viterbi: need cand_period and cand_value [T, %d] and gate [T], got shapes %r, %r and %r"
+                         % (F0_CANDIDATES, per.shape, val.shape, gate.shape))
+    return per, val, gate
+
+
+def f0_viterbi_numpy(cand_period, cand_value, gate, sr, tau_max, jump_cost=JUMP_COST, switch_cost=SWITCH_COST, unvoiced_cost=THRESHOLD,
+                     lag_bias=LAG_BIAS):
+    """(f0 float32 [T], state uint8 [T], cost float32) of one utterance's candidate tables: the bits of csrc/f0_viterbi.hip.  The
+    costs of all steps at once, then the chain one frame at a time."""
+    per, val, gate = _table(cand_period, cand_value, gate)
+    T, K, F = len(per), F0_CANDIDATES, np.float32
+    f0_viterbi_check(T, jump_cost, switch_cost, unvoiced_cost, lag_bias)
+    inf = F(np.inf)
+    with np.errstate(all="ignore"):
+        obs = np.full((T, K + 1), F(unvoiced_cost), np.float32)
+        used = (gate[:, None] != 0) & (per > 0)
+        obs[:, :K] = np.where(used, val + F(lag_bias) * (per / F(tau_max)), inf)
+        trans = np.full((max(T - 1, 0), K + 1, K + 1), F(switch_cost), np.float32)     # [t - 1, q, j]: from q of t - 1 to j of t
+        trans[:, K, K] = 0
+        pq, pj = per[:-1, :, None], per[1:, None, :]
+        up = pq > pj
+        trans[:, :K, :K] = F(jump_cost) * (np.where(up, pq, pj) / np.where(up, pj, pq) - F(1.0))
+        pred = np.full((T, K + 1), K, np.uint8)
+        delta, cols = obs[0].copy(), np.arange(K + 1)
+        for t in range(1, T):
+            v = delta[:, None] + trans[t - 1]
+            v[np.isnan(v)] = inf                                        # a strict < from +inf passes NaN and +inf over
+            arg = np.argmin(v, axis=0)                                  # the first minimum: the smaller q
+            best = v[arg, cols]
+            pred[t] = np.where(best < inf, arg, K)
+            delta = best + obs[t]
+        v = np.where(np.isnan(delta), inf, delta)
+        end = int(np.argmin(v)) if v.min() < inf else K
+        state = np.empty(T, np.uint8)
+        s = end
+        for t in range(T - 1, -1, -1):
+            state[t] = s
+            s = int(pred[t, s])
+        cand = state < K
+        f0 = np.zeros(T, np.float32)
+        f0[cand] = F(sr) / per[cand, state[cand]]
+        return f0, state, F(v[end])
+
+
+def _groups(items, sizes, budget):
+    """`items` cut into consecutive groups whose sizes add up to at most `budget` (one item always goes out)"""
+    group, count = [], 0
+    for it, n in zip(items, sizes):
+        if group and count + n > budget:
+            yield group
+            group, count = [], 0
+        group.append(it)
+        count += n
+    if group:
+        yield group
+
+
+def _budget(max_launch_samples):
+    from .audio import MAX_LAUNCH_SAMPLES
+    return MAX_LAUNCH_SAMPLES if max_launch_samples is None else int(max_launch_samples)
+
+
+def _candidates_launch(signals, hop, W, tau_min, tau_max, device):
+    import torch
+    from .. import ops
+    lens = np.asarray([len(s) for s in signals], np.int64)
+    io = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    fo = np.concatenate([[0], np.cumsum(1 + lens // hop)]).astype(np.int64)
+    x = torch.from_numpy(np.concatenate(signals)).to(device)
+    total = int(fo[-1])
+    per, val = (torch.empty((total, F0_CANDIDATES), dtype=torch.float32, device=device) for _ in range(2))
+    power = torch.empty(total, dtype=torch.float32, device=device)
+    ops.yin_candidates(x, torch.from_numpy(io).to(device), torch.from_numpy(fo).to(device), W, tau_min, tau_max, hop, per, val, power)
+    per, val, power = (o.cpu().numpy() for o in (per, val, power))
+    return [(per[fo[u]:fo[u + 1]], val[fo[u]:fo[u + 1]], power[fo[u]:fo[u + 1]]) for u in range(len(signals))]
+
+
+def yin_candidates_hip(signals, sr, hop, fmin=FMIN, fmax=FMAX, window_ms=WINDOW_MS, device="cuda", max_launch_samples=None):
+    """csrc/yin.hip satt_yin_candidates over `signals`: the list of (cand_period, cand_value, power), in input order.  One launch for
+    the batch, cut only where it would exceed `max_launch_samples` (default audio.MAX_LAUNCH_SAMPLES; one signal always goes out)."""
+    W, tau_min, tau_max = yin_check(sr, hop, fmin, fmax, window_ms)
+    signals = [_signal(s) for s in signals]
+    out = []
+    for group in _groups(signals, [len(s) for s in signals], _budget(max_launch_samples)):
+        out += _candidates_launch(group, hop, W, tau_min, tau_max, device)
+    return out
+
+
+def _viterbi_launch(tables, sr, tau_max, costs, device):
+    import torch
+    from .. import ops
+    lens = np.asarray([len(t[0]) for t in tables], np.int64)
+    fo = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    per, val, gate = (torch.from_numpy(np.concatenate([t[i] for t in tables])).to(device) for i in range(3))
+    f0 = torch.empty(int(fo[-1]), dtype=torch.float32, device=device)
+    state = torch.empty(int(fo[-1]), dtype=torch.uint8, device=device)
+    cost = torch.empty(len(tables), dtype=torch.float32, device=device)
+    ops.f0_viterbi(per, val, gate, torch.from_numpy(fo).to(device), int(lens.max()), tau_max, sr, *costs, f0, state, cost)
+    f0, state, cost = (o.cpu().numpy() for o in (f0, state, cost))
+    return [(f0[fo[u]:fo[u + 1]], state[fo[u]:fo[u + 1]], cost[u]) for u in range(len(tables))]
+
+
+def f0_viterbi_hip(tables, sr, tau_max, jump_cost=JUMP_COST, switch_cost=SWITCH_COST, unvoiced_cost=THRESHOLD, lag_bias=LAG_BIAS,
+                   device="cuda", max_launch_samples=None):
+    """csrc/f0_viterbi.hip over `tables`, a list of (cand_period [T, 8], cand_value [T, 8], gate [T]): the list of (f0, state, cost),
+    in input order.  One launch for the batch, cut only where its frames would exceed `max_launch_samples` (default
+    audio.MAX_LAUNCH_SAMPLES; one utterance always goes out)."""
+    tables = [_table(*t) for t in tables]
+    for t in tables:
+        f0_viterbi_check(len(t[0]), jump_cost, switch_cost, unvoiced_cost, lag_bias)
+    out = []
+    for group in _groups(tables, [len(t[0]) for t in tables], _budget(max_launch_samples)):
+        out += _viterbi_launch(group, sr, tau_max, (jump_cost, switch_cost, unvoiced_cost, lag_bias), device)
+    return out
+
+
+def track_f0(signals, sr, hop, fmin=FMIN, fmax=FMAX, window_ms=WINDOW_MS, threshold=THRESHOLD, silence_db=SILENCE_DB, tracker="yin",
+             jump_cost=JUMP_COST, switch_cost=SWITCH_COST, unvoiced_cost=None, lag_bias=LAG_BIAS, backend="numpy", device="cuda",
+             max_launch_samples=None, with_state=False):
+    """the list of (f0, aperiodicity, power, voiced) of `signals` (with_state: and the state track, uint8, under "viterbi").
+    tracker "yin": the YIN pick and voicing().  tracker "viterbi": the candidates of every frame, gate = silence_gate(power), the
+    cheapest path; voiced is state != 8 and aperiodicity the chosen slot's value, in state 8 the frame's smallest candidate value
+    (+inf without a candidate).  unvoiced_cost defaults to the threshold, which plain YIN alone uses otherwise.  backend "hip"
+    runs the kernels, "numpy" their float32 restatements: the same bits."""
+    if tracker not in TRACKERS:
+        raise ValueError("track_f0: tracker=%r is none of %r" % (tracker, TRACKERS))
+    if backend not in ("hip", "numpy"):
+        raise ValueError("track_f0: backend=%r is neither 'hip' nor 'numpy'" % (backend,))
+    _, _, tau_max = yin_check(sr, hop, fmin, fmax, window_ms)
+    signals = [_signal(s) for s in signals]
+    if not signals:
+        return []
+    par = dict(fmin=fmin, fmax=fmax, window_ms=window_ms)
+    if tracker == "yin":
+        if backend == "numpy":
+            res = [yin_numpy(y, sr, hop, threshold=threshold, **par) for y in signals]
+        else:
+            res = yin_hip(signals, sr, hop, threshold=threshold, device=device, max_launch_samples=max_launch_samples, **par)
+        return [(f0, ap, power, voicing(f0, power, silence_db)) for f0, ap, power in res]
+    costs = dict(jump_cost=jump_cost, switch_cost=switch_cost, unvoiced_cost=threshold if unvoiced_cost is None else unvoiced_cost,
+                 lag_bias=lag_bias)
+    for y in signals:
+        f0_viterbi_check(1 + len(y) // hop, **costs)
+    if backend == "numpy":
+        cands = [yin_candidates_numpy(y, sr, hop, **par) for y in signals]
+    else:
+        cands = yin_candidates_hip(signals, sr, hop, device=device, max_launch_samples=max_launch_samples, **par)
+    tables = [(per, val, silence_gate(power, silence_db)) for per, val, power in cands]
+    if backend == "numpy":
+        paths = [f0_viterbi_numpy(*t, sr, tau_max, **costs) for t in tables]
+    else:
+        paths = f0_viterbi_hip(tables, sr, tau_max, device=device, max_launch_samples=max_launch_samples, **costs)
+    out = []
+    for (per, val, power), (f0, state, _) in zip(cands, paths):
+        voiced = state != F0_CANDIDATES
+        ap = val.min(axis=1)                                            # unused slots hold +inf
+        ap[voiced] = val[voiced, state[voiced]]
+        out.append((f0, ap, power, voiced) + ((state,) if with_state else ()))
+    return out
 
 
 def f0_metrics(f0_pred, v_pred, f0_ref, v_ref, path):
