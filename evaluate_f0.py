@@ -5,12 +5,15 @@ compared along the dynamic-time-warping path of their mel spectrograms.
 Usage: evaluate_f0.py --hparam-json-file=<hparams.json> [--hparams=<a=b>] [--backend=hip|numpy] [--fmin=<Hz>] [--fmax=<Hz>]
                       [--window-ms=<ms>] [--threshold=<x>] [--silence-db=<dB>] [--iters=<N>] [--seed=<S>]
                       [--tracker=yin|viterbi] [--jump-cost=<x>] [--switch-cost=<x>] [--unvoiced-cost=<x>] [--lag-bias=<x>]
+                      [--inversion=pinv|nnls] [--nnls-iters=<N>]
                       [--pred-wav-dir=<D> --ref-wav-dir=<D>] [--write-tracks] <prediction_dir> [<out_dir>]
 
 Default mode: every `<key>.tfrecord` of <prediction_dir> (predict_mel.py's prediction record) holds the predicted `mel` and, when the
 run had a --target-data-root, the `ground_truth_mel`; records without one are listed and skipped.  The predicted AND the ground-truth
 mel both go through Audio.inv_melspectrogram_batch (Griffin-Lim) with the same --iters (default 60) and --seed (default 0), so the
-phase reconstruction biases both sides alike; F0 is tracked on both signals and the path comes from Audio.mel_distance_batch on the
+phase reconstruction biases both sides alike; --inversion nnls (default pinv) gives both sides the non-negative mel inversion of
+--nnls-iters (64) iterations in front of it (csrc/mel_nnls.hip; summary.json then holds inversion and nnls_iters, a summary without
+`inversion` is a pinv run); F0 is tracked on both signals and the path comes from Audio.mel_distance_batch on the
 record's mels.  The hparams.json must be the one the preprocessing run wrote (the corpus statistics de-normalise the mels).
 Wav mode (--pred-wav-dir and --ref-wav-dir, both): the `<key>.wav` files of the two directories are matched by basename, unmatched
 keys are listed and skipped; the wavs are read with Audio.load_wav, their mels come from melspectrogram_batch + normalize_mel, and
@@ -63,6 +66,9 @@ def main(argv=None):
     ap.add_argument("--switch-cost", type=float, default=None, help="viterbi: the cost of entering or leaving the unvoiced state")
     ap.add_argument("--unvoiced-cost", type=float, default=None, help="viterbi: the cost of an unvoiced frame (default: --threshold)")
     ap.add_argument("--lag-bias", type=float, default=None, help="viterbi: added to a candidate's d', times period / longest lag")
+    ap.add_argument("--inversion", choices=("pinv", "nnls"), default="pinv",
+                    help="mel -> linear magnitudes of both sides (default mode): the floored pseudo-inverse or the non-negative solve")
+    ap.add_argument("--nnls-iters", type=int, default=64, metavar="N", help="iterations of --inversion nnls (default 64)")
     ap.add_argument("--pred-wav-dir", default=None, metavar="D")
     ap.add_argument("--ref-wav-dir", default=None, metavar="D")
     ap.add_argument("--write-tracks", action="store_true", help="write <key>.f0.npz with both tracks and the path")
@@ -71,6 +77,10 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if (a.pred_wav_dir is None) != (a.ref_wav_dir is None):
         raise SystemExit("--pred-wav-dir and --ref-wav-dir go together")
+    if not 0 <= a.nnls_iters <= 1024:
+        raise SystemExit("--nnls-iters: 0 .. 1024")
+    if a.inversion == "nnls" and a.pred_wav_dir is not None:
+        raise SystemExit("--inversion belongs to the default mode: wav mode inverts no mel")
 
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import satt_amd  # noqa: F401
@@ -135,7 +145,7 @@ def main(argv=None):
             if not np.isfinite(S).all():
                 raise ValueError("%s: a mel holds non-finite values" % key)
         wavs = audio.inv_melspectrogram_batch([audio.denormalize_mel(np.asarray(S, np.float64)) for S in preds + refs],
-                                              iters=a.iters, seed=a.seed)
+                                              iters=a.iters, seed=a.seed, inversion=a.inversion, nnls_iters=a.nnls_iters)
         sig_pred, sig_ref = wavs[:len(keys)], wavs[len(keys):]
     dist = audio.mel_distance_batch(preds, refs, want_paths=True, keys=keys)
     tracks = audio.f0_batch(sig_pred + sig_ref, **par, **costs)
@@ -167,10 +177,11 @@ def main(argv=None):
     def weighted(k):
         nb = sum(m["voiced_both"] for m in rows)
         return math.sqrt(sum(m["voiced_both"] * m[k] ** 2 for m in rows if m[k] is not None) / nb) if nb else None
+    inv = dict(inversion=a.inversion, nnls_iters=a.nnls_iters) if a.inversion != "pinv" else {}
     summary = dict(count=len(rows), mode=mode, steps=sum(m["steps"] for m in rows), voiced_both=sum(m["voiced_both"] for m in rows),
                    mean={k: mean(k) for k in METRICS}, weighted_f0_rmse_cents=weighted("f0_rmse_cents"),
                    weighted_f0_rmse_hz=weighted("f0_rmse_hz"), sample_rate=hparams.sample_rate, hop=audio.tables.hop, **par, **costs,
-                   iters=a.iters if mode == "griffin_lim" else None, seed=a.seed if mode == "griffin_lim" else None, skipped=skipped)
+                   iters=a.iters if mode == "griffin_lim" else None, seed=a.seed if mode == "griffin_lim" else None, **inv, skipped=skipped)
     with open(os.path.join(out_dir, "summary.json"), "w") as f:
         json.dump(summary, f, indent=1)
     print("%d pairs, %d steps, %d voiced on both sides: mean V/UV error %.4f, voiced-step-weighted F0 RMSE %s cents"

@@ -1167,6 +1167,44 @@ int satt_f0_viterbi_supported(int max_frames);
 int satt_f0_viterbi_max_frames(void);
 int satt_f0_viterbi(const satt_f0_viterbi_params* p, void* stream);
 
+/* ---- non-negative inversion of the mel basis for a batch of frames in one launch (csrc/mel_nnls.hip).  Frame n
+ * has band amplitudes amp[n M ..] and the start x_0 = start[n F ..] (F = num_bins, M = num_mels) and receives out[n F ..].  W is
+ * the banded mel basis of satt_melspec (band_start [M], band_offset [M + 1], band_weight [n_weights]); W^T comes from its
+ * transposed table: bin f lies under the bands bin_first[f] .. + c - 1, c = bin_offset[f + 1] - bin_offset[f], with the weights
+ * bin_weight[bin_offset[f] ..] (bin_first [F], bin_offset [F + 1], bin_weight [n_tweights]; no assumption on c).  All fp32, every
+ * product, difference and sum rounded on its own (no fused multiply-add):
+ *   y_1 = x_0;  for k = 1 .. iters:
+ *     p[m] = sum over the band's bins of w y_k: lane j = 0 .. 15 sums the terms j, j + 16, .. ascending in one chain from +0, the
+ *            16 partial sums are joined by the adjacent pairwise tree ((s0 + s1) + (s2 + s3)) + ..
+ *     r[m] = p[m] - amp[m];   g[f] = sum over the bin's bands of w^T r, one chain from +0, bands ascending (no band: g = 0)
+ *     v = y_k - step * g;   x_k = v > 0 ? v : 0 (a NaN becomes 0);   y_k+1 = x_k + beta[k - 1] * (x_k - x_k-1)
+ *   out = x_iters
+ * step (1 / the largest eigenvalue of W W^T, rounded towards 0) and beta [iters] (FISTA's (t_k - 1) / t_k+1) come from the host
+ * (utils/audio.py MelNnlsTables).  satt_mel_nnls_supported (no GPU needed) == 1: 1 <= num_bins <= 2049, 1 <= num_mels <= 128,
+ * 1 <= iters <= 1024; anything else, and n_frames outside 1 .. 2^31 - 1, returns SATT_E_UNSUPPORTED.  Null pointers, n_weights or
+ * n_tweights < 1 or a step that is not finite and > 0 return SATT_E_BADARG; both before anything is launched.  A band or a bin
+ * whose table entry does not lie inside num_bins / n_weights / num_mels / n_tweights is taken as empty: nothing is read or written
+ * out of bounds whatever the tables hold.  Weight tables that do not fit 64 KiB of LDS beside the frame are read from global memory
+ * (the same bits).  One workgroup per frame, no atomics: two launches are bit-identical and a frame's result does not depend on its
+ * batch; utils/audio.py mel_nnls_numpy gives the same bits. */
+typedef struct {
+  int num_bins, num_mels, iters, n_weights, n_tweights;
+  float step;
+  int64_t n_frames;
+  const float* amp;            /* [n_frames, num_mels] */
+  const float* start;          /* [n_frames, num_bins] */
+  const float* beta;           /* [iters] */
+  const int32_t* band_start;   /* [num_mels] */
+  const int32_t* band_offset;  /* [num_mels + 1] */
+  const float* band_weight;    /* [n_weights] */
+  const int32_t* bin_first;    /* [num_bins] */
+  const int32_t* bin_offset;   /* [num_bins + 1] */
+  const float* bin_weight;     /* [n_tweights] */
+  float* out;                  /* [n_frames, num_bins] */
+} satt_mel_nnls_params;
+int satt_mel_nnls_supported(int num_bins, int num_mels, int iters);
+int satt_mel_nnls(const satt_mel_nnls_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

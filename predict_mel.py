@@ -4,7 +4,7 @@
 Usage: predict_mel.py --source-data-root=<dir> --target-data-root=<dir> --checkpoint-dir=<dir> --output-dir=<dir>
                       --selected-list-dir=<dir> [--checkpoint=<file>] [--selected-list-filename=<name>]
                       [--hparams=<a=b>] [--hparam-json-file=<path>] [--batch-size=<N>] [--stop-per-utterance]
-                      [--wav] [--griffin-lim-iters=<N>] [--griffin-lim-power=<P>]
+                      [--wav] [--griffin-lim-iters=<N>] [--griffin-lim-power=<P>] [--inversion=pinv|nnls] [--nnls-iters=<N>]
 
 For every key of the list: free-running decode (batch size 1) from `model-<step>.pt`, output `<key>.mfbsp` (raw
 little-endian float32 [T, num_mels]; the PostNetV2 output when `use_postnet_v2`, models/models.py:440-462), `<key>.alignment.npz` + `<key>.png` (the
@@ -13,7 +13,8 @@ reference's prediction record, utils/tfrecord.py:135-152).  `use_forced_alignmen
 pass 1 is the validation decode fed with the GROUND-TRUTH mel (needs --target-data-root), pass 2 feeds its own outputs
 back while both attention mechanisms return pass 1's alignments.  `--batch-size N` (forced-alignment mode only) decodes N
 utterances per pass; `--batch-size N --stop-per-utterance` decodes N free-running utterances at once, each ending at its own stop
-token.  `--wav` adds `<key>.wav`: Griffin-Lim phase reconstruction of the de-normalised mel (csrc/griffin_lim.hip).
+token.  `--wav` adds `<key>.wav`: Griffin-Lim phase reconstruction of the de-normalised mel (csrc/griffin_lim.hip); with
+`--inversion nnls` its magnitudes come from the non-negative mel inversion (csrc/mel_nnls.hip) instead of the floored pseudo-inverse.
 Usage: see --help"""
 import argparse
 import glob
@@ -50,7 +51,13 @@ def main(argv=None):
     ap.add_argument("--griffin-lim-iters", type=int, default=60, metavar="N", help="Griffin-Lim iterations of --wav (default 60)")
     ap.add_argument("--griffin-lim-power", type=float, default=1.0, metavar="P",
                     help="exponent on the linear magnitudes of --wav (default 1.0)")
+    ap.add_argument("--inversion", choices=("pinv", "nnls"), default="pinv",
+                    help="mel -> linear magnitudes of --wav: the floored pseudo-inverse (default) or the non-negative solve that starts "
+                         "from it")
+    ap.add_argument("--nnls-iters", type=int, default=64, metavar="N", help="iterations of --inversion nnls (default 64)")
     a = ap.parse_args(argv)
+    if not 0 <= a.nnls_iters <= 1024:
+        raise SystemExit("--nnls-iters: 0 .. 1024")
     if not 1 <= a.batch_size <= 16:
         raise SystemExit("--batch-size: 1 .. 16")
     if a.griffin_lim_iters < 0:
@@ -114,7 +121,8 @@ def main(argv=None):
         mel.tofile(os.path.join(a.output_dir, "%s.%s" % (key, hparams.predicted_mel_extension)))
         if audio is not None:
             audio.save_wav_pcm16(audio.inv_melspectrogram(audio.denormalize_mel(mel).T, iters=a.griffin_lim_iters,
-                                                          power=a.griffin_lim_power), os.path.join(a.output_dir, "%s.wav" % key))
+                                                          power=a.griffin_lim_power, inversion=a.inversion, nnls_iters=a.nnls_iters),
+                                 os.path.join(a.output_dir, "%s.wav" % key))
         # [T_memory, T_query]; the single-source baseline model has one history (reference models/models.py:196-212)
         aligns = [p[k] for k in ("alignment", "alignment2") if k in p]
         np.savez(os.path.join(a.output_dir, "%s.alignment.npz" % key), **{k: p[k] for k in ("alignment", "alignment2") if k in p})

@@ -197,6 +197,14 @@ class F0ViterbiParams(C.Structure):
                 [(n, C.c_void_p) for n in ("cand_period", "cand_value", "gate", "frame_offsets", "f0", "state", "cost")])
 
 
+class MelNnlsParams(C.Structure):
+    """satt_mel_nnls_params (include/satt_hip.h): non-negative inversion of the mel basis for a batch of frames"""
+    _fields_ = ([(n, C.c_int) for n in ("num_bins", "num_mels", "iters", "n_weights", "n_tweights")] + [("step", C.c_float)] +
+                [("n_frames", c_i64)] +
+                [(n, C.c_void_p) for n in ("amp", "start", "beta", "band_start", "band_offset", "band_weight", "bin_first",
+                                           "bin_offset", "bin_weight", "out")])
+
+
 # name -> (restype, argtypes); must list EVERY symbol declared in include/satt_hip.h
 _P = C.c_void_p
 _I = C.c_int
@@ -346,6 +354,8 @@ SIGNATURES = {
     "satt_f0_viterbi_supported": (_I, [_I]),
     "satt_f0_viterbi_max_frames": (_I, []),
     "satt_f0_viterbi": (_I, [C.POINTER(F0ViterbiParams), _P]),
+    "satt_mel_nnls_supported": (_I, [_I, _I, _I]),
+    "satt_mel_nnls": (_I, [C.POINTER(MelNnlsParams), _P]),
     "satt_l2_reg": (_I, [_P, _P, _P, _I, _F, _P, _P, _P]),
     "satt_sumsq": (_I, [_P, c_i64, _P, _P]),
     "satt_sumsq_state_floats": (_I, []),

@@ -5,7 +5,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["gemm.hip", "gemm_tile.hip", "flash.hip", "small_attn.hip", "elementwise.hip", "accent_prenet.hip", "speaker_cond.hip", "highway.hip", "lstm.hip", "lstm_cluster.hip", "attn_rnn.hip", "attn_cluster.hip", "decode.hip", "decode_mega2.hip", "decode_ends.hip", "melspec.hip", "griffin_lim.hip", "resample.hip", "dtw.hip", "yin.hip", "f0_viterbi.hip", "api.hip"]
+SOURCES = ["gemm.hip", "gemm_tile.hip", "flash.hip", "small_attn.hip", "elementwise.hip", "accent_prenet.hip", "speaker_cond.hip", "highway.hip", "lstm.hip", "lstm_cluster.hip", "attn_rnn.hip", "attn_cluster.hip", "decode.hip", "decode_mega2.hip", "decode_ends.hip", "melspec.hip", "griffin_lim.hip", "resample.hip", "dtw.hip", "yin.hip", "f0_viterbi.hip", "mel_nnls.hip", "api.hip"]
 OUT = os.path.join(os.path.dirname(HERE), "libsatt_hip.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc"] + os.environ.get("SATT_EXTRA_FLAGS", "").split()
 

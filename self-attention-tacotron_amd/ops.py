@@ -575,6 +575,37 @@ def yin_candidates(signal, in_offsets, frame_offsets, window, tau_min, tau_max, 
     _lib.check(_lib.lib().satt_yin_candidates(C.byref(p), _s()), "yin_candidates")
 
 
+def mel_nnls_supported(num_bins, num_mels, iters):
+    """True when satt_mel_nnls takes this many bins, bands and iterations (host-only: needs the library, not a GPU)"""
+    return bool(_lib.lib().satt_mel_nnls_supported(int(num_bins), int(num_mels), int(iters)))
+
+
+def mel_nnls(amp, start, beta, step, band_start, band_offset, band_weight, bin_first, bin_offset, bin_weight, out):
+    """non-negative inversion of the mel basis for a batch of frames in one launch (csrc/mel_nnls.hip).  amp: fp32 [N, num_mels],
+    start and out: fp32 [N, num_bins], beta: fp32 [iters]; the banded basis and its transposed table are those of utils/audio.py
+    MelNnlsTables.  Sizes outside satt_mel_nnls_supported raise."""
+    assert amp.dtype == torch.float32 and amp.dim() == 2 and amp.is_contiguous()
+    N, M = amp.shape
+    for o in (start, out):
+        assert o.dtype == torch.float32 and o.dim() == 2 and o.is_contiguous() and o.shape[0] == N and o.shape[1] == start.shape[1]
+    F = start.shape[1]
+    assert beta.dtype == torch.float32 and beta.dim() == 1 and beta.is_contiguous()
+    for o in (band_start, band_offset, bin_first, bin_offset):
+        assert o.dtype == torch.int32 and o.dim() == 1 and o.is_contiguous()
+    assert band_start.numel() == M and band_offset.numel() == M + 1 and bin_first.numel() == F and bin_offset.numel() == F + 1
+    for o in (band_weight, bin_weight):
+        assert o.dtype == torch.float32 and o.dim() == 1 and o.is_contiguous()
+    iters = beta.numel()
+    if not mel_nnls_supported(F, M, iters) or N < 1:
+        raise ValueError("mel_nnls does not take num_bins=%d num_mels=%d iters=%d frames=%d (num_bins <= 2049, num_mels <= 128, "
+                         "1 <= iters <= 1024, frames >= 1)" % (F, M, iters, N))
+    p = _lib.MelNnlsParams(num_bins=F, num_mels=M, iters=iters, n_weights=band_weight.numel(), n_tweights=bin_weight.numel(),
+                           step=float(step), n_frames=N, amp=_p(amp), start=_p(start), beta=_p(beta), band_start=_p(band_start),
+                           band_offset=_p(band_offset), band_weight=_p(band_weight), bin_first=_p(bin_first),
+                           bin_offset=_p(bin_offset), bin_weight=_p(bin_weight), out=_p(out))
+    _lib.check(_lib.lib().satt_mel_nnls(C.byref(p), _s()), "mel_nnls")
+
+
 def f0_viterbi_supported(max_frames):
     """True when satt_f0_viterbi takes utterances of up to this many frames (host-only: needs the library, not a GPU)"""
     return bool(_lib.lib().satt_f0_viterbi_supported(int(max_frames)))

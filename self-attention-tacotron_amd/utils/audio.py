@@ -7,7 +7,8 @@ of the two rates, in csrc/resample.hip or as a float32 NumPy restatement on the 
 backends agree bit for bit; DESIGN.md 3.6 holds the definition; it is not librosa's bits).  Without it a wav whose rate differs
 from hparams.sample_rate is refused.
 The way back - `inv_melspectrogram`: the pseudo-inverse of the mel basis and Griffin-Lim phase reconstruction - runs in
-csrc/griffin_lim.hip or as the same kind of restatement; it is a quick listen, not a vocoder."""
+csrc/griffin_lim.hip or as the same kind of restatement; it is a quick listen, not a vocoder.  Opt-in (`inversion="nnls"`), the
+floored pseudo-inverse is refined by a non-negative solve in csrc/mel_nnls.hip, or in float32 NumPy with the kernel's bits."""
 import math
 
 import numpy as np
@@ -89,6 +90,7 @@ class MelspecTables:
         self.twiddle = twiddles(n_fft)
         self._dev = {}
         self._basis_pinv = None              # mel_to_linear's, computed on first use
+        self._nnls = None                    # mel_nnls_tables', built on first use
 
     def device(self, device):
         import torch
@@ -277,16 +279,252 @@ def griffin_lim_hip(tables, mags, ang0s, iters, alpha, device="cuda", c_prevs=No
     return ys, down(ang), down(prev), down(spec)
 
 
-def mel_to_linear(tables, S_db, ref_level_db, power=1.0):
+def _mel_amp_and_start(tables, S_db, ref_level_db):
+    """(amp, amp @ pinv(basis).T), both float64: the band amplitudes of a dB mel spectrogram and their least-norm spectrum, the
+    pseudo-inverse computed once per table"""
+    if tables._basis_pinv is None:
+        tables._basis_pinv = np.linalg.pinv(tables.basis)
+    amp = 10.0 ** ((np.asarray(S_db, np.float64) + ref_level_db) / 20.0)
+    return amp, amp @ tables._basis_pinv.T
+
+
+# ---- non-negative mel inversion (csrc/mel_nnls.hip, or float32 NumPy in the kernel's order) ------------------------------------------
+#
+# One frame with band amplitudes a (float32 [M]) and the start x_0 (float32 [F], the floored pseudo-inverse); W the float32 banded
+# basis (band_start / band_offset / band_weight, the operator csrc/melspec.hip applies).  K iterations of accelerated projected
+# gradient on min_{x >= 0} |W x - a|^2 / 2 (DESIGN.md 3.6):
+#   y_1 = x_0;  for k = 1 .. K:  p = W y_k;  r = p - a;  g = W^T r;  v = y_k - step g;  x_k = v > 0 ? v : 0;
+#                                y_k+1 = x_k + beta_k (x_k - x_k-1);     result x_K
+# every product, difference and sum rounded to float32.  p[m]: lane j = 0 .. 15 sums the band's terms j, j + 16, .. ascending in one
+# chain from +0, the 16 partial sums are joined by the adjacent pairwise tree ((s0 + s1) + (s2 + s3)) + ..; g[f]: one chain from +0
+# over the bin's bands, ascending.  A fixed K keeps the bits reproducible: there is no stopping rule.
+
+MEL_NNLS_ITERS = 64                   # the default K (profiles/mel_nnls_quality.txt)
+MEL_NNLS_TEAM = 16                    # lanes that share a band's sum
+MEL_NNLS_MAX_BINS, MEL_NNLS_MAX_MELS, MEL_NNLS_MAX_ITERS = 2049, 128, 1024          # satt_mel_nnls_supported's bounds
+MEL_NNLS_NUMPY_BLOCK = 64             # frames solved at a time by mel_nnls_numpy (the temporaries stay in cache)
+
+
+def transposed_banded(band_start, band_offset, band_weight, num_bins):
+    """the banded basis seen from the bins: (first int32 [F], offset int32 [F + 1], weight float32 [offset[F]]).  Bin f lies under
+    the bands first[f] .. first[f] + c - 1, c = offset[f + 1] - offset[f]: from the first to the last band that holds a non-zero
+    weight for it, bands ascending; a band of that range without one has weight 0.  A bin under no band has c = 0.  The weights are
+    the float32 values of band_weight themselves; an empty table keeps one zero weight."""
+    M = len(band_start)
+    lo = np.full(num_bins, M, np.int64)
+    hi = np.full(num_bins, -1, np.int64)
+    for m in range(M):
+        w = band_weight[band_offset[m]:band_offset[m + 1]]
+        f = int(band_start[m]) + np.nonzero(w)[0]
+        lo[f] = np.minimum(lo[f], m)
+        hi[f] = np.maximum(hi[f], m)
+    count = np.where(hi >= 0, hi - lo + 1, 0)
+    offset = np.concatenate([[0], np.cumsum(count)])
+    weight = np.zeros(max(1, int(offset[-1])), np.float32)
+    for m in range(M):
+        s, n = int(band_start[m]), int(band_offset[m + 1] - band_offset[m])
+        f = s + np.arange(n)
+        inside = (count[f] > 0) & (lo[f] <= m) & (m <= hi[f])
+        weight[offset[f[inside]] + m - lo[f[inside]]] = band_weight[band_offset[m]:band_offset[m + 1]][inside]
+    first = np.where(count > 0, lo, 0)
+    return first.astype(np.int32), offset.astype(np.int32), weight
+
+
+class MelNnlsTables:
+    """what the non-negative inversion needs beside the banded basis: its transposed table (transposed_banded), `step` and
+    beta(K), and the gather tables of the NumPy backend; device copies are made on first use.
+      step = float32(1 / L), L the largest eigenvalue of W W^T in float64 from the float32 weights; the next float32 towards 0
+             when float64(step) * L > 1
+      beta_k = float32((t_k - 1) / t_k+1), t_1 = 1, t_k+1 = (1 + sqrt(1 + 4 t_k^2)) / 2 in float64"""
+
+    def __init__(self, band_start, band_offset, band_weight, num_bins):
+        self.band_start = np.ascontiguousarray(band_start, np.int32)
+        self.band_offset = np.ascontiguousarray(band_offset, np.int32)
+        self.band_weight = np.ascontiguousarray(band_weight, np.float32)
+        self.num_bins, self.num_mels = int(num_bins), len(self.band_start)
+        M, F = self.num_mels, self.num_bins
+        length = np.diff(self.band_offset)
+        if len(self.band_offset) != M + 1 or (length < 0).any() or self.band_offset[0] < 0 or self.band_offset[-1] > len(self.band_weight) \
+                or (self.band_start < 0).any() or (self.band_start + length > F).any():
+            raise ValueError("mel_nnls: the banded table does not lie inside %d bins / %d weights" % (F, len(self.band_weight)))
+        self.bin_first, self.bin_offset, self.bin_weight = transposed_banded(self.band_start, self.band_offset, self.band_weight, F)
+        dense = self.dense()
+        L = float(np.linalg.eigvalsh(dense @ dense.T)[-1])
+        if not (L > 0.0 and math.isfinite(L)):
+            raise ValueError("mel_nnls: the basis has no positive weight")
+        step = np.float32(1.0 / L)
+        if float(step) * L > 1.0:
+            step = np.nextafter(step, np.float32(0.0))
+        self.lipschitz, self.step = L, np.float32(step)
+        # the NumPy backend's gathers: band m's terms padded to rounds of MEL_NNLS_TEAM lanes, a bin's bands to the widest count.  A
+        # padded term multiplies weight 0 with the zero appended behind y / r: it adds +0, which changes no bit of a chain that
+        # started from +0
+        R = max(1, -(-int(length.max()) // MEL_NNLS_TEAM))
+        i = np.arange(R * MEL_NNLS_TEAM)[None, :]
+        live = i < length[:, None]
+        self._w_pad = np.where(live, self.band_weight[np.where(live, self.band_offset[:-1, None] + i, 0)], np.float32(0)) \
+            .astype(np.float32).reshape(M, R, MEL_NNLS_TEAM)
+        self._y_idx = np.where(live, self.band_start[:, None] + i, F).reshape(M, R, MEL_NNLS_TEAM)
+        count = np.diff(self.bin_offset)
+        C = max(1, int(count.max()))
+        c = np.arange(C)[None, :]
+        live = c < count[:, None]
+        self._tw_pad = np.where(live, self.bin_weight[np.where(live, self.bin_offset[:-1, None] + c, 0)], np.float32(0)).astype(np.float32)
+        self._r_idx = np.where(live, self.bin_first[:, None] + c, M)
+        self._beta, self._dev = np.zeros(0, np.float32), {}
+
+    def dense(self):
+        """float64 [M, F] from the float32 banded weights"""
+        B = np.zeros((self.num_mels, self.num_bins))
+        for m in range(self.num_mels):
+            n = self.band_offset[m + 1] - self.band_offset[m]
+            B[m, self.band_start[m]:self.band_start[m] + n] = self.band_weight[self.band_offset[m]:self.band_offset[m + 1]]
+        return B
+
+    def dense_transposed(self):
+        """float64 [F, M] from the transposed table"""
+        Bt = np.zeros((self.num_bins, self.num_mels))
+        for f in range(self.num_bins):
+            n = self.bin_offset[f + 1] - self.bin_offset[f]
+            Bt[f, self.bin_first[f]:self.bin_first[f] + n] = self.bin_weight[self.bin_offset[f]:self.bin_offset[f + 1]]
+        return Bt
+
+    def beta(self, iters):
+        """float32 [iters]; a longer table begins with the shorter one"""
+        if len(self._beta) < iters:
+            t, out = 1.0, []
+            for _ in range(iters):
+                t_next = (1.0 + math.sqrt(1.0 + 4.0 * t * t)) / 2.0
+                out.append((t - 1.0) / t_next)
+                t = t_next
+            self._beta = np.asarray(out, np.float64).astype(np.float32)
+        return self._beta[:iters]
+
+    def device(self, device):
+        import torch
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = {k: torch.from_numpy(getattr(self, k)).to(device)
+                              for k in ("band_start", "band_offset", "band_weight", "bin_first", "bin_offset", "bin_weight")}
+        return self._dev[key]
+
+
+def mel_nnls_tables(tables):
+    """the MelNnlsTables of a MelspecTables, built on first use and kept on it"""
+    nt = getattr(tables, "_nnls", None)
+    if nt is None:
+        nt = tables._nnls = MelNnlsTables(tables.band_start, tables.band_offset, tables.band_weight, tables.n_fft // 2 + 1)
+    return nt
+
+
+def mel_nnls_check(nnls, amp, x0, iters):
+    """(amp, x0) as contiguous float32 [N, M] and [N, F]; raises ValueError naming what csrc/mel_nnls.hip (and the NumPy
+    restatement) does not take"""
+    amp, x0 = np.ascontiguousarray(amp, np.float32), np.ascontiguousarray(x0, np.float32)
+    if amp.ndim != 2 or x0.ndim != 2 or amp.shape != (len(x0), nnls.num_mels) or x0.shape[1] != nnls.num_bins or len(x0) < 1:
+        raise ValueError("mel_nnls: amplitudes %r and starts %r, need [N, %d] and [N, %d] with N >= 1"
+                         % (amp.shape, x0.shape, nnls.num_mels, nnls.num_bins))
+    if not (nnls.num_bins <= MEL_NNLS_MAX_BINS and nnls.num_mels <= MEL_NNLS_MAX_MELS and 1 <= iters <= MEL_NNLS_MAX_ITERS):
+        raise ValueError("mel_nnls: num_bins=%d num_mels=%d iters=%d is outside num_bins <= %d, num_mels <= %d, 1 <= iters <= %d"
+                         % (nnls.num_bins, nnls.num_mels, iters, MEL_NNLS_MAX_BINS, MEL_NNLS_MAX_MELS, MEL_NNLS_MAX_ITERS))
+    return amp, x0
+
+
+def mel_nnls_numpy(nnls, amp, x0, iters):
+    """float32 [N, F]: x_K of every frame, with the kernel's operations in the kernel's order - the bits of csrc/mel_nnls.hip.
+    Vectorised over the frames (MEL_NNLS_NUMPY_BLOCK at a time), the bands and the bins; the loops are the chains' steps."""
+    t = nnls
+    amp, x0 = mel_nnls_check(t, amp, x0, iters)
+    beta, step, zero = t.beta(iters), t.step, np.float32(0)
+    out = np.empty_like(x0)
+    R, C = t._w_pad.shape[1], t._tw_pad.shape[1]
+    with np.errstate(all="ignore"):
+        for n0 in range(0, len(x0), MEL_NNLS_NUMPY_BLOCK):
+            a = amp[n0:n0 + MEL_NNLS_NUMPY_BLOCK]
+            x = x0[n0:n0 + MEL_NNLS_NUMPY_BLOCK].copy()
+            y = x.copy()
+            n = len(x)
+            y_ext, r_ext = np.zeros((n, t.num_bins + 1), np.float32), np.zeros((n, t.num_mels + 1), np.float32)
+            for k in range(iters):
+                y_ext[:, :-1] = y
+                s = np.zeros((n, t.num_mels, MEL_NNLS_TEAM), np.float32)
+                for i in range(R):                                     # a lane's chain: its terms ascending
+                    s = s + t._w_pad[None, :, i, :] * y_ext[:, t._y_idx[:, i, :]]
+                while s.shape[2] > 1:                                  # the adjacent pairwise tree
+                    s = s[:, :, 0::2] + s[:, :, 1::2]
+                r_ext[:, :-1] = s[:, :, 0] - a
+                g = np.zeros_like(x)
+                for c in range(C):                                     # a bin's chain: its bands ascending
+                    g = g + t._tw_pad[None, :, c] * r_ext[:, t._r_idx[:, c]]
+                v = y - step * g
+                xn = np.where(v > zero, v, zero)
+                y = xn + beta[k] * (xn - x)
+                x = xn
+            out[n0:n0 + n] = x
+    return out
+
+
+def mel_nnls_hip(nnls, amp, x0, iters, device="cuda", max_launch_frames=None):
+    """the same on csrc/mel_nnls.hip: one launch per group of at most max_launch_frames frames (default: all in one)"""
+    import torch
+    from .. import ops
+    t = nnls
+    amp, x0 = mel_nnls_check(t, amp, x0, iters)
+    d = t.device(device)
+    beta = torch.from_numpy(np.ascontiguousarray(t.beta(iters))).to(device)
+    N = len(x0)
+    group = N if max_launch_frames is None else max(1, int(max_launch_frames))
+    out = np.empty_like(x0)
+    up = lambda v: torch.from_numpy(v if v.flags.writeable else v.copy()).to(device)
+    for n0 in range(0, N, group):
+        a, s = up(amp[n0:n0 + group]), up(x0[n0:n0 + group])
+        o = torch.empty_like(s)
+        ops.mel_nnls(a, s, beta, float(t.step), d["band_start"], d["band_offset"], d["band_weight"], d["bin_first"], d["bin_offset"],
+                     d["bin_weight"], o)
+        out[n0:n0 + group] = o.cpu().numpy()
+    return out
+
+
+def mel_to_linear_batch(tables, Ss_db, ref_level_db, power=1.0, *, inversion="pinv", nnls_iters=MEL_NNLS_ITERS, backend="numpy",
+                        device="cuda"):
+    """mel_to_linear of a list of dB mel spectrograms.  With inversion="nnls" the frames of all of them are solved together (on
+    "hip": one launch per MAX_LAUNCH_SAMPLES // hop frames); a frame's result does not depend on what shares its batch."""
+    if inversion not in ("pinv", "nnls"):
+        raise ValueError("inversion must be 'pinv' or 'nnls', got %r" % (inversion,))
+    if backend not in ("hip", "numpy"):
+        raise ValueError("backend must be 'hip' or 'numpy', got %r" % (backend,))
+    if nnls_iters < 0:
+        raise ValueError("nnls_iters must be >= 0, got %d" % nnls_iters)
+    pairs = [_mel_amp_and_start(tables, S, ref_level_db) for S in Ss_db]
+    if inversion == "pinv" or nnls_iters == 0 or not pairs:
+        return [np.maximum(1e-10, lin) ** power for _, lin in pairs]
+    for amp, _ in pairs:
+        if amp.ndim != 2:
+            raise ValueError("mel_to_linear: inversion='nnls' takes [T, num_mels] spectrograms, got shape %r" % (amp.shape,))
+    nt = mel_nnls_tables(tables)
+    amp = np.concatenate([a for a, _ in pairs]).astype(np.float32)
+    x0 = np.concatenate([np.maximum(1e-10, lin) for _, lin in pairs]).astype(np.float32)
+    if backend == "numpy":
+        x = mel_nnls_numpy(nt, amp, x0, nnls_iters)
+    else:
+        x = mel_nnls_hip(nt, amp, x0, nnls_iters, device, max(1, MAX_LAUNCH_SAMPLES // tables.hop))
+    x = np.maximum(1e-10, x.astype(np.float64)) ** power
+    ends = np.cumsum([len(a) for a, _ in pairs])
+    return [x[e - len(a):e] for (a, _), e in zip(pairs, ends)]
+
+
+def mel_to_linear(tables, S_db, ref_level_db, power=1.0, *, inversion="pinv", nnls_iters=MEL_NNLS_ITERS, backend="numpy", device="cuda"):
     """float64 [T, n_fft / 2 + 1] linear magnitudes of a dB mel spectrogram [T, num_mels] (Audio.melspectrogram's scale):
         amp = 10 ** ((S + ref_level_db) / 20);   mag = max(1e-10, amp @ pinv(basis).T) ** power
     The mel basis maps n_fft / 2 + 1 bins onto num_mels bands and is NOT invertible: the Moore-Penrose pseudo-inverse picks, among
     the spectra with these band amplitudes, the one of least norm (the least-squares choice, librosa's mel_to_stft without its
-    non-negative solver) and the floor removes what it leaves negative.  The pseudo-inverse is computed once per table, in float64."""
-    if tables._basis_pinv is None:
-        tables._basis_pinv = np.linalg.pinv(tables.basis)
-    amp = 10.0 ** ((np.asarray(S_db, np.float64) + ref_level_db) / 20.0)
-    return np.maximum(1e-10, amp @ tables._basis_pinv.T) ** power
+    non-negative solver) and the floor removes what it leaves negative.  The pseudo-inverse is computed once per table, in float64.
+    The floored spectrum no longer has the band amplitudes asked for.  inversion="nnls" starts from it (rounded to float32) and
+    runs nnls_iters iterations of accelerated projected gradient on |W x - amp|^2 over x >= 0 (mel_nnls_numpy / mel_nnls_hip by
+    `backend`, the same bits), then applies max(1e-10, .) ** power in float64.  nnls_iters = 0 is the
+    pseudo-inverse path, bit for bit."""
+    return mel_to_linear_batch(tables, [S_db], ref_level_db, power, inversion=inversion, nnls_iters=nnls_iters, backend=backend,
+                               device=device)[0]
 
 
 # ---- sample-rate conversion (csrc/resample.hip, or float32 NumPy on the same table) -------------------------------------------------
@@ -564,13 +802,15 @@ class Audio:
         """the inverse of normalize_mel: dB values from what the model predicts"""
         return S * self.stddev_mel_level_db + self.average_mel_level_db
 
-    def inv_melspectrogram_batch(self, Ss, iters=60, alpha=0.99, power=1.0, seed=0):
+    def inv_melspectrogram_batch(self, Ss, iters=60, alpha=0.99, power=1.0, seed=0, inversion="pinv", nnls_iters=MEL_NNLS_ITERS):
         """list of float32 signals of (T - 1) hop samples, one per dB mel spectrogram [T, num_mels] (melspectrogram_batch's layout):
         mel_to_linear, then `iters` Griffin-Lim iterations from a phase drawn uniformly on the host by np.random.default_rng(seed)
-        - for every utterance afresh, so that neither the backend nor the batch changes the numbers it starts from."""
+        - for every utterance afresh, so that neither the backend nor the batch changes the numbers it starts from.
+        inversion="nnls": the non-negative mel inversion of mel_to_linear with nnls_iters iterations, the frames of all utterances
+        solved together on this Audio's backend."""
         t = self.tables
         griffin_lim_check(t, [len(S) for S in Ss])
-        mags = [mel_to_linear(t, S, self.hparams.ref_level_db, power).astype(np.float32) for S in Ss]
+        mags = [m.astype(np.float32) for m in self.mel_to_linear_batch(Ss, power, inversion, nnls_iters)]
         angs = [np.exp(2j * np.pi * np.random.default_rng(seed).random(m.shape)).astype(np.complex64) for m in mags]
         if self.backend == "numpy":
             return [griffin_lim_numpy(t, m, a, iters, alpha) for m, a in zip(mags, angs)]
@@ -585,6 +825,12 @@ class Audio:
         if group:
             out += griffin_lim_hip(t, [g[0] for g in group], [g[1] for g in group], iters, alpha, self.device)
         return out
+
+    def mel_to_linear_batch(self, Ss, power=1.0, inversion="pinv", nnls_iters=MEL_NNLS_ITERS):
+        """float64 linear magnitudes [T, n_fft / 2 + 1] of every dB mel spectrogram [T, num_mels]: what inv_melspectrogram_batch hands
+        (as float32) to Griffin-Lim"""
+        return mel_to_linear_batch(self.tables, Ss, self.hparams.ref_level_db, power, inversion=inversion, nnls_iters=nnls_iters,
+                                   backend=self.backend, device=self.device)
 
     def mel_distance_batch(self, preds, refs, feature="mcep", order=13, want_paths=False, keys=None):
         """DTW distance of every (predicted, ground-truth) pair of NORMALISED mels [T, num_mels] (what .mfbsp files and the prediction
@@ -660,9 +906,9 @@ class Audio:
             res = pitch.yin_hip(ys, sr, hop, device=self.device, **kw) if len(ys) else []
         return [dict(f0=f0, voiced=pitch.voicing(f0, power, silence_db), aperiodicity=ap, power=power) for f0, ap, power in res]
 
-    def inv_melspectrogram(self, S, iters=60, alpha=0.99, power=1.0, seed=0):
+    def inv_melspectrogram(self, S, iters=60, alpha=0.99, power=1.0, seed=0, inversion="pinv", nnls_iters=MEL_NNLS_ITERS):
         """float32 [(T - 1) hop] from one dB mel spectrogram [num_mels, T], the layout melspectrogram returns"""
-        return self.inv_melspectrogram_batch([np.asarray(S).T], iters, alpha, power, seed)[0]
+        return self.inv_melspectrogram_batch([np.asarray(S).T], iters, alpha, power, seed, inversion, nnls_iters)[0]
 
 
 def _gpu_bound():
