@@ -362,6 +362,11 @@ int satt_flash_attn_bwd_tiles_b(const uint16_t* kb, const uint16_t* vb, const ui
  * lengths[B] or NULL; direction 1 (if ndir==2) runs reversed over [0,len)
  * hout   [B,T,ld_hout] cell outputs h' (pre-zoneout), direction d written at column d*H; zero beyond len
  * saved for backward: gates [ndir,B,T,4H] (sigmoid(i),tanh(j),sigmoid(f+1),sigmoid(o)), cnew/cstate/hstate [ndir,B,T,H]
+ *        (cnew = c', cstate / hstate = the carried state after zoneout); all of them zero beyond len, as hout
+ * H accepted: satt_lstm_fwd every EVEN H <= 1024, satt_lstm_bwd every H % 8 == 0, H <= 1024; anything else is
+ * SATT_E_UNSUPPORTED (a layer that trains needs H % 8 == 0: the forward alone also runs H = 12 or 132).  H <= 128 takes the
+ * register-resident kernels, larger H the streaming ones.  ndir outside {1, 2}, B <= 0, T <= 0: SATT_E_BADARG.
+ * lengths[b] in [0, T]; 0 writes zeros only.
  */
 int satt_lstm_fwd(const float* xg, const uint16_t* Wh, const int64_t* lengths, int ndir, int B, int T, int H,
                   int training, float zc, float zh, uint32_t zc_thresh, uint32_t zh_thresh,

@@ -928,6 +928,7 @@ def _u32arr(vals):
 
 def lstm_fwd(xg, Wh, lengths, ndir, B, T, H, training, zc, zh, seed, streams_c, streams_h, hout, gates, cnew,
              cstate, hstate):
+    """satt_lstm_fwd: every even H <= 1024 (H <= 128: register-resident kernel, else streaming); SattError otherwise"""
     zct, _ = rate_thresh(zc if training else 0.0)
     zht, _ = rate_thresh(zh if training else 0.0)
     _lib.check(_lib.lib().satt_lstm_fwd(_p(xg), _p(Wh), _p(lengths), ndir, B, T, H, int(training), zc, zh, zct, zht,
@@ -937,6 +938,7 @@ def lstm_fwd(xg, Wh, lengths, ndir, B, T, H, training, zc, zh, seed, streams_c, 
 
 def lstm_bwd(dhout, WhT, lengths, ndir, B, T, H, training, zc, zh, seed, streams_c, streams_h, gates, cnew, cstate,
              dxg):
+    """satt_lstm_bwd: H % 8 == 0, H <= 1024 (narrower than the forward, which takes every even H); SattError otherwise"""
     zct, _ = rate_thresh(zc if training else 0.0)
     zht, _ = rate_thresh(zh if training else 0.0)
     _lib.check(_lib.lib().satt_lstm_bwd(_p(dhout), _ld(dhout), _p(WhT), _p(lengths), ndir, B, T, H, int(training), zc,
